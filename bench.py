@@ -11,9 +11,9 @@ the packed tiles to rank 0. The frame is fixed as N grows: "sca
   is one rank; WORLD_SIZE must equal --gpus, else bench.py exits with status 2 before touching a GPU.
 - `python bench.py --gpus N` (N > 1, no WORLD_SIZE) starts that same torch.distributed.run as a child process before
   any GPU call (no exec), relays its output and exits with its status, so an N-GPU request is always N ranks.
-- The N > 1 line carries n_gpus as RCCL's communicator reports it (ncclCommCount), per-rank frame and render-kernel
-  times (min / max over ranks), and the exchange time per frame (gather + rank 0's unpack, HIP events on the comm
-  stream).
+- The N > 1 line carries n_gpus as RCCL's communicator reports it (ncclCommCount) and the per-rank frame times
+  (min / max over ranks); with --full also the per-rank render-kernel times and the exchange time per frame (gather +
+  rank 0's unpack, HIP events on the comm stream).
 
 Warm-up: W frames as asked (in chunks of 8, each ended by a synchronisation), continued until the warm-up has
 rendered for --warmup-min-s seconds (0.3 s by default); with N ranks every rank runs the same chunks (an all-reduce
@@ -21,7 +21,13 @@ decides when all are done). The MI355X lowers its clock when the render load sta
 (1.96 -> 2.36 GHz, profiles/archive/r02_clock_ramp.txt); a timed region that starts inside the ramp measures the
 DVFS governor, not the kernels. The JSON line reports W and the frames the warm-up actually ran.
 
-Extra JSON objects:
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: the
+timed frames carry no HIP events and nothing else is rendered or measured. `--dump-outputs DIR` also writes what the
+last timed step left its caller (dump_outputs below). Everything else is measured only with `--full`: the counting
+pass and the render kernel's HIP events (roofline, per-rank kernel and exchange times), the serialised frames after the
+timed region, the steady-state LBVH rebuild (config.bvh_build_ms), the N-rank sharded_frame_check and the CPU baseline.
+
+Extra JSON objects (with --full):
 - roofline: the shading kernel k_render_cor is VALU-issue bound. `achieved` = the
   algorithmic FP32 operations of the frame (per ray, per AABB candidate |C_r| and per blended hit |H_r|,
   from the counting pass; the per-op tables OPS_* below, an FMA counted as 2 FLOP like the peak) / the kernel's
@@ -108,6 +114,12 @@ def parse():
     ap.add_argument("--warmup-min-s", type=float, default=0.3,
                     help="keep warming up until this many seconds of frames ran (DVFS clock ramp)")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the counting pass and kernel events "
+                         "(roofline, per-rank kernel / exchange times), the serialised kernel time, the LBVH rebuild "
+                         "time, the sharded frame check and the CPU baseline (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU baseline sample length")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stats", action="store_true", help="skip the counting pass (roofline operations)")
@@ -126,7 +138,10 @@ def parse():
                     help="c5 with device-resident jitter sets: attach = the frame reads the set in place "
                          "(gsrt_scene_attach, the producer's arrays are the scene's), copy = gsrt_scene_update copies "
                          "it into the scene's own buffers first (360 MB device to device per frame)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_model() -> str:
@@ -385,8 +400,53 @@ def _compare_sharded(scene, ubo, mode, img):
                     "0 rendering the whole frame alone in RGBA32F, and the PPM dump of each"}
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SEED = 0
+
+
+def _dump_sample(a, budget):
+    """`a` (one entry per row) as it is when it fits `budget` bytes, else a fixed sample of its rows: those a
+    default_rng(DUMP_SEED) draws without replacement, in ascending order, the same for every run of the same shape."""
+    if a.nbytes <= budget:
+        return a
+    keep = budget // (a.nbytes // len(a))
+    return a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), keep, replace=False))]
+
+
+def dump_outputs(path, ctx, width, height):
+    """What the last timed step left for its caller, as float32 / float64 .npy files under `path`, DUMP_BYTES in all
+    at the most (rank 0 of a sharded run; the ctx must be synchronised):
+    - an RGBA32F frame: rgba.npy, float32 [H, W, 4], the ctx framebuffer (gsrt_framebuffer); a frame larger than the
+      budget is written as [K, 4], a fixed sample of its pixels (_dump_sample);
+    - a dump8 sharded frame (gsrt_dump8_read): codes.npy, float64 [H, W], the packed integers of the frame's PPM dump,
+      and escapes.npy, float64 [E, 4], (pixel, r, g, b) of every escaped pixel in pixel order."""
+    import ctypes
+
+    os.makedirs(path, exist_ok=True)
+    fb = ctx.framebuffer_ptr
+    if fb:
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        rgba = np.zeros((height, width, 4), np.float32)
+        err = hip.hipMemcpy(rgba.ctypes.data, fb, rgba.nbytes, 2)  # hipMemcpyDeviceToHost
+        if err:
+            raise RuntimeError(f"--dump-outputs: hipMemcpy of the framebuffer failed ({err})")
+        if rgba.nbytes > DUMP_BYTES:
+            rgba = _dump_sample(rgba.reshape(-1, 4), DUMP_BYTES)
+        np.save(os.path.join(path, "rgba.npy"), rgba)
+        return
+    codes, esc = ctx.dump8_read(width, height)
+    codes = codes.astype(np.float64)
+    if codes.nbytes > DUMP_BYTES // 2:
+        codes = _dump_sample(codes.reshape(-1, 1), DUMP_BYTES // 2)[:, 0]
+    esc = np.stack([esc[k].astype(np.float64) for k in ("pixel", "r", "g", "b")], axis=1)
+    np.save(os.path.join(path, "codes.npy"), codes)
+    np.save(os.path.join(path, "escapes.npy"), _dump_sample(esc, DUMP_BYTES // 2) if len(esc) else esc)
+
+
 def main():
     args = parse()
+    full = args.full
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, sys.argv[1:])
     if args.gpus < 1 or check_world(args):
@@ -420,13 +480,15 @@ def main():
     c, r, s, o, sh = gsrt.synth_cloud(gsrt.SYNTH_COR, n, 42, with_sh)
     scene = gsrt.Scene.from_model(ctx, c, r, s, o, sh)
     # the LBVH build (synchronous): the first one also pays the runtime's lazy load of the build kernels, the second
-    # is the steady-state cost of a rebuild
+    # (--full) is the steady-state cost of a rebuild
     tb = time.perf_counter()
     scene.build_bvh()
     bvh_cold_ms = (time.perf_counter() - tb) * 1e3
-    tb = time.perf_counter()
-    scene.build_bvh()
-    bvh_ms = (time.perf_counter() - tb) * 1e3
+    bvh_ms = None
+    if full:
+        tb = time.perf_counter()
+        scene.build_bvh()
+        bvh_ms = (time.perf_counter() - tb) * 1e3
     mv = gsrt.lookat((0, 0, 0), (0, 0, -1))
     ubo = gsrt.camera_from_modelview(mv, 60.0, W, H, 1.0, spp, 16)
     mode = gsrt.MODE_COR
@@ -502,7 +564,7 @@ def main():
 
     # counting pass for the algorithmic operations: |C_r|, |H_r| per ray
     stats = None
-    if not args.no_stats:
+    if full and not args.no_stats:
         scene.render_async(ubo, mode | gsrt.FLAG_STATS)
         ctx.synchronize()
         stats = ctx.last_stats((H, W))
@@ -515,7 +577,8 @@ def main():
             return bool(t[0])
     warm = warm_up(frame, ctx.synchronize, args.warmup, args.warmup_min_s, agree)
     warm_s = time.perf_counter() - tw
-    if not args.no_events:
+    events = full and not args.no_events
+    if events:
         # the render kernel's two events on every EVENT_STRIDE-th timed frame (no frame start / end events: the events
         # are what the line needs and no more; on every frame they cost the C3 frame ~1.2 %, profiles/r05/events_ab.txt)
         ctx.timing(-(-args.steps // EVENT_STRIDE), kernel_only=True, stride=EVENT_STRIDE)
@@ -534,9 +597,11 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     slot_streams = ctx.slot_streams()
-    kern_ms, frame_ms = ctx.timing_read() if not args.no_events else ([], [])
-    exch_ms = ctx.timing_read_exchange() if ((world > 1 or rank_of > 1) and not args.no_events) else []
+    kern_ms, frame_ms = ctx.timing_read() if events else ([], [])
+    exch_ms = ctx.timing_read_exchange() if ((world > 1 or rank_of > 1) and events) else []
     ctx.timing(0)
+    if args.dump_outputs and rank == 0:  # before anything else renders: the last timed step's frame
+        dump_outputs(args.dump_outputs, ctx, W, H)
     # the roofline needs the render kernel's own duration: when frames overlapped (slot streams), or its events span
     # more than a frame, time it again with frames serialised (after the timed region; not part of `value`)
     ser_ms = None
@@ -558,7 +623,7 @@ def main():
             return None if not len(v) else {"min": round(float(v.min()) * scale, 4), "max": round(float(v.max()) * scale, 4),
                                             "argmax_rank": int(np.argmax(allr[:, col]))}
         bands_used = ctx.last_bands()
-        frame_check = sharded_frame_check(scene, ubo, smode, rank)
+        frame_check = sharded_frame_check(scene, ubo, smode, rank) if full else None
         per_rank = {"frame_ms": mm(0, 1e3 / args.steps), "render_kernel_ms": mm(1, 1.0),
                     "exchange_ms": mm(2, 1.0),
                     "exchange_ms_rank0": round(float(allr[0, 2]), 4) if allr[0, 2] >= 0 else None,
@@ -585,7 +650,7 @@ def main():
                    "exchange_format": (("dump8: 4 B/pixel, the integers the PPM dump prints (exact; escapes for the "
                                         "rest)" if args.out == "dump8" else "rgba32f: 16 B/pixel")
                                        if world > 1 or rank_of > 1 else None),
-                   "bvh_build_ms": round(bvh_ms, 2), "bvh_build_first_ms": round(bvh_cold_ms, 2)},
+                   "bvh_build_ms": round(bvh_ms, 2) if bvh_ms is not None else None, "bvh_build_first_ms": round(bvh_cold_ms, 2)},
         "warmup_frames_run": warm, "warmup_s": round(warm_s, 3),
     }
     if per_rank is not None:
@@ -651,7 +716,7 @@ def main():
                 roof["lds_array_frac"] = round(prof["lds_array_ms"] / k_ms, 4)
             roof["pmc_profile"] = os.path.relpath(args.traffic, ROOT) + " (" + str(prof.get("tag")) + ")"
         out["roofline"] = roof
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:
         rgba, _ = scene.render(ubo, mode)
         p, a = scene.download()
         out["cpu_baseline"] = cpu_baseline(p, a, sh, ubo, W, H, args.cpu_seconds, gpu_rgba=rgba)

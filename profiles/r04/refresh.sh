@@ -14,9 +14,9 @@ mkdir -p $O
 if [[ $PART == *a* ]]; then
 COR_F64_REPORT=$O/cor_f64_report.jsonl timeout -k 10 500 python3 -u -m pytest tests -m gpu -x -q --timeout 150 --timeout-method thread > $O/gpu_tests.log 2>&1
 tail -1 $O/gpu_tests.log
-timeout -k 10 400 python3 bench.py > $O/bench_c3.json 2> $O/bench_c3.err
-timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c3_driver.json 2> $O/bench_c3_driver.err
-for c in c2 c4 c5 c1; do timeout -k 10 200 python3 bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
+timeout -k 10 400 python3 bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err
+timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c3_driver.json 2> $O/bench_c3_driver.err
+for c in c2 c4 c5 c1; do timeout -k 10 200 python3 bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
 echo benches done
 bash profiles/r04/shares.sh $TAG c3 8 0 1 2 3 4 5 6 7 > $O/shares_c3r8.txt
 bash profiles/r04/shares.sh $TAG c4 8 0 1 2 3 4 5 6 7 > $O/shares_c4r8.txt

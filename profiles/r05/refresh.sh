@@ -15,9 +15,9 @@ COR_F64_REPORT=$O/cor_f64_report.jsonl timeout -k 10 600 python3 -u -m pytest te
 tail -1 $O/gpu_tests.log
 fi
 if [[ $PART == *a* ]]; then
-timeout -k 10 400 python3 bench.py > $O/bench_c3.json 2> $O/bench_c3.err
-timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c3_driver.json 2> $O/bench_c3_driver.err
-for c in c2 c4 c5 c1; do timeout -k 10 200 python3 bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
+timeout -k 10 400 python3 bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err
+timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c3_driver.json 2> $O/bench_c3_driver.err
+for c in c2 c4 c5 c1; do timeout -k 10 200 python3 bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err; done
 echo benches done
 fi
 if [[ $PART == *b* ]]; then
@@ -29,7 +29,7 @@ echo shares done
 fi
 if [[ $PART == *c* ]]; then
 for c in c3 c2 c4 c5 c1; do
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kst_$c -o run -- python3 bench.py --config $c \
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kst_$c -o run -- python3 bench.py --full --config $c \
     --no-cpu-baseline --steps 50 --warmup 10 > $O/kst_$c.json 2> $O/kst_$c.err
 done
 timeout -k 10 200 python3 profiles/bvh_timing.py > $O/bvh.txt 2>&1

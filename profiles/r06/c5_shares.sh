@@ -8,7 +8,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 for r in "$@"; do
-  GSRT_DEBUG_RANK_OF=$N:$r timeout -k 10 150 python3 bench.py --config c5 --no-cpu-baseline --no-stats --steps 100 --warmup 20 \
+  GSRT_DEBUG_RANK_OF=$N:$r timeout -k 10 150 python3 bench.py --full --config c5 --no-cpu-baseline --no-stats --steps 100 --warmup 20 \
     > $O/share_c5_${N}_$r.json 2> $O/share_c5_${N}_$r.err
   python3 -c "import json; d=json.load(open('$O/share_c5_${N}_$r.json')); print('c5 N=$N rank $r:', d['ms_per_step'], 'ms, kernel', d.get('roofline',{}).get('kernel_ms'), 'exchange', d.get('rank_share_exchange_ms'), 'ms, bands', d.get('rank_share_bands'))"
 done

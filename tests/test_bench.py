@@ -65,6 +65,30 @@ def test_zero_gpus_refused():
     assert r.returncode == 2
 
 
+def test_plain_run_is_lean_by_default(monkeypatch):
+    """--full and --dump-outputs are off unless asked for, and --steps is the number of timed steps (at least 1)."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    assert run(["--gpus", "1", "--steps", "0"]).returncode == 2
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """An output larger than the budget is written as a sample of its rows: the same rows for every run, in order,
+    within the budget; one that fits is written whole."""
+    import numpy as np
+
+    a = np.arange(1000 * 4, dtype=np.float32).reshape(1000, 4)
+    assert bench._dump_sample(a, a.nbytes) is a
+    s1, s2 = bench._dump_sample(a, 16 * 100 + 5), bench._dump_sample(a.copy(), 16 * 100 + 5)
+    assert s1.shape == (100, 4) and s1.nbytes <= 16 * 100 + 5 and np.array_equal(s1, s2)
+    assert (np.diff(s1[:, 0]) > 0).all() and (s1[:, 1] == s1[:, 0] + 1).all()  # whole rows of `a`, ascending
+    assert bench.DUMP_BYTES == 64 << 20
+
+
 def test_warm_up_single_rank_counts():
     calls = {"frames": 0, "syncs": 0}
     t = [0.0]

@@ -941,6 +941,41 @@ def test_bench_sharded_frame_check(monkeypatch):
         sc.close()
 
 
+def test_bench_dump_outputs(monkeypatch, tmp_path):
+    """bench.py --dump-outputs writes what the last timed step left its caller: after pipelined frames rgba.npy is the
+    framebuffer of the last one (bit for bit its synchronous render), after dump8 sharded frames codes.npy and
+    escapes.npy are the frame's dump codes and escapes; float32 / float64 arrays."""
+    import bench
+
+    monkeypatch.setenv("GSRT_DEBUG_COMM_LOOPBACK", "1")
+    c, r, s, o, sh = gsrt.synth_cloud(gsrt.SYNTH_COR, 20000, 21, True)
+    W, H = 200, 72  # no multiple of the tile
+    ubos = [gsrt.camera_from_modelview(gsrt.lookat((0.05 * i, 0, 0), (0, 0, -1)), 60.0, W, H, 1.0, 4, 16)
+            for i in range(3)]
+    with gsrt.Context(0) as cx:
+        cx.comm_init(gsrt.comm_unique_id(), 1, 0)
+        sc = gsrt.Scene.from_model(cx, c, r, s, o, sh)
+        sc.build_bvh()
+        want, _ = sc.render(ubos[-1], gsrt.MODE_COR)
+        for u in ubos:
+            sc.render_async(u, gsrt.MODE_COR)
+        cx.synchronize()
+        bench.dump_outputs(str(tmp_path / "a"), cx, W, H)
+        got = np.load(tmp_path / "a" / "rgba.npy")
+        assert got.dtype == np.float32 and got.shape == (H, W, 4) and got.tobytes() == want.tobytes()
+        for u in ubos:
+            sc.render_sharded_async(u, gsrt.MODE_COR | gsrt.FLAG_OUT_DUMP8)
+        cx.synchronize()
+        bench.dump_outputs(str(tmp_path / "b"), cx, W, H)
+        codes, esc = np.load(tmp_path / "b" / "codes.npy"), np.load(tmp_path / "b" / "escapes.npy")
+        wc, we = gsrt.dump8_encode(want)
+        assert codes.dtype == esc.dtype == np.float64 and codes.shape == (H, W) and esc.shape == (len(we), 4)
+        assert np.array_equal(codes, wc.astype(np.float64))
+        for i, k in enumerate(("pixel", "r", "g", "b")):
+            assert np.array_equal(esc[:, i], we[k].astype(np.float64), equal_nan=True)
+        sc.close()
+
+
 def test_timing_kernel_only():
     """gsrt_timing records the render kernel and the whole frame per timed frame; with gsrt_timing_kernel_only only
     the kernel's two events (frame times read 0). The events carry no system-scope fence (kTimingEventFlags)."""
