@@ -777,7 +777,8 @@ struct CorRay {
 
 // Front-to-back blend of candidate c (alpha 0: no contribution) into every lane's ray; the SH-3 colour only
 // when some lane blends. A ray whose transmittance would drop below 1e-4 stops (the hit is not blended):
-// returns true on the lane whose ray stopped here.
+// returns the mask of the lanes whose ray stopped here. contrib is the wave's lane mask of alpha > 0: the masks are
+// ballots combined by scalar instructions (SGPR pairs), read back per lane by lane_of.
 // channel colour 0.5 + sum basis * coef (the 0.5 and s_0 Y_0 folded into coefficient 0, gsrt_api.cpp upload_common),
 // clamped at 0: the same fma chain whatever the coefficients' home
 __device__ GSRT_INLINE float sh_channel(const float (&bs)[16], const float (&s)[16]) {
@@ -800,16 +801,19 @@ struct ShFromStage {  // the stage's LDS copy of candidate c's row
         }
     }
 };
+// This lane's bit of a wave-uniform lane mask (a ballot held in an SGPR pair): the mask itself is the v_cndmask
+// or exec source, no compare forms it again.
+__device__ GSRT_INLINE bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 template <bool SH, bool STATS, class ShSrc>
-__device__ GSRT_INLINE bool blend_hit(const ShSrc& shsrc, float alpha, bool contrib, CorRay& ray) {
+__device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint64_t contrib, CorRay& ray) {
     const float tn = ray.T * (1.0f - alpha);
-    const bool low = tn < 1e-4f;  // one compare serves both masks
-    const bool term = contrib && low;
-    const bool blend = contrib && !low;
-    if (__ballot(blend)) {
+    const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
+    const uint64_t term = contrib & low;
+    const uint64_t blend = contrib & ~low;  // the wave-uniform branch and the mask of the accumulate
+    if (blend) {
         float col[3] = {1.0f, 1.0f, 1.0f};
         if (SH) shsrc(ray.bs, col);
-        if (blend) {
+        if (lane_of(blend)) {
             const float w = alpha * ray.T;
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
             ray.C[1] = fmaf(col[1], w, ray.C[1]);
@@ -818,16 +822,19 @@ __device__ GSRT_INLINE bool blend_hit(const ShSrc& shsrc, float alpha, bool cont
             if (STATS) ++ray.blended;
         }
     }
-    if (term) {
-        ray.active = false;
-        ray.pxs = __builtin_nanf("");  // every later g is NaN: the g-first test fails without an active flag
-        if (STATS) ++ray.term;
+    if (term) {  // wave-uniform: a ray stops once
+        if (lane_of(term)) {
+            ray.active = false;
+            ray.pxs = __builtin_nanf("");  // every later g is NaN: the g-first test fails without an active flag
+            if (STATS) ++ray.term;
+        }
     }
     return term;
 }
 
-// Shade candidates 0..m of one stage (sorted front to back) for every lane's ray.
-template <bool SH, bool LUT, bool STATS>
+// Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
+// compile time (the steady state of shade_sorted), so no candidate is tested against m.
+template <bool SH, bool LUT, bool STATS, bool FULL = false>
 __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay& ray) {
     if (!STATS) {
         // Phase 1, g of all kGroup candidates at once (independent chains, one LDS wait): g first because lanes
@@ -836,8 +843,9 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
         // unchanged. g in [0, gcut] is one unsigned compare of the bit patterns: gcut >= +0 (k_project); g is
         // never -0 (its first term (A/2 dx) dx is +0 or positive and an exact cancellation rounds to +0); a
         // negative g has the sign bit set; a terminated or invalid ray has pxs = NaN, so g is NaN and fails.
+        // okg[c] is the wave's lane mask of candidate c (a ballot: an SGPR pair, no VGPR flag per lane).
         float gv[kGroup];
-        bool okg[kGroup];
+        uint64_t okg[kGroup];
 #pragma unroll
         for (uint32_t c = 0; c < kGroup; ++c) {
             const float4 q2 = reinterpret_cast<const float4*>(&stg->rec[c])[2];  // ppx, ppy, A/2, B
@@ -846,7 +854,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             const float c2 = q3.x, cut = LUT ? kGMax : q3.y;
             const float dx = ray.pxs - q2.x, dy = ray.pys - q2.y;
             gv[c] = fmaf(c2 * dy, dy, fmaf(q2.w * dx, dy, (q2.z * dx) * dx));
-            okg[c] = c < m && __float_as_uint(gv[c]) <= __float_as_uint(cut);  // stale records past m: never
+            okg[c] = (FULL || c < m) ? __ballot(__float_as_uint(gv[c]) <= __float_as_uint(cut)) : 0;  // stale records past m: never
         }
 #ifdef GSRT_DIAG
         ray.dg_staged += __ballot(ray.active) ? m : 0u;
@@ -854,7 +862,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
         // Phase 2, front to back over the candidates some lane passed: slab test, exp, alpha, blend
 #pragma unroll
         for (uint32_t c = 0; c < kGroup; ++c) {
-            if (!__ballot(okg[c])) continue;
+            if (!okg[c]) continue;
             float4 q0 = reinterpret_cast<const float4*>(&stg->rec[c])[0];  // lo or near, depth
             const float4 q1 = reinterpret_cast<const float4*>(&stg->rec[c])[1];  // hi or far, +-opacity
             // q0.w (depth) is unused, but reading all 16 B keeps one ds_read_b128 (4 LDS-array cycles) instead of a
@@ -864,25 +872,28 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             // record's layout (k_project) is wave-uniform: (near, far) when the opacity word is positive
             const float lo[3] = {q0.x, q0.y, q0.z}, hi[3] = {q1.x, q1.y, q1.z};
             const bool ordered = (int)__builtin_amdgcn_readfirstlane(__float_as_uint(q1.w)) >= 0;
-            const bool ok = okg[c] & (ordered ? slab_hit_ordered(ray.R, lo, hi) : slab_hit_rel(ray.R, lo, hi));
+            const uint64_t ok = okg[c] & (ordered ? __ballot(slab_hit_ordered(ray.R, lo, hi))
+                                                  : __ballot(slab_hit_rel(ray.R, lo, hi)));
             // the LUT index must stay in range on every lane (g in [0, kGMax]); exp_neg_nocheck takes any g (a
             // failed lane's value, even NaN, is discarded below)
-            const float gs = LUT ? (ok ? gv[c] : 0.0f) : gv[c];
+            const float gs = LUT ? (lane_of(ok) ? gv[c] : 0.0f) : gv[c];
             const float e = LUT ? linear_exp(lut_s, gs) : exp_neg_nocheck(-gs);
             // min(a, 0.99) as v_min: a is never NaN where it is kept (ok: g in [0, gcut], e in (0, 1])
             const float a = __builtin_fminf(fabsf(q1.w) * e, 0.99f);
-            const bool contrib = ok && a > kAlphaMin;
-            const float alpha = contrib ? a : 0.0f;
+            const uint64_t contrib = ok & __ballot(a > kAlphaMin);
+            const float alpha = lane_of(contrib) ? a : 0.0f;
 #ifdef GSRT_DIAG
             ray.dg_gpass += 1u;
-            ray.dg_lanes_g += (uint32_t)__popcll(__ballot(okg[c]));
+            ray.dg_lanes_g += (uint32_t)__popcll(okg[c]);
             ray.dg_contrib += __ballot(alpha > 0.0f) ? 1u : 0u;
             ray.dg_blend += __ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f) ? 1u : 0u;
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
-            if (blend_hit<SH, STATS>(ShFromStage{stg, c}, alpha, contrib, ray)) {
+            // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
+            const uint64_t stopped = blend_hit<SH, STATS>(ShFromStage{stg, c}, alpha, contrib, ray);
+            if (stopped) {
 #pragma unroll
-                for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] = false;  // this lane's ray stopped
+                for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
             }
         }
         return;
@@ -908,7 +919,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
                 }
             }
         }
-        blend_hit<SH, STATS>(ShFromStage{stg, c}, alpha, alpha > 0.0f, ray);
+        blend_hit<SH, STATS>(ShFromStage{stg, c}, alpha, __ballot(alpha > 0.0f), ray);
     }
 }
 
@@ -928,6 +939,8 @@ __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, St
         const uint32_t m = count - g < kGroup ? count - g : kGroup;
         shade_stage<SH, LUT, STATS>(stg, m, lut_s, ray);
     };
+    auto shade_full = [&](Stage* stg) { shade_stage<SH, LUT, STATS, true>(stg, kGroup, lut_s, ray); };
+    constexpr uint32_t kWaitTwo = 2 * kStagePieceOps<SH>;  // the two younger stages' DMAs stay in flight
     // stages issued after stage g's DMA when it is read: those of g + kGroup and g + 2 kGroup that exist
     auto wait = [count](uint32_t g) {
         wait_stage<SH>((g + kGroup < count ? 1u : 0u) + (g + 2 * kGroup < count ? 1u : 0u));
@@ -935,7 +948,28 @@ __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, St
     issue(0, stA);
     if (kGroup < count) issue(kGroup, stB);
     bool live = true;
-    for (uint32_t g0 = 0; g0 < count; g0 += 3 * kGroup) {
+    uint32_t g0 = 0;
+    // Steady state: the stage triples whose three "two stages ahead" issues all exist (g0 + 4 kGroup < count). Every
+    // stage shaded here is full and has two younger stages in flight: unconditional issues, a constant wait, no
+    // test against the list's end. It leaves the state the general loop below starts from (stage g0 in stA and, issued
+    // after it, stage g0 + kGroup in stB), which shades the rest: at most four stages.
+    if (!STATS) {
+        for (; g0 + 4 * kGroup < count; g0 += 3 * kGroup) {
+            issue(g0 + 2 * kGroup, stC);
+            wait_vmcnt<kWaitTwo>();
+            shade_full(stA);
+            if (!__ballot(ray.active)) { live = false; break; }
+            issue(g0 + 3 * kGroup, stA);
+            wait_vmcnt<kWaitTwo>();
+            shade_full(stB);
+            if (!__ballot(ray.active)) { live = false; break; }
+            issue(g0 + 4 * kGroup, stB);
+            wait_vmcnt<kWaitTwo>();
+            shade_full(stC);
+            if (!__ballot(ray.active)) { live = false; break; }
+        }
+    }
+    for (; live && g0 < count; g0 += 3 * kGroup) {
         if (g0 + 2 * kGroup < count) issue(g0 + 2 * kGroup, stC);
         wait(g0);
         shade(stA, g0);
