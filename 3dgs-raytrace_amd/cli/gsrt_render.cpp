@@ -12,7 +12,8 @@
 // Extra flags: --mode ref|cor, --lut, --gaussians N, --seed S, --sh, --camera FILE (.camera: eye, centre),
 // --fov DEG, --out PATH (PPM), --binary PATH (image.binary records), --text PATH (dump_image.sh lines),
 // --ply PATH (3DGS scene: COR mode, camera from --camera or looking down -z from the origin), --no-dump,
-// --device D, --frames F (with --benchmark: frames timed), --stats.
+// --device D, --frames F (with --benchmark: frames timed), --stats, --depth FILE (COR: the frame's expected depth,
+// GSRT_FLAG_DEPTH, as a one-channel PFM; a usage error with --mode ref or --stats).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -34,7 +35,7 @@ struct Options {
     uint32_t gaussians = 10000, seed = 42, frames = 10;
     int device = 0;
     float fov = 0.0f;  // 0: scene default
-    std::string camera, out, binary, text, ply;
+    std::string camera, out, binary, text, ply, depth;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -43,7 +44,8 @@ struct Options {
                  "usage: gsrt_render [--scene 33|100|101] [--shader-type N] [--width W] [--height H] [--samples S]\n"
                  "                   [--bounces B] [--benchmark] [--mode ref|cor] [--lut] [--gaussians N] [--seed S]\n"
                  "                   [--sh] [--camera FILE] [--fov DEG] [--out PPM] [--binary FILE] [--no-dump]\n"
-                 "                   [--text FILE] [--ply FILE] [--device D] [--frames F] [--stats]\n");
+                 "                   [--text FILE] [--ply FILE] [--device D] [--frames F] [--stats]\n"
+                 "                   [--depth PFM]\n");
     std::exit(2);
 }
 
@@ -84,6 +86,7 @@ Options parse(int argc, char** argv) {
         else if (a == "--binary") o.binary = val();
         else if (a == "--text") o.text = val();
         else if (a == "--ply") o.ply = val();
+        else if (a == "--depth") o.depth = val();
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -91,6 +94,8 @@ Options parse(int argc, char** argv) {
     if (o.mode.empty()) o.mode = (o.scene == 100 || !o.ply.empty()) ? "cor" : "ref";
     if (o.mode != "ref" && o.mode != "cor") usage("--mode must be ref or cor");
     if (!o.width || !o.height) usage("empty frame");
+    if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
+    if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
     return o;
 }
 
@@ -164,7 +169,15 @@ int main(int argc, char** argv) {
     if (o.lut) mode |= GSRT_FLAG_LUT;
     if (o.stats) mode |= GSRT_FLAG_STATS;
     std::vector<float> rgba((size_t)o.width * o.height * 4);
-    if (!rc) rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
+    std::vector<float> depth(o.depth.empty() ? 0 : (size_t)o.width * o.height);
+    if (!rc && !o.depth.empty()) {
+        mode |= GSRT_FLAG_DEPTH;
+        rc = check(gsrt_render_depth(scene, &ubo, mode, 0, rgba.data(), depth.data()), ctx, "render");
+        if (!rc) rc = check(gsrt_dump_pfm(o.depth.c_str(), depth.data(), o.width, o.height, 1), ctx, "dump_pfm");
+        if (!rc) std::printf("wrote %s\n", o.depth.c_str());
+    } else if (!rc) {
+        rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
+    }
     if (!rc && o.stats) {
         uint64_t st[8];
         rc = check(gsrt_last_stats(ctx, st, nullptr), ctx, "stats");

@@ -232,6 +232,7 @@ void gsrt_destroy(gsrt_ctx* ctx) {
         if (ctx->ev_share[p]) (void)hipEventDestroy(ctx->ev_share[p]);
     }
     (void)hipFree(ctx->d_ray_stats);
+    (void)hipFree(ctx->d_depth);
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_tile_counter);
     (void)hipFree(ctx->d_lut);
@@ -694,7 +695,12 @@ static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
     if (!sc || !ubo) return GSRT_E_ARG;
     if (ubo->width == 0 || ubo->height == 0 || ubo->width > 32768 || ubo->height > 32768)
         return fail(sc->ctx, GSRT_E_ARG, "bad frame size");
-    if ((mode & 0xffu) > GSRT_MODE_COR || (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS)))
+    if (mode & GSRT_FLAG_DEPTH) {  // a whole COR frame's second output; the counting pass and dump codes carry none
+        if ((mode & 0xffu) != GSRT_MODE_COR) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: COR frames only");
+        if (mode & GSRT_FLAG_STATS) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: not with GSRT_FLAG_STATS");
+        if (mode & GSRT_FLAG_OUT_DUMP8) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: not with GSRT_FLAG_OUT_DUMP8");
+    }
+    if ((mode & 0xffu) > GSRT_MODE_COR || (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH)))
         return fail(sc->ctx, GSRT_E_ARG, "bad mode");
     if ((mode & 0xffu) == GSRT_MODE_COR && ubo->samples == 0) return fail(sc->ctx, GSRT_E_ARG, "samples == 0");
     if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
@@ -712,6 +718,11 @@ static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mo
         s = grow(ctx, &ctx->d_ray_stats, &ctx->ray_stats_pixels, px * 4);
         if (s != GSRT_OK) return s;
     }
+    if (mode & GSRT_FLAG_DEPTH) {
+        s = grow(ctx, &ctx->d_depth, &ctx->depth_pixels, px);
+        if (s != GSRT_OK) return s;
+    }
+    ctx->last_depth = (mode & GSRT_FLAG_DEPTH) != 0;
     ctx->last_w = ubo->width;
     ctx->last_h = ubo->height;
     ctx->last_stats = (mode & GSRT_FLAG_STATS) != 0;
@@ -719,8 +730,9 @@ static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mo
     return GSRT_OK;
 }
 
-gsrt_status gsrt_render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
-                              gsrt_raystate* d_rs) {
+// one frame on the render stream; d_depth (a GSRT_FLAG_DEPTH frame's copy of ctx->d_depth) may be nullptr
+static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
+                                gsrt_raystate* d_rs, float* d_depth) {
     gsrt_status s = check_render_args(sc, ubo, mode);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
@@ -731,8 +743,9 @@ gsrt_status gsrt_render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode
     const gsrt::RenderPlan plan = gsrt::make_plan(*ubo, mode, k, 0, 1);
     gsrt::timing_mark(ctx, 0);
     // pipelined COR frames render into their own buffer while slot streams are chosen (their frames overlap); the
-    // ray states are one buffer, so frames that write them stay in order
-    const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs &&
+    // ray states are one buffer, so frames that write them stay in order; so is the depth image (GSRT_FLAG_DEPTH)
+    const bool depth = (mode & GSRT_FLAG_DEPTH) != 0;
+    const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth &&
                       gsrt::use_slot_streams(ctx, false);
     if (slot) {
         // the frame goes into one of two alternating buffers (the previous frame's render kernel may still write the
@@ -769,16 +782,57 @@ gsrt_status gsrt_render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode
     } else {
         if ((s = gsrt_comm_fb_render_write(ctx)) != GSRT_OK) return s;  // d_fb is also rank 0's unpack target
         gsrt::RenderSync rsy;  // a shared output: frames in order (and render times sampled for use_slot_streams)
-        s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs ? nullptr : &rsy);
+        if (depth) rsy.depth = ctx->d_depth;
+        s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
         ctx->fb_view = nullptr;
         if (d_rgba && d_rgba != ctx->d_fb)
             GSRT_HIP(ctx, hipMemcpyAsync(d_rgba, ctx->d_fb, sizeof(float) * 4 * ubo->width * ubo->height,
                                          hipMemcpyDeviceToDevice, ctx->stream));
+        if (depth && d_depth && d_depth != ctx->d_depth)
+            GSRT_HIP(ctx, hipMemcpyAsync(d_depth, ctx->d_depth, sizeof(float) * ubo->width * ubo->height,
+                                         hipMemcpyDeviceToDevice, ctx->stream));
     }
     gsrt::timing_mark(ctx, 3);
     return GSRT_OK;
 }
+
+gsrt_status gsrt_render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
+                              gsrt_raystate* d_rs) {
+    return render_async(sc, ubo, mode, k, d_rgba, d_rs, nullptr);
+}
+
+gsrt_status gsrt_render_depth_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
+                                    float* d_depth) {
+    return render_async(sc, ubo, mode | GSRT_FLAG_DEPTH, k, d_rgba, nullptr, d_depth);
+}
+
+gsrt_status gsrt_render_depth(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
+                              float* depth_out) {
+    mode |= GSRT_FLAG_DEPTH;
+    gsrt_status s = check_render_args(sc, ubo, mode);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const size_t px = (size_t)ubo->width * ubo->height;
+    const bool rgba_dev = is_device_ptr(rgba_out), depth_dev = is_device_ptr(depth_out);
+    s = render_async(sc, ubo, mode, k, rgba_dev ? rgba_out : nullptr, nullptr, depth_dev ? depth_out : nullptr);
+    if (s == GSRT_OK && rgba_out && !rgba_dev) {
+        if (hipMemcpyAsync(rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px, hipMemcpyDeviceToHost,
+                           ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "framebuffer download failed");
+    }
+    if (s == GSRT_OK && depth_out && !depth_dev) {
+        if (hipMemcpyAsync(depth_out, ctx->d_depth, sizeof(float) * px, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "depth download failed");
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
+        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
+    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
+    return s;
+}
+
+const float* gsrt_depth_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_depth ? ctx->d_depth : nullptr; }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
                         gsrt_raystate* rs_out) {

@@ -261,6 +261,18 @@ extern "C" gsrt_status gsrt_dump_image_binary(const char* path, const float* rgb
     return w == rec.size() ? GSRT_OK : GSRT_E_IO;
 }
 
+// PFM: "Pf" (1 channel) or "PF" (3) header, "W H", scale -1.0 (negative: little-endian floats), then the rows bottom to top
+extern "C" gsrt_status gsrt_dump_pfm(const char* path, const float* data, uint32_t width, uint32_t height,
+                                     uint32_t channels) {
+    if (!path || !data || width == 0 || height == 0 || (channels != 1 && channels != 3)) return GSRT_E_ARG;
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return GSRT_E_IO;
+    bool ok = std::fprintf(f, "%s\n%u %u\n-1.0\n", channels == 1 ? "Pf" : "PF", width, height) > 0;
+    const size_t row = (size_t)width * channels;
+    for (uint32_t y = height; ok && y-- > 0;) ok = std::fwrite(data + y * row, sizeof(float), row, f) == row;
+    return std::fclose(f) == 0 && ok ? GSRT_OK : GSRT_E_IO;
+}
+
 extern "C" gsrt_status gsrt_synth_cloud(uint32_t kind, uint32_t n, uint32_t seed, int with_sh, float* center,
                                         float* rot, float* scale, float* opacity, float* sh) {
     if (n == 0 || !center || !rot || !scale || !opacity || (with_sh && !sh) || kind > GSRT_SYNTH_NEEDLE)

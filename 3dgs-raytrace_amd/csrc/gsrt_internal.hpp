@@ -150,6 +150,9 @@ struct gsrt_ctx {
     size_t fb_pixels = 0;
     uint32_t* d_ray_stats = nullptr;
     size_t ray_stats_pixels = 0;
+    float* d_depth = nullptr;                  // GSRT_FLAG_DEPTH frames: W x H floats (one buffer: such frames stay in order)
+    size_t depth_pixels = 0;
+    bool last_depth = false;                   // the last frame wrote d_depth (gsrt_depth_buffer)
     unsigned long long* d_counters = nullptr;  // kCounters words: [0..7] stats, [kErrWord] sticky error word
     uint32_t* d_tile_counter = nullptr;
     uint32_t last_w = 0, last_h = 0;
@@ -327,6 +330,8 @@ struct RenderSync {
     uint4* esc = nullptr;
     uint32_t esc_cap = 0;
     float4* accum = nullptr;
+    // GSRT_FLAG_DEPTH (a whole COR frame on the in-order path): the frame's depth image, W x H floats, or nullptr
+    float* depth = nullptr;
 };
 gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_rgba,
                           gsrt_raystate* d_rs, RenderSync* sync = nullptr);

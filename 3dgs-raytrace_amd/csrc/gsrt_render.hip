@@ -105,6 +105,8 @@ struct RenderArgs {
     const uint32_t* depth_unsafe;    // COR: the scene's word k_project sets when a keyed centre lies outside its AABB's
                                      // depth bound (depth_lo): the traversals' depth cull is off while it is non-zero
     uint32_t depth_cull;             // the traversals' depth cull is on (where group lists overflow, launch_render)
+    float* depth_out;                // COR with GSRT_FLAG_DEPTH: width x height floats, row-major (k_render_cor DEPTH);
+                                     // the last member, so that no other member's kernarg offset moved
 };
 
 #ifdef GSRT_WAVE_TIMES
@@ -766,6 +768,7 @@ struct CorRay {
     float pxs, pys;
     float bs[16];
     float T, C[3];
+    float D;  // DEPTH instantiations only: sum of z w over the blended hits (expected view depth, premultiplied)
     bool active;
     uint32_t cand, blended, term;
 #ifdef GSRT_DIAG
@@ -804,8 +807,9 @@ struct ShFromStage {  // the stage's LDS copy of candidate c's row
 // This lane's bit of a wave-uniform lane mask (a ballot held in an SGPR pair): the mask itself is the v_cndmask
 // or exec source, no compare forms it again.
 __device__ GSRT_INLINE bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
-template <bool SH, bool STATS, class ShSrc>
-__device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint64_t contrib, CorRay& ray) {
+// DEPTH: z is the candidate's view depth (SplatRec::depth); the blend's own w also weighs it into ray.D
+template <bool SH, bool STATS, bool DEPTH = false, class ShSrc>
+__device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint64_t contrib, CorRay& ray, float z = 0.0f) {
     const float tn = ray.T * (1.0f - alpha);
     const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
     const uint64_t term = contrib & low;
@@ -818,6 +822,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint6
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
             ray.C[1] = fmaf(col[1], w, ray.C[1]);
             ray.C[2] = fmaf(col[2], w, ray.C[2]);
+            if constexpr (DEPTH) ray.D = fmaf(z, w, ray.D);
             ray.T = tn;
             if (STATS) ++ray.blended;
         }
@@ -834,7 +839,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint6
 
 // Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
 // compile time (the steady state of shade_sorted), so no candidate is tested against m.
-template <bool SH, bool LUT, bool STATS, bool FULL = false>
+template <bool SH, bool LUT, bool STATS, bool FULL = false, bool DEPTH = false>
 __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay& ray) {
     if (!STATS) {
         // Phase 1, g of all kGroup candidates at once (independent chains, one LDS wait): g first because lanes
@@ -865,8 +870,8 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             if (!okg[c]) continue;
             float4 q0 = reinterpret_cast<const float4*>(&stg->rec[c])[0];  // lo or near, depth
             const float4 q1 = reinterpret_cast<const float4*>(&stg->rec[c])[1];  // hi or far, +-opacity
-            // q0.w (depth) is unused, but reading all 16 B keeps one ds_read_b128 (4 LDS-array cycles) instead of a
-            // ds_read_b96 (8)
+            // q0.w (depth) is unused without DEPTH, but reading all 16 B keeps one ds_read_b128 (4 LDS-array cycles)
+            // instead of a ds_read_b96 (8)
             asm volatile("" : "+v"(q0.w));
             // the slab test and exp run for the whole wave; a lane keeps alpha only if it passed both tests. The
             // record's layout (k_project) is wave-uniform: (near, far) when the opacity word is positive
@@ -890,7 +895,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
-            const uint64_t stopped = blend_hit<SH, STATS>(ShFromStage{stg, c}, alpha, contrib, ray);
+            const uint64_t stopped = blend_hit<SH, STATS, DEPTH>(ShFromStage{stg, c}, alpha, contrib, ray, q0.w);
             if (stopped) {
 #pragma unroll
                 for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
@@ -928,7 +933,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
 // Three stage buffers: while stage k is shaded, the DMAs of stages k+1 and k+2 are in flight; wait_stage waits
 // for stage k's own DMA only. No DMA stays in flight past a return (the LDS is reused by the next round or by
 // the next workgroup).
-template <bool SH, bool LUT, bool STATS>
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false>
 __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, Stage* stA, Stage* stB, Stage* stC,
                              const float* lut_s, CorRay& ray, const SplatRec* recs, const float* sh) {
     const uint32_t lane = lane_id();
@@ -937,9 +942,9 @@ __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, St
     auto issue = [&](uint32_t g, Stage* dst) { stage_issue<SH>(ids, count, g, lane, dst, recs, sh); };
     auto shade = [&](Stage* stg, uint32_t g) {
         const uint32_t m = count - g < kGroup ? count - g : kGroup;
-        shade_stage<SH, LUT, STATS>(stg, m, lut_s, ray);
+        shade_stage<SH, LUT, STATS, false, DEPTH>(stg, m, lut_s, ray);
     };
-    auto shade_full = [&](Stage* stg) { shade_stage<SH, LUT, STATS, true>(stg, kGroup, lut_s, ray); };
+    auto shade_full = [&](Stage* stg) { shade_stage<SH, LUT, STATS, true, DEPTH>(stg, kGroup, lut_s, ray); };
     constexpr uint32_t kWaitTwo = 2 * kStagePieceOps<SH>;  // the two younger stages' DMAs stay in flight
     // stages issued after stage g's DMA when it is read: those of g + kGroup and g + 2 kGroup that exist
     auto wait = [count](uint32_t g) {
@@ -1432,12 +1437,16 @@ __global__ __launch_bounds__(64) void k_collect_cor(const KArgs karg) {
         K.a.list_hdr[lt] = make_uint4(cl.count | (cl.more ? 0x80000000u : 0u), cl.total, (uint32_t)last, (uint32_t)(last >> 32));
 }
 
-template <bool SH, bool LUT, bool STATS>
+// DEPTH (GSRT_FLAG_DEPTH, never with STATS): the frame also writes its expected view depth, sum of z w over each ray's
+// blended hits (z = SplatRec::depth, w = the blend's alpha T), combined over the samples as the colour is, to
+// RenderArgs::depth_out. Everything it adds sits under if constexpr: the other instantiations' code does not change.
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false>
 // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
 // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
 // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6))))
 void k_render_cor(const KArgs karg) {
+    static_assert(!(DEPTH && STATS), "the counting pass has no depth output");
     // traversal buffers (keys, stack) and shading buffers (ids, two stages) are never live at once
     union CorLds {
         struct { uint64_t keys[kRBuf]; uint32_t stack[kRStack]; } t;
@@ -1517,6 +1526,7 @@ void k_render_cor(const KArgs karg) {
     // (spp > 64: one pixel per lane) the framebuffer entry holds the running sum between passes, so that no
     // accumulator lives (spilled) across the shading loop. The sums are formed in the same order either way.
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    [[maybe_unused]] float acc_d = 0.0f;  // DEPTH: the depth's sum, carried beside acc
     uint32_t st_cand = 0, st_blend = 0, st_term = 0, st_rounds = 0, restarts = 0, maxc = 0;
 #ifdef GSRT_DIAG  // diagnostic build only: per-wave cycle split between traversal+sort and shading
     unsigned long long diag_collect = 0, diag_shade = 0;
@@ -1542,6 +1552,7 @@ void k_render_cor(const KArgs karg) {
         }
         ray.T = 1.0f;
         ray.C[0] = ray.C[1] = ray.C[2] = 0.0f;
+        if constexpr (DEPTH) ray.D = 0.0f;
         ray.active = valid;
         if (!valid) ray.pxs = __builtin_nanf("");  // see blend_hit
         ray.cand = ray.blended = ray.term = 0;
@@ -1638,7 +1649,7 @@ void k_render_cor(const KArgs karg) {
 #endif
             ++st_rounds;
             if (cl.total > maxc) maxc = cl.total;
-            const bool live = shade_sorted<SH, LUT, STATS>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
+            const bool live = shade_sorted<SH, LUT, STATS, DEPTH>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
 #ifdef GSRT_DIAG
             diag_last = __builtin_amdgcn_s_memtime();
             diag_shade += diag_last - d1;
@@ -1661,6 +1672,17 @@ void k_render_cor(const KArgs karg) {
                 if (pass + 1 < passes) *o = make_float4(acc[0], acc[1], acc[2], acc[3]);
             }
         }
+        if constexpr (DEPTH) {
+            acc_d = ray.D;
+            if (passes > 1) {  // as the colour above: the depth image's own entry holds the running sum between passes
+                pixel(pix_in_tile, s_in, px, py, valid);
+                if (valid) {
+                    float* od = kargs().a.depth_out + ((size_t)py * kargs().a.width + px);
+                    if (pass > 0) acc_d = *od + acc_d;
+                    if (pass + 1 < passes) *od = acc_d;
+                }
+            }
+        }
         st_cand += ray.cand; st_blend += ray.blended; st_term += ray.term;
 #ifdef GSRT_DIAG
         if (!STATS && lane == 0) {
@@ -1681,15 +1703,20 @@ void k_render_cor(const KArgs karg) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             acc[q] = acc[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[q]), 0xB1, 0xF, 0xF, false));
+        if constexpr (DEPTH)
+            acc_d = acc_d + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_d), 0xB1, 0xF, 0xF, false));
     }
     if (S > 2) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             acc[q] = acc[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[q]), 0x4E, 0xF, 0xF, false));
+        if constexpr (DEPTH)
+            acc_d = acc_d + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_d), 0x4E, 0xF, 0xF, false));
     }
     for (uint32_t off = 4; off < S; off <<= 1) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = acc[q] + __shfl_xor(acc[q], (int)off);
+        if constexpr (DEPTH) acc_d = acc_d + __shfl_xor(acc_d, (int)off);
     }
     for (uint32_t off = 1; STATS && off < S; off <<= 1) {
         st_cand += __shfl_xor(st_cand, (int)off);
@@ -1720,6 +1747,8 @@ void k_render_cor(const KArgs karg) {
         } else {
             reinterpret_cast<float4*>(K.a.out)[idx] = v;
         }
+        if constexpr (DEPTH)  // row-major whatever the colour's layout (a depth frame is never packed)
+            K.a.depth_out[(size_t)py * K.a.width + px] = (ns & (ns - 1)) == 0 ? acc_d * (1.0f / nsamp) : acc_d / nsamp;
         if (STATS && K.a.ray_stats)
             reinterpret_cast<uint4*>(K.a.ray_stats)[(size_t)py * K.a.width + px] = make_uint4(st_cand, st_blend, st_rounds, st_term);
     }
@@ -2123,9 +2152,9 @@ static bool debug_no_leaf_fp() {
     return e && e[0] == '1';
 }
 
-template <bool SH, bool LUT, bool STATS>
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false>
 static void launch_cor_t(hipStream_t st, const KArgs& k) {
-    hipLaunchKernelGGL((k_render_cor<SH, LUT, STATS>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
+    hipLaunchKernelGGL((k_render_cor<SH, LUT, STATS, DEPTH>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
 }
 
 // A rank of a sharded frame projects in sorted-leaf chunks (k_prep_cor) from this many ranks on: most 64-leaf chunks
@@ -2254,6 +2283,7 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     A.lut = ctx->d_lut;
     A.out = d_out;
     A.rs = d_rs;
+    A.depth_out = cor && !stats && !plan.packed && sync ? sync->depth : nullptr;
     A.ray_stats = stats ? ctx->d_ray_stats : nullptr;
     A.counters = ctx->d_counters;
     A.n = sc->n;
@@ -2629,6 +2659,9 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
                   : (stats ? launch_cor_t<true, false, true> : launch_cor_t<true, false, false>))
            : (lut ? (stats ? launch_cor_t<false, true, true> : launch_cor_t<false, true, false>)
                   : (stats ? launch_cor_t<false, false, true> : launch_cor_t<false, false, false>));
+    if (A.depth_out)  // GSRT_FLAG_DEPTH (never with stats, gsrt_api.cpp check_render_args)
+        render = sh ? (lut ? launch_cor_t<true, true, false, true> : launch_cor_t<true, false, false, true>)
+                    : (lut ? launch_cor_t<false, true, false, true> : launch_cor_t<false, false, false, true>);
     k.a.cull2d = stats ? 0u : 1u;  // the counting pass keeps every AABB candidate (|C_r| of SURVEY.md 8d)
     if (A.frontier && fr != ps) {  // pipelined: the frontier ran beside the projection; join it here
         GSRT_HIP(ctx, hipEventRecord(ctx->ev_front, fr));

@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("GSRT_LIB_PATH") or os.path.join(_HERE, "libgsrt.so") 
 OK, E_ARG, E_OOM, E_DEVICE, E_IO, E_STATE, E_COMM = 0, -1, -2, -3, -4, -5, -6
 PAGE_GAUSSIANS = 4096  # GSRT_PAGE_GAUSSIANS
 MODE_REF, MODE_COR = 0, 1
-FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8 = 0x100, 0x200, 0x400
+FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8, FLAG_DEPTH = 0x100, 0x200, 0x400, 0x800
 DUMP8_ESCAPE = 1 << 30  # GSRT_DUMP8_ESCAPE
 SYNTH_COR, SYNTH_REF, SYNTH_NEEDLE = 0, 1, 2
 
@@ -60,7 +60,7 @@ EXPORTS = [
     "gsrt_set_bands", "gsrt_last_bands", "gsrt_row_costs", "gsrt_dump8_read", "gsrt_dump8_encode", "gsrt_dump8_ppm",
     "gsrt_render_sharded_emulated_dump8", "gsrt_debug_share_costs", "gsrt_debug_row_profile", "gsrt_debug_streams", "gsrt_deal_units", "gsrt_dump8_layout",
     "gsrt_tile_pack_dump8_host", "gsrt_tile_unpack_dump8_host", "gsrt_timing_stride", "gsrt_partition_hash",
-    "gsrt_decide_bands",
+    "gsrt_decide_bands", "gsrt_render_depth", "gsrt_render_depth_async", "gsrt_depth_buffer", "gsrt_dump_pfm",
 ]
 
 
@@ -160,6 +160,10 @@ def _load():
         "gsrt_debug_row_profile": ([P, P, u32, P], i32),
         "gsrt_debug_streams": ([P, P, P], i32),
         "gsrt_deal_units": ([P, P, u32, P], i32),
+        "gsrt_render_depth": ([P, P, u32, u32, P, P], i32),
+        "gsrt_render_depth_async": ([P, P, u32, u32, P, P], i32),
+        "gsrt_depth_buffer": ([P], P),
+        "gsrt_dump_pfm": ([ctypes.c_char_p, P, u32, u32, u32], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -231,6 +235,16 @@ def dump_ppm(path, rgba):
     rgba = np.ascontiguousarray(rgba, np.float32)
     h, w = rgba.shape[:2]
     _check(lib.gsrt_dump_ppm(os.fsencode(path), _p(rgba), w, h))
+
+
+def dump_pfm(path, img):
+    """Portable float map of an (H, W) or (H, W, 1) image ("Pf") or an (H, W, 3) one ("PF"), e.g. a depth image:
+    scale -1.0 (little-endian float32), rows bottom to top (gsrt_dump_pfm)"""
+    img = np.ascontiguousarray(img, np.float32)
+    if img.ndim not in (2, 3):
+        raise GsrtError(E_ARG, "dump_pfm: an (H, W) or (H, W, channels) image")
+    h, w = img.shape[:2]
+    _check(lib.gsrt_dump_pfm(os.fsencode(path), _p(img), w, h, 1 if img.ndim == 2 else img.shape[2]))
 
 
 def dump8_encode(rgba):
@@ -485,6 +499,10 @@ class Context:
     @property
     def framebuffer_ptr(self) -> int:
         return lib.gsrt_framebuffer(self.handle) or 0
+
+    def depth_ptr(self) -> int:
+        """device address of the last frame's depth image (gsrt_depth_buffer); 0 when the last frame had none"""
+        return lib.gsrt_depth_buffer(self.handle) or 0
 
     def last_stats(self, per_ray_shape=None):
         out = np.zeros(8, np.uint64)
@@ -776,6 +794,21 @@ class Scene:
     def render_async(self, ubo, mode=MODE_COR, k=0, d_rgba: int = 0, d_raystate: int = 0):
         """Enqueue one frame on ctx.stream; outputs are device pointers (0 = keep in the framebuffer)."""
         _check(lib.gsrt_render_async(self.handle, _p(ubo), mode, k, d_rgba or None, d_raystate or None), self.ctx)
+
+    def render_depth(self, ubo, mode=MODE_COR, k=0):
+        """One COR frame with its expected depth (FLAG_DEPTH) to host memory: (rgba[H,W,4], depth[H,W]). depth is
+        the premultiplied sum of z w over each ray's blended hits (z: the Gaussian centre's view depth), combined over
+        the samples like the colour; divide by rgba[..., 3] for the normalised value (gsrt_render_depth)."""
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        rgba = np.zeros((H, W, 4), np.float32)
+        depth = np.zeros((H, W), np.float32)
+        _check(lib.gsrt_render_depth(self.handle, _p(ubo), mode, k, _p(rgba), _p(depth)), self.ctx)
+        return rgba, depth
+
+    def render_depth_async(self, ubo, mode=MODE_COR, k=0, d_rgba: int = 0, d_depth: int = 0):
+        """Enqueue one depth frame on ctx.stream; outputs are device pointers (0 = keep in the ctx buffers:
+        Context.framebuffer_ptr, Context.depth_ptr())."""
+        _check(lib.gsrt_render_depth_async(self.handle, _p(ubo), mode, k, d_rgba or None, d_depth or None), self.ctx)
 
     def render_sharded(self, ubo, mode=MODE_COR, k=0, want_image=True):
         W, H = int(ubo["width"][0]), int(ubo["height"][0])

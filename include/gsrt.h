@@ -71,8 +71,10 @@ enum {
                                depth-ordered blend, early stop at T<1e-4, jittered spp */
     GSRT_FLAG_LUT = 0x100,  /* COR: use the reference LinearExp LUT (ExpLUT.hpp) instead of exp */
     GSRT_FLAG_STATS = 0x200, /* also count candidates / blended hits (gsrt_last_stats) */
-    GSRT_FLAG_OUT_DUMP8 = 0x400 /* sharded COR frames: exchange and keep the frame as the integers its PPM dump prints
+    GSRT_FLAG_OUT_DUMP8 = 0x400, /* sharded COR frames: exchange and keep the frame as the integers its PPM dump prints
                                    (gsrt_dump8_*), 4 bytes per pixel instead of RGBA32F's 16 */
+    GSRT_FLAG_DEPTH = 0x800 /* whole COR frames: also write the expected view depth per pixel (gsrt_render_depth below);
+                               GSRT_E_ARG with REF, GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8 or a sharded entry point */
 };
 /* synthetic cloud kinds */
 enum { GSRT_SYNTH_COR = 0, GSRT_SYNTH_REF = 1, GSRT_SYNTH_NEEDLE = 2 };
@@ -226,6 +228,26 @@ gsrt_status gsrt_render_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t m
  * (gsrt_slot_streams) alternate between two buffers, so query it after each render rather than keeping it. NULL after
  * a GSRT_FLAG_OUT_DUMP8 sharded frame (its image is read with gsrt_dump8_read), until the next RGBA32F frame */
 const float* gsrt_framebuffer(gsrt_ctx* ctx);
+/* Expected depth of a COR frame (GSRT_FLAG_DEPTH). Per sample ray, over exactly the hits the colour blend takes (the same
+ * order, the same alpha, the same stop before a hit that would take T below 1e-4):
+ *     D = sum_i z_i w_i,   w_i = alpha_i T_i (the blend's own weight), accumulated front to back as fma(z_i, w_i, D),
+ * and a pixel's depth combines its samples' D exactly as its colour channels are combined. z_i is the float32 view depth
+ * of Gaussian i's centre (the key the hits are sorted by): the convention of rasterised 3DGS, not the point of maximum
+ * response along the ray. The value is premultiplied, like the colour: divide by rgba[3] for a normalised depth; a
+ * pixel that blends nothing holds 0. depth: W*H floats, row-major. The frame's RGBA is the plain frame's, bit for bit.
+ * A depth frame always takes the in-order path: one depth image per ctx, frames in stream order on gsrt_stream(), never
+ * on slot streams (gsrt_slot_streams reads 0 after it); plain frames before and after it choose as they do without it.
+ * Not provided: depth of sharded frames, depth on slot streams, median or nearest-hit depth, a normalised output.
+ * gsrt_render_depth sets the flag itself; rgba_out / depth_out are host or device pointers, either may be NULL (the
+ * images stay in gsrt_framebuffer / gsrt_depth_buffer); it blocks until the frame is done, like gsrt_render.
+ * gsrt_render / gsrt_render_async with the flag render the same frame and leave the depth in gsrt_depth_buffer. */
+gsrt_status gsrt_render_depth(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
+                              float* depth_out);
+/* the same, enqueued on gsrt_stream(); outputs (device pointers only) may be NULL */
+gsrt_status gsrt_render_depth_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
+                                    float* d_depth);
+/* device pointer of the last frame's depth image (W*H floats), or NULL when the last frame had none */
+const float* gsrt_depth_buffer(gsrt_ctx* ctx);
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into
@@ -334,6 +356,9 @@ gsrt_status gsrt_reference_ppm_name(char* out, size_t cap);
 gsrt_status gsrt_dump_rgba_text(const char* path, const float* rgba, uint32_t width, uint32_t height);
 /* Intel-path image.binary records {float r, g, b; uint32 offset = x + y*W} (vulkan_ray_tracing.cc:2165-2179) */
 gsrt_status gsrt_dump_image_binary(const char* path, const float* rgba, uint32_t width, uint32_t height);
+/* Portable float map of a host image with 1 ("Pf") or 3 ("PF") channels per pixel, e.g. a depth image: header
+ * "Pf\nW H\n-1.0\n" (negative scale: little-endian float32), then the rows bottom to top */
+gsrt_status gsrt_dump_pfm(const char* path, const float* data, uint32_t width, uint32_t height, uint32_t channels);
 
 
 
