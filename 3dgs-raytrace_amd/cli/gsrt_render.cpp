@@ -13,7 +13,10 @@
 // --fov DEG, --out PATH (PPM), --binary PATH (image.binary records), --text PATH (dump_image.sh lines),
 // --ply PATH (3DGS scene: COR mode, camera from --camera or looking down -z from the origin), --no-dump,
 // --device D, --frames F (with --benchmark: frames timed), --stats, --depth FILE (COR: the frame's expected depth,
-// GSRT_FLAG_DEPTH, as a one-channel PFM; a usage error with --mode ref or --stats).
+// GSRT_FLAG_DEPTH, as a one-channel PFM; a usage error with --mode ref or --stats), --features FILE --feature-channels C
+// (raw little-endian float32, n*C values: the scene's feature table) with --features-out FILE (COR: the feature frame,
+// GSRT_FLAG_FEATURES, as raw float32 H*W*C, and FILE.pfm when C is 1 or 3; usage errors: --mode ref, --stats, --depth,
+// C outside 1..16, one option of the pair without the other).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -35,7 +38,9 @@ struct Options {
     uint32_t gaussians = 10000, seed = 42, frames = 10;
     int device = 0;
     float fov = 0.0f;  // 0: scene default
-    std::string camera, out, binary, text, ply, depth;
+    std::string camera, out, binary, text, ply, depth, features, features_out;
+    uint32_t feature_channels = 0;
+    bool feature_channels_given = false;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -45,7 +50,7 @@ struct Options {
                  "                   [--bounces B] [--benchmark] [--mode ref|cor] [--lut] [--gaussians N] [--seed S]\n"
                  "                   [--sh] [--camera FILE] [--fov DEG] [--out PPM] [--binary FILE] [--no-dump]\n"
                  "                   [--text FILE] [--ply FILE] [--device D] [--frames F] [--stats]\n"
-                 "                   [--depth PFM]\n");
+                 "                   [--depth PFM] [--features FILE --feature-channels C --features-out FILE]\n");
     std::exit(2);
 }
 
@@ -87,6 +92,9 @@ Options parse(int argc, char** argv) {
         else if (a == "--text") o.text = val();
         else if (a == "--ply") o.ply = val();
         else if (a == "--depth") o.depth = val();
+        else if (a == "--features") o.features = val();
+        else if (a == "--features-out") o.features_out = val();
+        else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -96,6 +104,14 @@ Options parse(int argc, char** argv) {
     if (!o.width || !o.height) usage("empty frame");
     if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
     if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
+    if (!o.features.empty() || !o.features_out.empty() || o.feature_channels_given) {
+        if (o.features.empty() || o.features_out.empty() || !o.feature_channels_given)
+            usage("--features, --feature-channels and --features-out go together");
+        if (o.feature_channels < 1 || o.feature_channels > GSRT_MAX_FEATURES) usage("--feature-channels must be 1..16");
+        if (o.mode != "cor") usage("--features needs --mode cor (REF frames blend nothing)");
+        if (o.stats) usage("--features cannot be combined with --stats");
+        if (!o.depth.empty()) usage("--features cannot be combined with --depth");
+    }
     return o;
 }
 
@@ -175,6 +191,32 @@ int main(int argc, char** argv) {
         rc = check(gsrt_render_depth(scene, &ubo, mode, 0, rgba.data(), depth.data()), ctx, "render");
         if (!rc) rc = check(gsrt_dump_pfm(o.depth.c_str(), depth.data(), o.width, o.height, 1), ctx, "dump_pfm");
         if (!rc) std::printf("wrote %s\n", o.depth.c_str());
+    } else if (!rc && !o.features.empty()) {
+        // the table: n * C raw float32; the frame: H * W * C raw float32 (and a PFM of it when C is 1 or 3)
+        const uint32_t C = o.feature_channels;
+        std::vector<float> table((size_t)gsrt_scene_size(scene) * C), feat((size_t)o.width * o.height * C);
+        FILE* f = std::fopen(o.features.c_str(), "rb");
+        const bool whole = f && std::fread(table.data(), sizeof(float), table.size(), f) == table.size() &&
+                           std::fgetc(f) == EOF;
+        if (f) std::fclose(f);
+        if (!whole) {
+            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (Gaussians x channels)\n", o.features.c_str(),
+                         table.size());
+            rc = 1;
+        }
+        if (!rc) rc = check(gsrt_scene_set_features(scene, table.data(), C), ctx, "set_features");
+        if (!rc) rc = check(gsrt_render_features(scene, &ubo, mode, 0, rgba.data(), feat.data()), ctx, "render");
+        if (!rc) {
+            f = std::fopen(o.features_out.c_str(), "wb");
+            const bool ok = f && std::fwrite(feat.data(), sizeof(float), feat.size(), f) == feat.size();
+            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.features_out.c_str());
+        }
+        if (!rc) std::printf("wrote %s\n", o.features_out.c_str());
+        if (!rc && (C == 1 || C == 3)) {
+            const std::string pfm = o.features_out + ".pfm";
+            rc = check(gsrt_dump_pfm(pfm.c_str(), feat.data(), o.width, o.height, C), ctx, "dump_pfm");
+            if (!rc) std::printf("wrote %s\n", pfm.c_str());
+        }
     } else if (!rc) {
         rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
     }

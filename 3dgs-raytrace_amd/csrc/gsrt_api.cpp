@@ -233,6 +233,7 @@ void gsrt_destroy(gsrt_ctx* ctx) {
     }
     (void)hipFree(ctx->d_ray_stats);
     (void)hipFree(ctx->d_depth);
+    (void)hipFree(ctx->d_feat);
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_tile_counter);
     (void)hipFree(ctx->d_lut);
@@ -380,6 +381,40 @@ gsrt_status gsrt_scene_download(gsrt_scene* sc, gsrt_gauss_param* params, gsrt_a
 
 uint32_t gsrt_scene_size(const gsrt_scene* sc) { return sc ? sc->n : 0u; }
 
+// The table is kept as one 64-B row per Gaussian id (16 floats, channels >= C zero): the render kernel's stage DMA
+// fetches a row as four 16-B pieces beside the candidate's record. A host source is padded here before the copy, a
+// device source by a small kernel. No frame is in flight while the rows change (sync_all first).
+gsrt_status gsrt_scene_set_features(gsrt_scene* sc, const float* feat, uint32_t channels) {
+    if (!sc) return GSRT_E_ARG;
+    gsrt_ctx* ctx = sc->ctx;
+    if ((feat == nullptr) != (channels == 0))
+        return fail(ctx, GSRT_E_ARG, "set_features: a table needs 1..16 channels, NULL with 0 channels removes it");
+    if (channels > GSRT_MAX_FEATURES) return fail(ctx, GSRT_E_ARG, "set_features: more than GSRT_MAX_FEATURES channels");
+    (void)hipSetDevice(ctx->device);
+    if (gsrt_status s = gsrt::sync_all(ctx); s != GSRT_OK) return s;  // queued frames read the old rows
+    if (!feat) {
+        (void)hipFree(sc->d_feat_rows);
+        sc->d_feat_rows = nullptr;
+        sc->feat_channels = 0;
+        return GSRT_OK;
+    }
+    const size_t n = sc->n;
+    if (!sc->d_feat_rows) GSRT_HIP(ctx, hipMalloc(&sc->d_feat_rows, sizeof(float) * 16 * (n ? n : 1)));
+    if (is_device_ptr(feat)) {
+        gsrt::launch_pad_features(ctx->stream, sc->d_feat_rows, feat, sc->n, channels);
+        GSRT_HIP(ctx, hipGetLastError());
+    } else if (n) {
+        std::vector<float> rows(16 * n, 0.0f);
+        for (size_t i = 0; i < n; ++i) std::memcpy(&rows[16 * i], feat + i * channels, sizeof(float) * channels);
+        GSRT_HIP(ctx, hipMemcpyAsync(sc->d_feat_rows, rows.data(), sizeof(float) * 16 * n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    GSRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the source (and rows above) may go once the call returns
+    sc->feat_channels = channels;
+    return GSRT_OK;
+}
+
+uint32_t gsrt_scene_features(const gsrt_scene* sc) { return sc && sc->d_feat_rows ? sc->feat_channels : 0u; }
+
 void gsrt_destroy_scene(gsrt_scene* sc) {
     if (!sc) return;
     if (sc->ctx) {
@@ -399,6 +434,7 @@ void gsrt_destroy_scene(gsrt_scene* sc) {
                 if (sc->ev_ret[a][b][k]) (void)hipEventDestroy(sc->ev_ret[a][b][k]);
         }
     (void)hipFree(sc->d_sh);
+    (void)hipFree(sc->d_feat_rows);
     (void)hipFree(sc->d_flags);
     for (uint32_t b = 0; b < kSlots; ++b) {
         (void)hipFree(sc->d_recs[b]);
@@ -700,16 +736,25 @@ static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
         if (mode & GSRT_FLAG_STATS) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: not with GSRT_FLAG_STATS");
         if (mode & GSRT_FLAG_OUT_DUMP8) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: not with GSRT_FLAG_OUT_DUMP8");
     }
-    if ((mode & 0xffu) > GSRT_MODE_COR || (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH)))
+    if (mode & GSRT_FLAG_FEATURES) {  // a whole COR frame that blends the feature table instead of colour
+        if ((mode & 0xffu) != GSRT_MODE_COR) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: COR frames only");
+        if (mode & GSRT_FLAG_STATS) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_STATS");
+        if (mode & GSRT_FLAG_OUT_DUMP8) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_OUT_DUMP8");
+        if (mode & GSRT_FLAG_DEPTH) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_DEPTH");
+    }
+    if ((mode & 0xffu) > GSRT_MODE_COR ||
+        (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH | GSRT_FLAG_FEATURES)))
         return fail(sc->ctx, GSRT_E_ARG, "bad mode");
     if ((mode & 0xffu) == GSRT_MODE_COR && ubo->samples == 0) return fail(sc->ctx, GSRT_E_ARG, "samples == 0");
     if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
     if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
         return fail(sc->ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
+    if ((mode & GSRT_FLAG_FEATURES) && !gsrt_scene_features(sc))
+        return fail(sc->ctx, GSRT_E_STATE, "GSRT_FLAG_FEATURES: the scene has no feature table (gsrt_scene_set_features)");
     return GSRT_OK;
 }
 
-static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mode) {
+static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mode, uint32_t feat_channels = 0) {
     const size_t px = (size_t)ubo->width * ubo->height;
     gsrt_status s = grow(ctx, &ctx->d_fb, &ctx->fb_pixels, px * 4);
     if (s != GSRT_OK) return s;
@@ -722,7 +767,12 @@ static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mo
         s = grow(ctx, &ctx->d_depth, &ctx->depth_pixels, px);
         if (s != GSRT_OK) return s;
     }
+    if (mode & GSRT_FLAG_FEATURES) {
+        s = grow(ctx, &ctx->d_feat, &ctx->feat_floats, px * feat_channels);
+        if (s != GSRT_OK) return s;
+    }
     ctx->last_depth = (mode & GSRT_FLAG_DEPTH) != 0;
+    ctx->last_feat = (mode & GSRT_FLAG_FEATURES) != 0;
     ctx->last_w = ubo->width;
     ctx->last_h = ubo->height;
     ctx->last_stats = (mode & GSRT_FLAG_STATS) != 0;
@@ -730,22 +780,24 @@ static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mo
     return GSRT_OK;
 }
 
-// one frame on the render stream; d_depth (a GSRT_FLAG_DEPTH frame's copy of ctx->d_depth) may be nullptr
+// one frame on the render stream; d_depth (a GSRT_FLAG_DEPTH frame's copy of ctx->d_depth) and d_feat (a
+// GSRT_FLAG_FEATURES frame's copy of ctx->d_feat) may be nullptr
 static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
-                                gsrt_raystate* d_rs, float* d_depth) {
+                                gsrt_raystate* d_rs, float* d_depth, float* d_feat = nullptr) {
     gsrt_status s = check_render_args(sc, ubo, mode);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
-    s = prepare_frame(ctx, ubo, mode);
+    s = prepare_frame(ctx, ubo, mode, sc->feat_channels);
     if (s != GSRT_OK) return s;
     ctx->fb_dump8 = false;
     const gsrt::RenderPlan plan = gsrt::make_plan(*ubo, mode, k, 0, 1);
     gsrt::timing_mark(ctx, 0);
     // pipelined COR frames render into their own buffer while slot streams are chosen (their frames overlap); the
-    // ray states are one buffer, so frames that write them stay in order; so is the depth image (GSRT_FLAG_DEPTH)
-    const bool depth = (mode & GSRT_FLAG_DEPTH) != 0;
-    const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth &&
+    // ray states are one buffer, so frames that write them stay in order; so are the depth image (GSRT_FLAG_DEPTH) and
+    // the feature image (GSRT_FLAG_FEATURES)
+    const bool depth = (mode & GSRT_FLAG_DEPTH) != 0, feat = (mode & GSRT_FLAG_FEATURES) != 0;
+    const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth && !feat &&
                       gsrt::use_slot_streams(ctx, false);
     if (slot) {
         // the frame goes into one of two alternating buffers (the previous frame's render kernel may still write the
@@ -783,7 +835,8 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
         if ((s = gsrt_comm_fb_render_write(ctx)) != GSRT_OK) return s;  // d_fb is also rank 0's unpack target
         gsrt::RenderSync rsy;  // a shared output: frames in order (and render times sampled for use_slot_streams)
         if (depth) rsy.depth = ctx->d_depth;
-        s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth ? nullptr : &rsy);
+        if (feat) rsy.feat = ctx->d_feat;
+        s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
         ctx->fb_view = nullptr;
         if (d_rgba && d_rgba != ctx->d_fb)
@@ -791,6 +844,10 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
                                          hipMemcpyDeviceToDevice, ctx->stream));
         if (depth && d_depth && d_depth != ctx->d_depth)
             GSRT_HIP(ctx, hipMemcpyAsync(d_depth, ctx->d_depth, sizeof(float) * ubo->width * ubo->height,
+                                         hipMemcpyDeviceToDevice, ctx->stream));
+        if (feat && d_feat && d_feat != ctx->d_feat)
+            GSRT_HIP(ctx, hipMemcpyAsync(d_feat, ctx->d_feat,
+                                         sizeof(float) * ubo->width * ubo->height * sc->feat_channels,
                                          hipMemcpyDeviceToDevice, ctx->stream));
     }
     gsrt::timing_mark(ctx, 3);
@@ -833,6 +890,39 @@ gsrt_status gsrt_render_depth(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode
 }
 
 const float* gsrt_depth_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_depth ? ctx->d_depth : nullptr; }
+
+gsrt_status gsrt_render_features_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
+                                       float* d_feat) {
+    return render_async(sc, ubo, mode | GSRT_FLAG_FEATURES, k, d_rgba, nullptr, nullptr, d_feat);
+}
+
+gsrt_status gsrt_render_features(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
+                                 float* feat_out) {
+    mode |= GSRT_FLAG_FEATURES;
+    gsrt_status s = check_render_args(sc, ubo, mode);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const size_t px = (size_t)ubo->width * ubo->height;
+    const bool rgba_dev = is_device_ptr(rgba_out), feat_dev = is_device_ptr(feat_out);
+    s = render_async(sc, ubo, mode, k, rgba_dev ? rgba_out : nullptr, nullptr, nullptr, feat_dev ? feat_out : nullptr);
+    if (s == GSRT_OK && rgba_out && !rgba_dev) {
+        if (hipMemcpyAsync(rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px, hipMemcpyDeviceToHost,
+                           ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "framebuffer download failed");
+    }
+    if (s == GSRT_OK && feat_out && !feat_dev) {
+        if (hipMemcpyAsync(feat_out, ctx->d_feat, sizeof(float) * px * sc->feat_channels, hipMemcpyDeviceToHost,
+                           ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "feature image download failed");
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
+        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
+    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
+    return s;
+}
+
+const float* gsrt_feature_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_feat ? ctx->d_feat : nullptr; }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
                         gsrt_raystate* rs_out) {

@@ -354,6 +354,7 @@ gsrt_status gsrt_render_sharded_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint3
     if (!sc->bvh_built) return fail(ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
     if (ubo->width == 0 || ubo->height == 0 || (mode & 0xffu) > GSRT_MODE_COR) return GSRT_E_ARG;
     if (mode & GSRT_FLAG_DEPTH) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: whole frames only, not sharded ones");
+    if (mode & GSRT_FLAG_FEATURES) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: whole frames only, not sharded ones");
     if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     (void)hipSetDevice(ctx->device);
@@ -395,6 +396,7 @@ gsrt_status gsrt_render_sharded_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint3
     ctx->last_h = ubo->height;
     ctx->last_stats = false;
     ctx->last_depth = false;  // (gsrt_depth_buffer: the last frame wrote no depth image)
+    ctx->last_feat = false;   // (gsrt_feature_buffer likewise)
     ctx->fb_view = nullptr;  // sharded frames land in d_fb (rank 0's unpack)
     ctx->fb_dump8 = d8;      // a dump8 frame leaves no RGBA32F image (gsrt_dump8_read reads it)
     gsrt::timing_mark(ctx, 0);
@@ -797,6 +799,7 @@ static gsrt_status render_emulated(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t
     if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     if (mode & GSRT_FLAG_DEPTH) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: whole frames only, not sharded ones");
+    if (mode & GSRT_FLAG_FEATURES) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: whole frames only, not sharded ones");
     const bool d8 = (mode & GSRT_FLAG_OUT_DUMP8) != 0;
     if (d8 && ((mode & 0xffu) != GSRT_MODE_COR || (mode & GSRT_FLAG_STATS)))
         return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OUT_DUMP8: COR frames without GSRT_FLAG_STATS only");

@@ -153,6 +153,9 @@ struct gsrt_ctx {
     float* d_depth = nullptr;                  // GSRT_FLAG_DEPTH frames: W x H floats (one buffer: such frames stay in order)
     size_t depth_pixels = 0;
     bool last_depth = false;                   // the last frame wrote d_depth (gsrt_depth_buffer)
+    float* d_feat = nullptr;                   // GSRT_FLAG_FEATURES frames: W x H x C floats (one buffer, as d_depth)
+    size_t feat_floats = 0;
+    bool last_feat = false;                    // the last frame wrote d_feat (gsrt_feature_buffer)
     unsigned long long* d_counters = nullptr;  // kCounters words: [0..7] stats, [kErrWord] sticky error word
     uint32_t* d_tile_counter = nullptr;
     uint32_t last_w = 0, last_h = 0;
@@ -196,6 +199,8 @@ struct gsrt_scene {
     hipEvent_t ev_ret[2][2][3] = {};
     bool ret_rec[2][2][3] = {};
     float* d_sh = nullptr;
+    float* d_feat_rows = nullptr;                    // gsrt_scene_set_features: per Gaussian id one 64-B row of 16 floats,
+    uint32_t feat_channels = 0;                      // channels >= feat_channels zero; nullptr / 0 without a table
     uint32_t* d_flags = nullptr;                     // [0]: a keyed centre lay outside its AABB's depth bound (k_project,
                                                      // sticky until the next build): the traversals' depth cull is off
     gsrt::SplatRec* d_recs[kSlots] = {};             // per frame slot (FrameSlot); REF and stats use [0]
@@ -332,6 +337,8 @@ struct RenderSync {
     float4* accum = nullptr;
     // GSRT_FLAG_DEPTH (a whole COR frame on the in-order path): the frame's depth image, W x H floats, or nullptr
     float* depth = nullptr;
+    // GSRT_FLAG_FEATURES (likewise): the frame's feature image, W x H x feat_channels floats, or nullptr
+    float* feat = nullptr;
 };
 gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_rgba,
                           gsrt_raystate* d_rs, RenderSync* sync = nullptr);
@@ -354,6 +361,8 @@ uint32_t max_local_tiles(const RenderPlan& plan);  // over all ranks: the packed
 // device-to-device copy on s by a copy kernel of one-wave workgroups, each looping over its share (gsrt_scene.hip;
 // unaligned pointers or sizes fall back to hipMemcpyAsync)
 void launch_copy_d2d(hipStream_t s, void* dst, const void* src, size_t bytes);
+// feature rows (gsrt_scene.hip): rows[g][0..16) = src[g][0..channels) of a device source, zero from channels on
+void launch_pad_features(hipStream_t s, float* rows, const float* src, uint32_t n, uint32_t channels);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into
 inline float* framebuffer_of(gsrt_ctx* ctx) { return ctx->fb_view ? ctx->fb_view : ctx->d_fb; }
 // the prep stream must not overtake what is on ctx->stream now (scene upload/update, BVH build/refit)

@@ -106,7 +106,12 @@ struct RenderArgs {
                                      // depth bound (depth_lo): the traversals' depth cull is off while it is non-zero
     uint32_t depth_cull;             // the traversals' depth cull is on (where group lists overflow, launch_render)
     float* depth_out;                // COR with GSRT_FLAG_DEPTH: width x height floats, row-major (k_render_cor DEPTH);
-                                     // the last member, so that no other member's kernarg offset moved
+                                     // after the members before it, so that no other member's kernarg offset moved
+    // COR with GSRT_FLAG_FEATURES (k_render_cor FEAT), likewise appended: the image, width x height x feat_channels floats
+    // (row-major, pixel-interleaved), and the scene's table, one 64-B row of 16 floats per Gaussian id
+    float* feat_out;
+    const float* feat_rows;
+    uint32_t feat_channels;
 };
 
 #ifdef GSRT_WAVE_TIMES
@@ -694,6 +699,7 @@ __device__ GSRT_INLINE void add_counters(unsigned long long rays, unsigned long 
 
 // LDS stage of one group of sorted candidates: the 64-B records and the SH-3 coefficients. Filled by LDS-DMA
 // (global_load_lds, 16 B per lane, no VGPR destination): the stage is 16-B pieces in lane order, records first.
+// FEAT kernels stage no SH rows: the candidates' 64-B feature rows take the first kGroup * 64 B of sh (feat_row).
 struct Stage {
     SplatRec rec[kGroup];         // kGroup * 64 B
     float sh[kGroup][3][16];      // kGroup * 192 B, device layout [gauss][rgb][coef]
@@ -703,15 +709,15 @@ static_assert(sizeof(Stage) == kGroup * 256 && sizeof(Stage) % 1024 == 0, "whole
 // DMA instructions per stage (one 16-B piece per lane each), and the wait for the stage issued `younger`
 // stages before the most recent one: vmcnt counts VMEM operations in issue order, so vmcnt(younger * ops)
 // leaves the younger stages' DMAs in flight (any other younger VMEM operation only makes the wait stricter)
-template <bool SH>
-constexpr uint32_t kStagePieces = SH ? 16 * kGroup : 4 * kGroup;
-template <bool SH>
-constexpr uint32_t kStagePieceOps = (kStagePieces<SH> + 63) / 64;
+template <bool SH, bool FEAT = false>
+constexpr uint32_t kStagePieces = SH ? 16 * kGroup : (FEAT ? 8 * kGroup : 4 * kGroup);
+template <bool SH, bool FEAT = false>
+constexpr uint32_t kStagePieceOps = (kStagePieces<SH, FEAT> + 63) / 64;
 template <uint32_t N>
 __device__ GSRT_INLINE void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <bool SH>
+template <bool SH, bool FEAT = false>
 __device__ GSRT_INLINE void wait_stage(uint32_t younger) {
-    constexpr uint32_t P = kStagePieceOps<SH>;
+    constexpr uint32_t P = kStagePieceOps<SH, FEAT>;
     if (younger >= 2) wait_vmcnt<2 * P>();
     else if (younger == 1) wait_vmcnt<P>();
     else wait_vmcnt<0>();
@@ -730,22 +736,24 @@ __device__ GSRT_INLINE uint32_t lds_read_settled(const uint32_t* p) {
 // issue the LDS-DMA of group g0 of ids[0..count) into dst: piece p < 4*kGroup is quarter p&3 of record p>>2,
 // the next 12*kGroup pieces are the SH rows (12 pieces each); piece p lands at byte 16 p of the stage. Every
 // lane computes its piece's address the same way (base, row stride and offset selected, no divergent paths).
-// Waited for by wait_stage before the stage is read.
-template <bool SH>
+// Waited for by wait_stage before the stage is read. FEAT: sh is the feature table and a row is 4 pieces (64 B), so
+// the stage is 4 kGroup record pieces and 4 kGroup feature pieces, one DMA instruction.
+template <bool SH, bool FEAT = false>
 __device__ GSRT_INLINE void stage_issue(const uint32_t* ids, uint32_t count, uint32_t g0, uint32_t lane, Stage* dst,
                                    const SplatRec* recs, const float* sh) {
-    constexpr uint32_t kRecPieces = 4 * kGroup, kPieces = kStagePieces<SH>;
+    constexpr uint32_t kRecPieces = 4 * kGroup, kPieces = kStagePieces<SH, FEAT>;
+    constexpr uint32_t kRowPieces = FEAT ? 4u : 12u;  // 16-B pieces of a row of sh
 #pragma unroll
     for (uint32_t i = 0; i < (kPieces + 63) / 64; ++i) {
         const uint32_t p = i * 64 + lane;
         const bool is_rec = p < kRecPieces;
         const uint32_t q = p - kRecPieces;
-        uint32_t c = g0 + (is_rec ? p >> 2 : q / 12);
+        uint32_t c = g0 + (is_rec ? p >> 2 : q / kRowPieces);
         c = c < count ? c : g0;  // past the list's end: a copy of candidate g0 (never read; keeps lane 0 active)
         if (p < kPieces) {       // lane 0 always loads: each stage is exactly kStagePieceOps DMA instructions
             const uint32_t id = lds_read_settled(ids + c);
             const char* base = is_rec ? reinterpret_cast<const char*>(recs) : reinterpret_cast<const char*>(sh);
-            const uint32_t stride = is_rec ? 64u : 192u, off = is_rec ? (p & 3) * 16u : (q % 12) * 16u;
+            const uint32_t stride = is_rec ? 64u : kRowPieces * 16u, off = is_rec ? (p & 3) * 16u : (q % kRowPieces) * 16u;
             __builtin_amdgcn_global_load_lds((const void*)(base + (size_t)id * stride + off),
                                              (void*)(reinterpret_cast<char*>(dst) + i * 1024), 16, 0, 0);
         }
@@ -769,6 +777,7 @@ struct CorRay {
     float bs[16];
     float T, C[3];
     float D;  // DEPTH instantiations only: sum of z w over the blended hits (expected view depth, premultiplied)
+    float F[16];  // FEAT instantiations only (no bs there): sum of f_k w over the blended hits, per feature channel
     bool active;
     uint32_t cand, blended, term;
 #ifdef GSRT_DIAG
@@ -807,9 +816,16 @@ struct ShFromStage {  // the stage's LDS copy of candidate c's row
 // This lane's bit of a wave-uniform lane mask (a ballot held in an SGPR pair): the mask itself is the v_cndmask
 // or exec source, no compare forms it again.
 __device__ GSRT_INLINE bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
+// candidate c's feature row in a FEAT kernel's stage (stage_issue): 16 floats at a wave-uniform address
+__device__ GSRT_INLINE const float4* feat_row(const Stage* stg, uint32_t c) {
+    return reinterpret_cast<const float4*>(&stg->sh[0][0][0]) + 4 * c;
+}
 // DEPTH: z is the candidate's view depth (SplatRec::depth); the blend's own w also weighs it into ray.D
-template <bool SH, bool STATS, bool DEPTH = false, class ShSrc>
-__device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint64_t contrib, CorRay& ray, float z = 0.0f) {
+// FEAT: frow is the candidate's staged feature row (feat_row); w weighs its 16 floats into ray.F, and the colour
+// (1, as without SH) into C[0] alone: r = g = b, replicated once the ray is done (k_render_cor)
+template <bool SH, bool STATS, bool DEPTH = false, bool FEAT = false, class ShSrc>
+__device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint64_t contrib, CorRay& ray, float z = 0.0f,
+                                          const float4* frow = nullptr) {
     const float tn = ray.T * (1.0f - alpha);
     const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
     const uint64_t term = contrib & low;
@@ -820,9 +836,23 @@ __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint6
         if (lane_of(blend)) {
             const float w = alpha * ray.T;
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
-            ray.C[1] = fmaf(col[1], w, ray.C[1]);
-            ray.C[2] = fmaf(col[2], w, ray.C[2]);
+            if constexpr (!FEAT) {
+                ray.C[1] = fmaf(col[1], w, ray.C[1]);
+                ray.C[2] = fmaf(col[2], w, ray.C[2]);
+            }
             if constexpr (DEPTH) ray.D = fmaf(z, w, ray.D);
+            if constexpr (FEAT) {
+                // the row's address is wave-uniform: four broadcast ds_read_b128, under the lane mask (only the
+                // blending lanes use the values)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 f = frow[q];
+                    ray.F[4 * q + 0] = fmaf(f.x, w, ray.F[4 * q + 0]);
+                    ray.F[4 * q + 1] = fmaf(f.y, w, ray.F[4 * q + 1]);
+                    ray.F[4 * q + 2] = fmaf(f.z, w, ray.F[4 * q + 2]);
+                    ray.F[4 * q + 3] = fmaf(f.w, w, ray.F[4 * q + 3]);
+                }
+            }
             ray.T = tn;
             if (STATS) ++ray.blended;
         }
@@ -839,7 +869,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint6
 
 // Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
 // compile time (the steady state of shade_sorted), so no candidate is tested against m.
-template <bool SH, bool LUT, bool STATS, bool FULL = false, bool DEPTH = false>
+template <bool SH, bool LUT, bool STATS, bool FULL = false, bool DEPTH = false, bool FEAT = false>
 __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay& ray) {
     if (!STATS) {
         // Phase 1, g of all kGroup candidates at once (independent chains, one LDS wait): g first because lanes
@@ -895,7 +925,8 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
-            const uint64_t stopped = blend_hit<SH, STATS, DEPTH>(ShFromStage{stg, c}, alpha, contrib, ray, q0.w);
+            const uint64_t stopped = blend_hit<SH, STATS, DEPTH, FEAT>(ShFromStage{stg, c}, alpha, contrib, ray, q0.w,
+                                                                       FEAT ? feat_row(stg, c) : nullptr);
             if (stopped) {
 #pragma unroll
                 for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
@@ -933,22 +964,22 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
 // Three stage buffers: while stage k is shaded, the DMAs of stages k+1 and k+2 are in flight; wait_stage waits
 // for stage k's own DMA only. No DMA stays in flight past a return (the LDS is reused by the next round or by
 // the next workgroup).
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false>
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false>
 __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, Stage* stA, Stage* stB, Stage* stC,
                              const float* lut_s, CorRay& ray, const SplatRec* recs, const float* sh) {
     const uint32_t lane = lane_id();
     count = __builtin_amdgcn_readfirstlane(count);  // wave-uniform: stage bounds as scalar compares
     if (count == 0) return __ballot(ray.active) != 0;
-    auto issue = [&](uint32_t g, Stage* dst) { stage_issue<SH>(ids, count, g, lane, dst, recs, sh); };
+    auto issue = [&](uint32_t g, Stage* dst) { stage_issue<SH, FEAT>(ids, count, g, lane, dst, recs, sh); };
     auto shade = [&](Stage* stg, uint32_t g) {
         const uint32_t m = count - g < kGroup ? count - g : kGroup;
-        shade_stage<SH, LUT, STATS, false, DEPTH>(stg, m, lut_s, ray);
+        shade_stage<SH, LUT, STATS, false, DEPTH, FEAT>(stg, m, lut_s, ray);
     };
-    auto shade_full = [&](Stage* stg) { shade_stage<SH, LUT, STATS, true, DEPTH>(stg, kGroup, lut_s, ray); };
-    constexpr uint32_t kWaitTwo = 2 * kStagePieceOps<SH>;  // the two younger stages' DMAs stay in flight
+    auto shade_full = [&](Stage* stg) { shade_stage<SH, LUT, STATS, true, DEPTH, FEAT>(stg, kGroup, lut_s, ray); };
+    constexpr uint32_t kWaitTwo = 2 * kStagePieceOps<SH, FEAT>;  // the two younger stages' DMAs stay in flight
     // stages issued after stage g's DMA when it is read: those of g + kGroup and g + 2 kGroup that exist
     auto wait = [count](uint32_t g) {
-        wait_stage<SH>((g + kGroup < count ? 1u : 0u) + (g + 2 * kGroup < count ? 1u : 0u));
+        wait_stage<SH, FEAT>((g + kGroup < count ? 1u : 0u) + (g + 2 * kGroup < count ? 1u : 0u));
     };
     issue(0, stA);
     if (kGroup < count) issue(kGroup, stB);
@@ -1437,16 +1468,24 @@ __global__ __launch_bounds__(64) void k_collect_cor(const KArgs karg) {
         K.a.list_hdr[lt] = make_uint4(cl.count | (cl.more ? 0x80000000u : 0u), cl.total, (uint32_t)last, (uint32_t)(last >> 32));
 }
 
+// waves/SIMD asked for the two FEAT kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
+// spill to scratch)
+constexpr uint32_t kFeatWaves = 4;
 // DEPTH (GSRT_FLAG_DEPTH, never with STATS): the frame also writes its expected view depth, sum of z w over each ray's
 // blended hits (z = SplatRec::depth, w = the blend's alpha T), combined over the samples as the colour is, to
 // RenderArgs::depth_out. Everything it adds sits under if constexpr: the other instantiations' code does not change.
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false>
+// FEAT (GSRT_FLAG_FEATURES, only as <false, LUT, false, false, true>): a feature frame. The stage carries each
+// candidate's 64-B feature row instead of SH rows, the blend weighs its 16 floats into ray.F, and the frame writes
+// feat_channels of them per pixel to RenderArgs::feat_out, combined over the samples as the colour is. Its RGBA is the
+// no-SH frame's (colour 1). Likewise all under if constexpr.
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false>
 // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
 // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
 // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6))))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FEAT ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6))))
 void k_render_cor(const KArgs karg) {
     static_assert(!(DEPTH && STATS), "the counting pass has no depth output");
+    static_assert(!FEAT || (!SH && !STATS && !DEPTH), "a feature frame evaluates no SH, counts nothing, has no depth");
     // traversal buffers (keys, stack) and shading buffers (ids, two stages) are never live at once
     union CorLds {
         struct { uint64_t keys[kRBuf]; uint32_t stack[kRStack]; } t;
@@ -1460,7 +1499,7 @@ void k_render_cor(const KArgs karg) {
     uint32_t* const ids = L.l.ids;
     uint32_t* const lhdr = L.l.hdr;
     const SplatRec* const recs = kargs().a.recs;  // stage DMA sources, read once (kargs() is not hoisted)
-    const float* const shp = kargs().a.sh;
+    const float* const shp = FEAT ? kargs().a.feat_rows : kargs().a.sh;
     (void)karg;  // read through kargs()
     const uint32_t lane = lane_id();
 #ifdef GSRT_DIAG
@@ -1527,6 +1566,7 @@ void k_render_cor(const KArgs karg) {
     // accumulator lives (spilled) across the shading loop. The sums are formed in the same order either way.
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     [[maybe_unused]] float acc_d = 0.0f;  // DEPTH: the depth's sum, carried beside acc
+    [[maybe_unused]] float acc_f[16];     // FEAT: the channels' sums, likewise (set after every pass)
     uint32_t st_cand = 0, st_blend = 0, st_term = 0, st_rounds = 0, restarts = 0, maxc = 0;
 #ifdef GSRT_DIAG  // diagnostic build only: per-wave cycle split between traversal+sort and shading
     unsigned long long diag_collect = 0, diag_shade = 0;
@@ -1553,6 +1593,10 @@ void k_render_cor(const KArgs karg) {
         ray.T = 1.0f;
         ray.C[0] = ray.C[1] = ray.C[2] = 0.0f;
         if constexpr (DEPTH) ray.D = 0.0f;
+        if constexpr (FEAT) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) ray.F[q] = 0.0f;
+        }
         ray.active = valid;
         if (!valid) ray.pxs = __builtin_nanf("");  // see blend_hit
         ray.cand = ray.blended = ray.term = 0;
@@ -1649,7 +1693,7 @@ void k_render_cor(const KArgs karg) {
 #endif
             ++st_rounds;
             if (cl.total > maxc) maxc = cl.total;
-            const bool live = shade_sorted<SH, LUT, STATS, DEPTH>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
+            const bool live = shade_sorted<SH, LUT, STATS, DEPTH, FEAT>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
 #ifdef GSRT_DIAG
             diag_last = __builtin_amdgcn_s_memtime();
             diag_shade += diag_last - d1;
@@ -1658,6 +1702,7 @@ void k_render_cor(const KArgs karg) {
             has_lo = true;  // lo = the last (largest) key of this round
             __syncthreads();
         }
+        if constexpr (FEAT) ray.C[1] = ray.C[2] = ray.C[0];  // colour 1: the blend kept one channel (blend_hit)
         acc[0] = ray.C[0]; acc[1] = ray.C[1]; acc[2] = ray.C[2]; acc[3] = 1.0f - ray.T;  // = 0 + x exactly (x >= +0)
         if (passes > 1) {  // then S == 1 (make_plan): the lane's pixel accumulates its passes in order
             pixel(pix_in_tile, s_in, px, py, valid);
@@ -1683,6 +1728,24 @@ void k_render_cor(const KArgs karg) {
                 }
             }
         }
+        if constexpr (FEAT) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc_f[q] = ray.F[q];
+            if (passes > 1) {  // as the colour above: the feature image's own entry holds the running sums between passes
+                pixel(pix_in_tile, s_in, px, py, valid);
+                if (valid) {
+                    const uint32_t C = kargs().a.feat_channels;
+                    float* of = kargs().a.feat_out + ((size_t)py * kargs().a.width + px) * C;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {  // unrolled, a uniform guard: acc_f is never indexed dynamically
+                        if ((uint32_t)q < C) {
+                            if (pass > 0) acc_f[q] = of[q] + acc_f[q];
+                            if (pass + 1 < passes) of[q] = acc_f[q];
+                        }
+                    }
+                }
+            }
+        }
         st_cand += ray.cand; st_blend += ray.blended; st_term += ray.term;
 #ifdef GSRT_DIAG
         if (!STATS && lane == 0) {
@@ -1705,6 +1768,11 @@ void k_render_cor(const KArgs karg) {
             acc[q] = acc[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[q]), 0xB1, 0xF, 0xF, false));
         if constexpr (DEPTH)
             acc_d = acc_d + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_d), 0xB1, 0xF, 0xF, false));
+        if constexpr (FEAT) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                acc_f[q] = acc_f[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_f[q]), 0xB1, 0xF, 0xF, false));
+        }
     }
     if (S > 2) {
 #pragma unroll
@@ -1712,11 +1780,20 @@ void k_render_cor(const KArgs karg) {
             acc[q] = acc[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[q]), 0x4E, 0xF, 0xF, false));
         if constexpr (DEPTH)
             acc_d = acc_d + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_d), 0x4E, 0xF, 0xF, false));
+        if constexpr (FEAT) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                acc_f[q] = acc_f[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_f[q]), 0x4E, 0xF, 0xF, false));
+        }
     }
     for (uint32_t off = 4; off < S; off <<= 1) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = acc[q] + __shfl_xor(acc[q], (int)off);
         if constexpr (DEPTH) acc_d = acc_d + __shfl_xor(acc_d, (int)off);
+        if constexpr (FEAT) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc_f[q] = acc_f[q] + __shfl_xor(acc_f[q], (int)off);
+        }
     }
     for (uint32_t off = 1; STATS && off < S; off <<= 1) {
         st_cand += __shfl_xor(st_cand, (int)off);
@@ -1749,6 +1826,15 @@ void k_render_cor(const KArgs karg) {
         }
         if constexpr (DEPTH)  // row-major whatever the colour's layout (a depth frame is never packed)
             K.a.depth_out[(size_t)py * K.a.width + px] = (ns & (ns - 1)) == 0 ? acc_d * (1.0f / nsamp) : acc_d / nsamp;
+        if constexpr (FEAT) {  // feat_channels floats per pixel, and only those
+            const uint32_t C = K.a.feat_channels;
+            float* of = K.a.feat_out + ((size_t)py * K.a.width + px) * C;
+            const bool pow2 = (ns & (ns - 1)) == 0;
+            const float r = 1.0f / nsamp;
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if ((uint32_t)q < C) of[q] = pow2 ? acc_f[q] * r : acc_f[q] / nsamp;
+        }
         if (STATS && K.a.ray_stats)
             reinterpret_cast<uint4*>(K.a.ray_stats)[(size_t)py * K.a.width + px] = make_uint4(st_cand, st_blend, st_rounds, st_term);
     }
@@ -2152,9 +2238,9 @@ static bool debug_no_leaf_fp() {
     return e && e[0] == '1';
 }
 
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false>
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false>
 static void launch_cor_t(hipStream_t st, const KArgs& k) {
-    hipLaunchKernelGGL((k_render_cor<SH, LUT, STATS, DEPTH>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
+    hipLaunchKernelGGL((k_render_cor<SH, LUT, STATS, DEPTH, FEAT>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
 }
 
 // A rank of a sharded frame projects in sorted-leaf chunks (k_prep_cor) from this many ranks on: most 64-leaf chunks
@@ -2284,6 +2370,9 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     A.out = d_out;
     A.rs = d_rs;
     A.depth_out = cor && !stats && !plan.packed && sync ? sync->depth : nullptr;
+    A.feat_out = cor && !stats && !plan.packed && sync ? sync->feat : nullptr;
+    A.feat_rows = A.feat_out ? sc->d_feat_rows : nullptr;
+    A.feat_channels = A.feat_out ? sc->feat_channels : 0u;
     A.ray_stats = stats ? ctx->d_ray_stats : nullptr;
     A.counters = ctx->d_counters;
     A.n = sc->n;
@@ -2662,6 +2751,8 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     if (A.depth_out)  // GSRT_FLAG_DEPTH (never with stats, gsrt_api.cpp check_render_args)
         render = sh ? (lut ? launch_cor_t<true, true, false, true> : launch_cor_t<true, false, false, true>)
                     : (lut ? launch_cor_t<false, true, false, true> : launch_cor_t<false, false, false, true>);
+    if (A.feat_out)  // GSRT_FLAG_FEATURES (never with stats or depth): no SH whatever the scene holds
+        render = lut ? launch_cor_t<false, true, false, false, true> : launch_cor_t<false, false, false, false, true>;
     k.a.cull2d = stats ? 0u : 1u;  // the counting pass keeps every AABB candidate (|C_r| of SURVEY.md 8d)
     if (A.frontier && fr != ps) {  // pipelined: the frontier ran beside the projection; join it here
         GSRT_HIP(ctx, hipEventRecord(ctx->ev_front, fr));

@@ -147,4 +147,20 @@ void launch_copy_d2d(hipStream_t s, void* dst, const void* src, size_t bytes) {
                        reinterpret_cast<const uint4*>(src), n16);
 }
 
+// Feature rows of a device source (gsrt_scene_set_features): one thread per float of the padded table, so that a row
+// is 64 B at a 64-B multiple, which the render kernel's stage DMA fetches as four 16-B pieces
+__global__ __launch_bounds__(256) void k_pad_features(float* __restrict__ rows, const float* __restrict__ src, size_t n16,
+                                                      uint32_t channels) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n16) return;
+    const uint32_t k = (uint32_t)(i & 15u);
+    rows[i] = k < channels ? src[(i >> 4) * channels + k] : 0.0f;
+}
+
+void launch_pad_features(hipStream_t s, float* rows, const float* src, uint32_t n, uint32_t channels) {
+    const size_t n16 = (size_t)n * 16;
+    if (!n16) return;
+    hipLaunchKernelGGL(k_pad_features, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, s, rows, src, n16, channels);
+}
+
 }  // namespace gsrt

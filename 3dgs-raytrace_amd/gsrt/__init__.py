@@ -22,7 +22,8 @@ LIB_PATH = os.environ.get("GSRT_LIB_PATH") or os.path.join(_HERE, "libgsrt.so") 
 OK, E_ARG, E_OOM, E_DEVICE, E_IO, E_STATE, E_COMM = 0, -1, -2, -3, -4, -5, -6
 PAGE_GAUSSIANS = 4096  # GSRT_PAGE_GAUSSIANS
 MODE_REF, MODE_COR = 0, 1
-FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8, FLAG_DEPTH = 0x100, 0x200, 0x400, 0x800
+FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8, FLAG_DEPTH, FLAG_FEATURES = 0x100, 0x200, 0x400, 0x800, 0x1000
+MAX_FEATURES = 16  # GSRT_MAX_FEATURES
 DUMP8_ESCAPE = 1 << 30  # GSRT_DUMP8_ESCAPE
 SYNTH_COR, SYNTH_REF, SYNTH_NEEDLE = 0, 1, 2
 
@@ -61,6 +62,8 @@ EXPORTS = [
     "gsrt_render_sharded_emulated_dump8", "gsrt_debug_share_costs", "gsrt_debug_row_profile", "gsrt_debug_streams", "gsrt_deal_units", "gsrt_dump8_layout",
     "gsrt_tile_pack_dump8_host", "gsrt_tile_unpack_dump8_host", "gsrt_timing_stride", "gsrt_partition_hash",
     "gsrt_decide_bands", "gsrt_render_depth", "gsrt_render_depth_async", "gsrt_depth_buffer", "gsrt_dump_pfm",
+    "gsrt_scene_set_features", "gsrt_scene_features", "gsrt_render_features", "gsrt_render_features_async",
+    "gsrt_feature_buffer",
 ]
 
 
@@ -164,6 +167,11 @@ def _load():
         "gsrt_render_depth_async": ([P, P, u32, u32, P, P], i32),
         "gsrt_depth_buffer": ([P], P),
         "gsrt_dump_pfm": ([ctypes.c_char_p, P, u32, u32, u32], i32),
+        "gsrt_scene_set_features": ([P, P, u32], i32),
+        "gsrt_scene_features": ([P], u32),
+        "gsrt_render_features": ([P, P, u32, u32, P, P], i32),
+        "gsrt_render_features_async": ([P, P, u32, u32, P, P], i32),
+        "gsrt_feature_buffer": ([P], P),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -504,6 +512,10 @@ class Context:
         """device address of the last frame's depth image (gsrt_depth_buffer); 0 when the last frame had none"""
         return lib.gsrt_depth_buffer(self.handle) or 0
 
+    def features_ptr(self) -> int:
+        """device address of the last frame's feature image (gsrt_feature_buffer); 0 when the last frame had none"""
+        return lib.gsrt_feature_buffer(self.handle) or 0
+
     def last_stats(self, per_ray_shape=None):
         out = np.zeros(8, np.uint64)
         per = np.zeros(per_ray_shape + (4,), np.uint32) if per_ray_shape else None
@@ -809,6 +821,42 @@ class Scene:
         """Enqueue one depth frame on ctx.stream; outputs are device pointers (0 = keep in the ctx buffers:
         Context.framebuffer_ptr, Context.depth_ptr())."""
         _check(lib.gsrt_render_depth_async(self.handle, _p(ubo), mode, k, d_rgba or None, d_depth or None), self.ctx)
+
+    def set_features(self, feat, channels=None):
+        """The scene's feature table for render_features: an (n, C) float32 array, 1 <= C <= MAX_FEATURES, copied
+        (a (n,) array is one channel), or a device address of n * channels floats; None removes it. Waits for every
+        queued frame first (gsrt_scene_set_features)."""
+        if feat is None:
+            _check(lib.gsrt_scene_set_features(self.handle, None, 0), self.ctx)
+            return
+        if isinstance(feat, int):
+            _check(lib.gsrt_scene_set_features(self.handle, ctypes.c_void_p(feat), channels or 0), self.ctx)
+            return
+        feat = np.ascontiguousarray(feat, np.float32)
+        if feat.ndim == 1:
+            feat = feat[:, None]
+        if feat.ndim != 2 or feat.shape[0] != self.n:
+            raise GsrtError(E_ARG, "set_features: an (n, channels) array")
+        _check(lib.gsrt_scene_set_features(self.handle, _p(feat), feat.shape[1]), self.ctx)
+
+    def features(self) -> int:
+        """channels of the scene's feature table, 0 without one (gsrt_scene_features)"""
+        return int(lib.gsrt_scene_features(self.handle))
+
+    def render_features(self, ubo, mode=MODE_COR, k=0):
+        """One feature frame (FLAG_FEATURES) to host memory: (rgba[H,W,4], feat[H,W,C]). feat[..., c] is the
+        premultiplied sum of f_c w over each ray's blended hits, combined over the samples like the colour; rgba is the
+        frame without SH rows (r = g = b = sum w, a = 1 - T): divide by it to normalise (gsrt_render_features)."""
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        rgba = np.zeros((H, W, 4), np.float32)
+        feat = np.zeros((H, W, max(self.features(), 1)), np.float32)
+        _check(lib.gsrt_render_features(self.handle, _p(ubo), mode, k, _p(rgba), _p(feat)), self.ctx)
+        return rgba, feat
+
+    def render_features_async(self, ubo, mode=MODE_COR, k=0, d_rgba: int = 0, d_feat: int = 0):
+        """Enqueue one feature frame on ctx.stream; outputs are device pointers (0 = keep in the ctx buffers:
+        Context.framebuffer_ptr, Context.features_ptr())."""
+        _check(lib.gsrt_render_features_async(self.handle, _p(ubo), mode, k, d_rgba or None, d_feat or None), self.ctx)
 
     def render_sharded(self, ubo, mode=MODE_COR, k=0, want_image=True):
         W, H = int(ubo["width"][0]), int(ubo["height"][0])

@@ -73,8 +73,11 @@ enum {
     GSRT_FLAG_STATS = 0x200, /* also count candidates / blended hits (gsrt_last_stats) */
     GSRT_FLAG_OUT_DUMP8 = 0x400, /* sharded COR frames: exchange and keep the frame as the integers its PPM dump prints
                                    (gsrt_dump8_*), 4 bytes per pixel instead of RGBA32F's 16 */
-    GSRT_FLAG_DEPTH = 0x800 /* whole COR frames: also write the expected view depth per pixel (gsrt_render_depth below);
+    GSRT_FLAG_DEPTH = 0x800, /* whole COR frames: also write the expected view depth per pixel (gsrt_render_depth below);
                                GSRT_E_ARG with REF, GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8 or a sharded entry point */
+    GSRT_FLAG_FEATURES = 0x1000 /* whole COR frames: blend the scene's feature table instead of colour
+                                   (gsrt_render_features below); GSRT_E_ARG with REF, GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8,
+                                   GSRT_FLAG_DEPTH or a sharded entry point; GSRT_E_STATE without a feature table */
 };
 /* synthetic cloud kinds */
 enum { GSRT_SYNTH_COR = 0, GSRT_SYNTH_REF = 1, GSRT_SYNTH_NEEDLE = 2 };
@@ -117,6 +120,15 @@ gsrt_status gsrt_scene_from_model(gsrt_ctx* ctx, const float* center, const floa
 gsrt_status gsrt_scene_download(gsrt_scene* scene, gsrt_gauss_param* params, gsrt_aabb* aabbs);
 uint32_t gsrt_scene_size(const gsrt_scene* scene);
 void gsrt_destroy_scene(gsrt_scene* scene);
+/* Per-Gaussian feature channels for feature frames (GSRT_FLAG_FEATURES, gsrt_render_features). feat: n*channels floats
+ * laid out [gauss][channel], a host or device pointer, copied (into one 64-byte row per Gaussian); 1 <= channels <=
+ * GSRT_MAX_FEATURES. feat == NULL with channels == 0 removes the table; channels == 0 with data, or above
+ * GSRT_MAX_FEATURES, is GSRT_E_ARG. The call first waits for every queued frame of the context, then replaces the table.
+ * Features are indexed by Gaussian id: gsrt_scene_update, gsrt_scene_attach, gsrt_scene_stream_pages and refits leave
+ * them as they are. gsrt_scene_features: the channel count, 0 when the scene has no table. */
+#define GSRT_MAX_FEATURES 16u
+gsrt_status gsrt_scene_set_features(gsrt_scene* scene, const float* feat, uint32_t channels);
+uint32_t gsrt_scene_features(const gsrt_scene* scene);
 
 /* 3DGS .ply ingestion (the reference only has hard-coded CreateGauss calls,
  * SceneList.cpp:123-125). Vertex properties x y z, scale_0..2 (log), rot_0..3 (w x y z, unnormalised),
@@ -248,6 +260,32 @@ gsrt_status gsrt_render_depth_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint
                                     float* d_depth);
 /* device pointer of the last frame's depth image (W*H floats), or NULL when the last frame had none */
 const float* gsrt_depth_buffer(gsrt_ctx* ctx);
+/* Feature frame (GSRT_FLAG_FEATURES): a whole COR frame that blends the scene's feature table (gsrt_scene_set_features,
+ * C channels) with the renderer's own weights. Per sample ray and channel c, over exactly the hits the colour blend takes
+ * (the same candidates and order, the same alpha with its min(., 0.99) and lower cut, the same stop before a hit that
+ * would take T below 1e-4):
+ *     F_c = sum_i f_{g_i,c} w_i,   w_i = alpha_i T_i, accumulated front to back as fma(f, w_i, F_c) from +0,
+ * and a pixel's F_c combines its samples' exactly as its colour channels and depth are combined. No clamp, no offset, no
+ * normalisation: the values are premultiplied, negative and non-finite features pass through as IEEE arithmetic gives
+ * them, a pixel that blends nothing holds +0 in every channel. feat: W*H*C floats, row-major, pixel-interleaved.
+ * The frame's RGBA is that of the same geometry rendered without SH rows (colour 1), bit for bit, whether or not the
+ * scene has SH rows: r = g = b = sum w (the normaliser), a = 1 - T; a feature frame evaluates no SH.
+ * Like a depth frame, a feature frame always takes the in-order path: one feature image per ctx, frames in stream order
+ * on gsrt_stream(), never on slot streams (gsrt_slot_streams reads 0 after it); plain frames before and after it choose
+ * as they do without it. GSRT_E_STATE when the scene has no feature table.
+ * Not provided: more than GSRT_MAX_FEATURES channels, features of sharded frames or on slot streams, colour in the same
+ * frame, a normalised output.
+ * gsrt_render_features sets the flag itself; rgba_out / feat_out are host or device pointers, either may be NULL (the
+ * images stay in gsrt_framebuffer / gsrt_feature_buffer); it blocks until the frame is done, like gsrt_render.
+ * gsrt_render / gsrt_render_async with the flag render the same frame and leave the image in gsrt_feature_buffer. */
+gsrt_status gsrt_render_features(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
+                                 float* feat_out);
+/* the same, enqueued on gsrt_stream(); outputs (device pointers only) may be NULL */
+gsrt_status gsrt_render_features_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
+                                       float* d_feat);
+/* device pointer of the last frame's feature image (W*H*C floats), or NULL when the last frame had none (after a feature
+ * frame gsrt_depth_buffer reads NULL, after a depth frame this does) */
+const float* gsrt_feature_buffer(gsrt_ctx* ctx);
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into
