@@ -16,7 +16,10 @@
 // GSRT_FLAG_DEPTH, as a one-channel PFM; a usage error with --mode ref or --stats), --features FILE --feature-channels C
 // (raw little-endian float32, n*C values: the scene's feature table) with --features-out FILE (COR: the feature frame,
 // GSRT_FLAG_FEATURES, as raw float32 H*W*C, and FILE.pfm when C is 1 or 3; usage errors: --mode ref, --stats, --depth,
-// C outside 1..16, one option of the pair without the other).
+// C outside 1..16, one option of the pair without the other), --feature-grad FILE --feature-channels C
+// --feature-grad-out FILE (COR: a gradient frame, gsrt_render_feature_grad: the upstream gradient of a feature image, raw
+// float32 W*H*C, in; the gradient of the feature table, raw float32 n*C, out; no image is dumped; usage errors: --mode ref
+// or a REF-default scene, --stats, --depth, --features, C outside 1..16, one option without the others).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -38,7 +41,7 @@ struct Options {
     uint32_t gaussians = 10000, seed = 42, frames = 10;
     int device = 0;
     float fov = 0.0f;  // 0: scene default
-    std::string camera, out, binary, text, ply, depth, features, features_out;
+    std::string camera, out, binary, text, ply, depth, features, features_out, feature_grad, feature_grad_out;
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
 };
@@ -50,7 +53,8 @@ struct Options {
                  "                   [--bounces B] [--benchmark] [--mode ref|cor] [--lut] [--gaussians N] [--seed S]\n"
                  "                   [--sh] [--camera FILE] [--fov DEG] [--out PPM] [--binary FILE] [--no-dump]\n"
                  "                   [--text FILE] [--ply FILE] [--device D] [--frames F] [--stats]\n"
-                 "                   [--depth PFM] [--features FILE --feature-channels C --features-out FILE]\n");
+                 "                   [--depth PFM] [--features FILE --feature-channels C --features-out FILE]\n"
+                 "                   [--feature-grad FILE --feature-channels C --feature-grad-out FILE]\n");
     std::exit(2);
 }
 
@@ -94,6 +98,8 @@ Options parse(int argc, char** argv) {
         else if (a == "--depth") o.depth = val();
         else if (a == "--features") o.features = val();
         else if (a == "--features-out") o.features_out = val();
+        else if (a == "--feature-grad") o.feature_grad = val();
+        else if (a == "--feature-grad-out") o.feature_grad_out = val();
         else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
@@ -104,7 +110,15 @@ Options parse(int argc, char** argv) {
     if (!o.width || !o.height) usage("empty frame");
     if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
     if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
-    if (!o.features.empty() || !o.features_out.empty() || o.feature_channels_given) {
+    if (!o.feature_grad.empty() || !o.feature_grad_out.empty()) {
+        if (o.feature_grad.empty() || o.feature_grad_out.empty() || !o.feature_channels_given)
+            usage("--feature-grad, --feature-channels and --feature-grad-out go together");
+        if (o.feature_channels < 1 || o.feature_channels > GSRT_MAX_FEATURES) usage("--feature-channels must be 1..16");
+        if (o.mode != "cor") usage("--feature-grad needs --mode cor (REF frames blend nothing)");
+        if (o.stats) usage("--feature-grad cannot be combined with --stats");
+        if (!o.depth.empty()) usage("--feature-grad cannot be combined with --depth");
+        if (!o.features.empty() || !o.features_out.empty()) usage("--feature-grad cannot be combined with --features");
+    } else if (!o.features.empty() || !o.features_out.empty() || o.feature_channels_given) {
         if (o.features.empty() || o.features_out.empty() || !o.feature_channels_given)
             usage("--features, --feature-channels and --features-out go together");
         if (o.feature_channels < 1 || o.feature_channels > GSRT_MAX_FEATURES) usage("--feature-channels must be 1..16");
@@ -217,6 +231,26 @@ int main(int argc, char** argv) {
             rc = check(gsrt_dump_pfm(pfm.c_str(), feat.data(), o.width, o.height, C), ctx, "dump_pfm");
             if (!rc) std::printf("wrote %s\n", pfm.c_str());
         }
+    } else if (!rc && !o.feature_grad.empty()) {
+        // the upstream gradient: W * H * C raw float32; the table's gradient: n * C raw float32
+        const uint32_t C = o.feature_channels;
+        std::vector<float> gimg((size_t)o.width * o.height * C), gtab((size_t)gsrt_scene_size(scene) * C);
+        FILE* f = std::fopen(o.feature_grad.c_str(), "rb");
+        const bool whole = f && std::fread(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size() &&
+                           std::fgetc(f) == EOF;
+        if (f) std::fclose(f);
+        if (!whole) {
+            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x channels)\n", o.feature_grad.c_str(),
+                         gimg.size());
+            rc = 1;
+        }
+        if (!rc) rc = check(gsrt_render_feature_grad(scene, &ubo, mode, 0, gimg.data(), C, gtab.data(), 0), ctx, "render");
+        if (!rc) {
+            f = std::fopen(o.feature_grad_out.c_str(), "wb");
+            const bool ok = f && std::fwrite(gtab.data(), sizeof(float), gtab.size(), f) == gtab.size();
+            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.feature_grad_out.c_str());
+        }
+        if (!rc) std::printf("wrote %s\n", o.feature_grad_out.c_str());
     } else if (!rc) {
         rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
     }
@@ -239,7 +273,7 @@ int main(int argc, char** argv) {
         const double rays = (double)o.width * o.height * o.samples * frames;
         if (!rc) std::printf("%u frames %.3f ms/frame %.1f Mrays/s\n", frames, dt / frames * 1e3, rays / dt / 1e6);
     }
-    if (!rc && !o.no_dump) {
+    if (!rc && !o.no_dump && o.feature_grad.empty()) {  // a gradient run writes its table only
         std::string path = o.out;
         if (path.empty()) {
             char name[128];

@@ -234,6 +234,9 @@ void gsrt_destroy(gsrt_ctx* ctx) {
     (void)hipFree(ctx->d_ray_stats);
     (void)hipFree(ctx->d_depth);
     (void)hipFree(ctx->d_feat);
+    (void)hipFree(ctx->d_grad_rows);
+    (void)hipFree(ctx->d_grad_in);
+    (void)hipFree(ctx->d_grad_out);
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_tile_counter);
     (void)hipFree(ctx->d_lut);
@@ -727,10 +730,22 @@ gsrt_status gsrt_bvh_download(gsrt_scene* sc, uint32_t* nodes, uint32_t* leaf_gi
     return GSRT_OK;
 }
 
-static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode) {
+// grad_call: the caller is gsrt_render_feature_grad(_async), the only entry point that may carry GSRT_FLAG_FEATURE_GRAD
+static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, bool grad_call = false) {
     if (!sc || !ubo) return GSRT_E_ARG;
     if (ubo->width == 0 || ubo->height == 0 || ubo->width > 32768 || ubo->height > 32768)
         return fail(sc->ctx, GSRT_E_ARG, "bad frame size");
+    if (mode & GSRT_FLAG_FEATURE_GRAD) {  // a whole COR frame that scatters a gradient image to the Gaussians it blends
+        const char* why = nullptr;
+        if (!grad_call) why = "GSRT_FLAG_FEATURE_GRAD: only through gsrt_render_feature_grad (the gradient image goes there)";
+        else if ((mode & 0xffu) != GSRT_MODE_COR) why = "GSRT_FLAG_FEATURE_GRAD: COR frames only";
+        else if (mode & GSRT_FLAG_STATS) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_STATS";
+        else if (mode & GSRT_FLAG_OUT_DUMP8) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_OUT_DUMP8";
+        else if (mode & GSRT_FLAG_DEPTH) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_DEPTH";
+        else if (mode & GSRT_FLAG_FEATURES) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_FEATURES";
+        else if (sc->ntri) why = "GSRT_FLAG_FEATURE_GRAD: not for a scene with a triangle mesh";
+        if (why) return fail(sc->ctx, GSRT_E_ARG, why);
+    }
     if (mode & GSRT_FLAG_DEPTH) {  // a whole COR frame's second output; the counting pass and dump codes carry none
         if ((mode & 0xffu) != GSRT_MODE_COR) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: COR frames only");
         if (mode & GSRT_FLAG_STATS) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: not with GSRT_FLAG_STATS");
@@ -743,7 +758,7 @@ static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
         if (mode & GSRT_FLAG_DEPTH) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_DEPTH");
     }
     if ((mode & 0xffu) > GSRT_MODE_COR ||
-        (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH | GSRT_FLAG_FEATURES)))
+        (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH | GSRT_FLAG_FEATURES | GSRT_FLAG_FEATURE_GRAD)))
         return fail(sc->ctx, GSRT_E_ARG, "bad mode");
     if ((mode & 0xffu) == GSRT_MODE_COR && ubo->samples == 0) return fail(sc->ctx, GSRT_E_ARG, "samples == 0");
     if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
@@ -780,11 +795,19 @@ static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mo
     return GSRT_OK;
 }
 
+// a GSRT_FLAG_FEATURE_GRAD frame's device buffers (gsrt_render_feature_grad_async)
+struct GradFrame {
+    const float* d_in;   // the upstream gradient image, W x H x channels floats
+    float* d_rows;       // the zeroed gradient table, n rows of 16 floats
+    uint32_t channels;
+};
+
 // one frame on the render stream; d_depth (a GSRT_FLAG_DEPTH frame's copy of ctx->d_depth) and d_feat (a
-// GSRT_FLAG_FEATURES frame's copy of ctx->d_feat) may be nullptr
+// GSRT_FLAG_FEATURES frame's copy of ctx->d_feat) may be nullptr; gf: a GSRT_FLAG_FEATURE_GRAD frame's buffers, else nullptr
 static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
-                                gsrt_raystate* d_rs, float* d_depth, float* d_feat = nullptr) {
-    gsrt_status s = check_render_args(sc, ubo, mode);
+                                gsrt_raystate* d_rs, float* d_depth, float* d_feat = nullptr,
+                                const GradFrame* gf = nullptr) {
+    gsrt_status s = check_render_args(sc, ubo, mode, gf != nullptr);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
@@ -795,9 +818,10 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
     gsrt::timing_mark(ctx, 0);
     // pipelined COR frames render into their own buffer while slot streams are chosen (their frames overlap); the
     // ray states are one buffer, so frames that write them stay in order; so are the depth image (GSRT_FLAG_DEPTH) and
-    // the feature image (GSRT_FLAG_FEATURES)
+    // the feature image (GSRT_FLAG_FEATURES) and a gradient frame's table (GSRT_FLAG_FEATURE_GRAD)
     const bool depth = (mode & GSRT_FLAG_DEPTH) != 0, feat = (mode & GSRT_FLAG_FEATURES) != 0;
-    const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth && !feat &&
+    const bool grad = (mode & GSRT_FLAG_FEATURE_GRAD) != 0;
+    const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth && !feat && !grad &&
                       gsrt::use_slot_streams(ctx, false);
     if (slot) {
         // the frame goes into one of two alternating buffers (the previous frame's render kernel may still write the
@@ -836,7 +860,12 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
         gsrt::RenderSync rsy;  // a shared output: frames in order (and render times sampled for use_slot_streams)
         if (depth) rsy.depth = ctx->d_depth;
         if (feat) rsy.feat = ctx->d_feat;
-        s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat ? nullptr : &rsy);
+        if (grad) {
+            rsy.grad_in = gf->d_in;
+            rsy.grad_rows = gf->d_rows;
+            rsy.grad_channels = gf->channels;
+        }
+        s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat && !grad ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
         ctx->fb_view = nullptr;
         if (d_rgba && d_rgba != ctx->d_fb)
@@ -923,6 +952,75 @@ gsrt_status gsrt_render_features(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t m
 }
 
 const float* gsrt_feature_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_feat ? ctx->d_feat : nullptr; }
+
+// The frame zeroes the ctx's gradient rows (n x 16 floats, 64-B rows: the shape the render kernel's atomics take), the
+// render kernel adds every blended hit's terms to them, and a small kernel compacts them into the caller's n x channels
+// table, all in order on the render stream.
+static gsrt_status check_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const float* grad_image,
+                                   uint32_t channels, const float* grad_table) {
+    if (!sc || !ubo) return GSRT_E_ARG;
+    if (channels < 1 || channels > GSRT_MAX_FEATURES)
+        return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: channels must be 1..GSRT_MAX_FEATURES");
+    if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: grad_image is NULL");
+    if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: grad_table is NULL");
+    return check_render_args(sc, ubo, mode, true);
+}
+
+gsrt_status gsrt_render_feature_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                           const float* d_grad_image, uint32_t channels, float* d_grad_table,
+                                           int accumulate) {
+    mode |= GSRT_FLAG_FEATURE_GRAD;
+    gsrt_status s = check_grad_args(sc, ubo, mode, d_grad_image, channels, d_grad_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const size_t rows = (size_t)16 * (sc->n ? sc->n : 1);
+    if (ctx->grad_rows_floats < rows || !ctx->d_grad_rows) {  // a queued frame may still use the old rows
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_rows, &ctx->grad_rows_floats, rows)) != GSRT_OK) return s;
+    }
+    GSRT_HIP(ctx, hipMemsetAsync(ctx->d_grad_rows, 0, sizeof(float) * rows, ctx->stream));
+    const GradFrame gf{d_grad_image, ctx->d_grad_rows, channels};
+    s = render_async(sc, ubo, mode, k, nullptr, nullptr, nullptr, nullptr, &gf);
+    if (s != GSRT_OK) return s;
+    gsrt::launch_grad_compact(ctx->stream, d_grad_table, ctx->d_grad_rows, sc->n, channels, accumulate != 0);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_render_feature_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                     const float* grad_image, uint32_t channels, float* grad_table, int accumulate) {
+    mode |= GSRT_FLAG_FEATURE_GRAD;
+    gsrt_status s = check_grad_args(sc, ubo, mode, grad_image, channels, grad_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
+    if (accumulate && !out_dev)
+        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: accumulate needs a device grad_table");
+    const size_t in_floats = (size_t)ubo->width * ubo->height * channels, out_floats = (size_t)sc->n * channels;
+    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
+    }
+    if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_out, &ctx->grad_out_floats, out_floats ? out_floats : 1)) != GSRT_OK) return s;
+    }
+    if (!in_dev)
+        GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
+    s = gsrt_render_feature_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in, channels,
+                                       out_dev ? grad_table : ctx->d_grad_out, accumulate);
+    if (s == GSRT_OK && !out_dev && out_floats) {
+        if (hipMemcpyAsync(grad_table, ctx->d_grad_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, ctx->stream) !=
+            hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "gradient table download failed");
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
+        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
+    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
+    return s;
+}
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
                         gsrt_raystate* rs_out) {

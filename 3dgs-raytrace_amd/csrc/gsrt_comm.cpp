@@ -355,6 +355,8 @@ gsrt_status gsrt_render_sharded_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint3
     if (ubo->width == 0 || ubo->height == 0 || (mode & 0xffu) > GSRT_MODE_COR) return GSRT_E_ARG;
     if (mode & GSRT_FLAG_DEPTH) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: whole frames only, not sharded ones");
     if (mode & GSRT_FLAG_FEATURES) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: whole frames only, not sharded ones");
+    if (mode & GSRT_FLAG_FEATURE_GRAD)
+        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: whole frames only, not sharded ones");
     if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     (void)hipSetDevice(ctx->device);
@@ -800,6 +802,8 @@ static gsrt_status render_emulated(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     if (mode & GSRT_FLAG_DEPTH) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: whole frames only, not sharded ones");
     if (mode & GSRT_FLAG_FEATURES) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: whole frames only, not sharded ones");
+    if (mode & GSRT_FLAG_FEATURE_GRAD)
+        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: whole frames only, not sharded ones");
     const bool d8 = (mode & GSRT_FLAG_OUT_DUMP8) != 0;
     if (d8 && ((mode & 0xffu) != GSRT_MODE_COR || (mode & GSRT_FLAG_STATS)))
         return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OUT_DUMP8: COR frames without GSRT_FLAG_STATS only");

@@ -156,6 +156,14 @@ struct gsrt_ctx {
     float* d_feat = nullptr;                   // GSRT_FLAG_FEATURES frames: W x H x C floats (one buffer, as d_depth)
     size_t feat_floats = 0;
     bool last_feat = false;                    // the last frame wrote d_feat (gsrt_feature_buffer)
+    // GSRT_FLAG_FEATURE_GRAD frames (one set of buffers: such frames stay in order): the gradient table the render
+    // kernel adds to, n rows of 16 floats; a host gradient image's device copy; a host table's compact device copy
+    float* d_grad_rows = nullptr;
+    size_t grad_rows_floats = 0;
+    float* d_grad_in = nullptr;
+    size_t grad_in_floats = 0;
+    float* d_grad_out = nullptr;
+    size_t grad_out_floats = 0;
     unsigned long long* d_counters = nullptr;  // kCounters words: [0..7] stats, [kErrWord] sticky error word
     uint32_t* d_tile_counter = nullptr;
     uint32_t last_w = 0, last_h = 0;
@@ -339,6 +347,11 @@ struct RenderSync {
     float* depth = nullptr;
     // GSRT_FLAG_FEATURES (likewise): the frame's feature image, W x H x feat_channels floats, or nullptr
     float* feat = nullptr;
+    // GSRT_FLAG_FEATURE_GRAD (likewise): the upstream gradient image, W x H x grad_channels floats, and the zeroed
+    // gradient table the frame adds to, n rows of 16 floats; or nullptr
+    const float* grad_in = nullptr;
+    float* grad_rows = nullptr;
+    uint32_t grad_channels = 0;
 };
 gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_rgba,
                           gsrt_raystate* d_rs, RenderSync* sync = nullptr);
@@ -363,6 +376,8 @@ uint32_t max_local_tiles(const RenderPlan& plan);  // over all ranks: the packed
 void launch_copy_d2d(hipStream_t s, void* dst, const void* src, size_t bytes);
 // feature rows (gsrt_scene.hip): rows[g][0..16) = src[g][0..channels) of a device source, zero from channels on
 void launch_pad_features(hipStream_t s, float* rows, const float* src, uint32_t n, uint32_t channels);
+// gradient rows (gsrt_scene.hip): dst[g][0..channels) = rows[g][0..channels), or += when accumulate
+void launch_grad_compact(hipStream_t s, float* dst, const float* rows, uint32_t n, uint32_t channels, bool accumulate);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into
 inline float* framebuffer_of(gsrt_ctx* ctx) { return ctx->fb_view ? ctx->fb_view : ctx->d_fb; }
 // the prep stream must not overtake what is on ctx->stream now (scene upload/update, BVH build/refit)

@@ -58,6 +58,13 @@ constexpr uint32_t kNoGroup = 0xFFFFFFFFu;
 #define GSRT_GROUP_REGSORT 1
 #endif
 constexpr bool kGroupRegSort = GSRT_GROUP_REGSORT != 0;
+// A/B knobs of the GRAD kernels (kGradWaves, shade_stage)
+#ifndef GSRT_GRAD_WAVES
+#define GSRT_GRAD_WAVES 5
+#endif
+#ifndef GSRT_GRAD_AB
+#define GSRT_GRAD_AB 0
+#endif
 constexpr uint32_t kSG = 4;        // super-group: kSG x kSG groups sharing one traversal frontier
 constexpr uint32_t kFront = 128;   // frontier entries per super-group
 
@@ -112,6 +119,12 @@ struct RenderArgs {
     float* feat_out;
     const float* feat_rows;
     uint32_t feat_channels;
+    // COR gradient frames (GSRT_FLAG_FEATURE_GRAD, k_render_cor GRAD), likewise appended: the upstream gradient image,
+    // width x height x grad_channels floats laid out as a feature image, and the gradient table the frame adds to, one
+    // 64-B row of 16 floats per Gaussian id (zeroed before the frame, compacted after it: launch_grad_compact)
+    const float* grad_in;
+    float* grad_rows;
+    uint32_t grad_channels;
 };
 
 #ifdef GSRT_WAVE_TIMES
@@ -820,12 +833,58 @@ __device__ GSRT_INLINE bool lane_of(uint64_t mask) { return __builtin_amdgcn_inv
 __device__ GSRT_INLINE const float4* feat_row(const Stage* stg, uint32_t c) {
     return reinterpret_cast<const float4*>(&stg->sh[0][0][0]) + 4 * c;
 }
+// GRAD: the sums of t[0..16) over the lanes of each 16-lane row, transposed: lane l returns the sum of t[l & 15] over
+// its row. A butterfly that halves the channels a lane carries at every step: partners 15 - i (row_mirror), 7 - i within
+// 8 lanes (row_half_mirror), i ^ 2 and i ^ 1 (quad permutes). A lane keeps the half its own lane bit names and sends
+// the other half, which is the half its partner keeps: 8 + 4 + 2 + 1 = 15 DPP moves instead of 16 x 4 for one
+// reduction per channel. The four partner sets of a lane tile its row, so every lane's term enters each sum once.
+template <int CTRL>
+__device__ GSRT_INLINE float dpp_from(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+__device__ GSRT_INLINE float grad_row_sums(const float (&t)[16]) {
+    const bool b3 = lane_of(0xFF00FF00FF00FF00ull), b2 = lane_of(0xF0F0F0F0F0F0F0F0ull);
+    const bool b1 = lane_of(0xCCCCCCCCCCCCCCCCull), b0 = lane_of(0xAAAAAAAAAAAAAAAAull);
+    float a[8], b[4], c[2];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = (b3 ? t[8 + k] : t[k]) + dpp_from<0x140>(b3 ? t[k] : t[8 + k]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k] = (b2 ? a[4 + k] : a[k]) + dpp_from<0x141>(b2 ? a[k] : a[4 + k]);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) c[k] = (b1 ? b[2 + k] : b[k]) + dpp_from<0x4E>(b1 ? b[k] : b[2 + k]);
+    return (b0 ? c[1] : c[0]) + dpp_from<0xB1>(b0 ? c[0] : c[1]);
+}
+// GRAD: a stage's four row sums per lane (gs[c]: candidate c, channel l & 15, the lane's 16-lane row) to the wave's sums,
+// transposed once more: lane 16 c + ch returns the wave's sum of candidate c's channel ch. v_permlane32_swap exchanges
+// the upper 32 lanes of its first operand with the lower 32 of its second, v_permlane16_swap the odd 16-lane rows of the
+// first with the even rows of the second: after either, first + second holds the first operand's sum on the lanes
+// that kept it and the second's on the others. Three swaps and three adds.
+__device__ GSRT_INLINE float grad_stage_sums(const float (&gs)[kGroup]) {
+    static_assert(kGroup == 4, "one candidate per 16-lane row");
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 p = __builtin_amdgcn_permlane32_swap(__float_as_uint(gs[0]), __float_as_uint(gs[2]), false, false);
+    const u32x2 q = __builtin_amdgcn_permlane32_swap(__float_as_uint(gs[1]), __float_as_uint(gs[3]), false, false);
+    const float u = __uint_as_float(p.x) + __uint_as_float(p.y);  // candidate 0 on lanes 0..31, candidate 2 above
+    const float v = __uint_as_float(q.x) + __uint_as_float(q.y);  // candidates 1 and 3
+    const u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(u), __float_as_uint(v), false, false);
+    return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+// GRAD: where a stage's gradient goes: the stage's candidate ids (ids + g0 of the round's list in LDS), the gradient
+// table's rows and the channel count. Empty in every other instantiation.
+struct GradOut {
+    const uint32_t* ids = nullptr;
+    float* rows = nullptr;
+    uint32_t channels = 0;
+};
 // DEPTH: z is the candidate's view depth (SplatRec::depth); the blend's own w also weighs it into ray.D
 // FEAT: frow is the candidate's staged feature row (feat_row); w weighs its 16 floats into ray.F, and the colour
 // (1, as without SH) into C[0] alone: r = g = b, replicated once the ray is done (k_render_cor)
-template <bool SH, bool STATS, bool DEPTH = false, bool FEAT = false, class ShSrc>
+// GRAD: ray.F holds the lane's upstream gradient G_c / ns (k_render_cor); the candidate's terms t_c = w G_c of the
+// blending lanes (+0, selected, on every other lane) are summed over each 16-lane row into *gsum (grad_row_sums), and
+// the colour is the feature frame's
+template <bool SH, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false, class ShSrc>
 __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint64_t contrib, CorRay& ray, float z = 0.0f,
-                                          const float4* frow = nullptr) {
+                                          const float4* frow = nullptr, float* gsum = nullptr, bool* gany = nullptr) {
     const float tn = ray.T * (1.0f - alpha);
     const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
     const uint64_t term = contrib & low;
@@ -833,10 +892,19 @@ __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint6
     if (blend) {
         float col[3] = {1.0f, 1.0f, 1.0f};
         if (SH) shsrc(ray.bs, col);
+        if constexpr (GRAD) {
+            const float w = alpha * ray.T;  // the blend's own weight (T is updated below)
+            const bool mine = lane_of(blend);
+            float t[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) t[q] = mine ? w * ray.F[q] : 0.0f;  // a select: another lane's G never enters
+            *gsum = grad_row_sums(t);
+            *gany = true;  // wave-uniform: some lane blended this candidate
+        }
         if (lane_of(blend)) {
             const float w = alpha * ray.T;
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
-            if constexpr (!FEAT) {
+            if constexpr (!FEAT && !GRAD) {
                 ray.C[1] = fmaf(col[1], w, ray.C[1]);
                 ray.C[2] = fmaf(col[2], w, ray.C[2]);
             }
@@ -869,8 +937,11 @@ __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint6
 
 // Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
 // compile time (the steady state of shade_sorted), so no candidate is tested against m.
-template <bool SH, bool LUT, bool STATS, bool FULL = false, bool DEPTH = false, bool FEAT = false>
-__device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay& ray) {
+// GRAD: the stage's terms w G go to the gradient table (go) in one atomic wave-instruction, lane 16 c + ch adding the
+// wave's sum for candidate c and channel ch, masked to the candidates some lane blended and to the channels in use.
+template <bool SH, bool LUT, bool STATS, bool FULL = false, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
+__device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay& ray,
+                                        const GradOut& go = GradOut{}) {
     if (!STATS) {
         // Phase 1, g of all kGroup candidates at once (independent chains, one LDS wait): g first because lanes
         // that miss mostly fail it, and a candidate no lane passes is skipped with one wave-uniform branch.
@@ -881,6 +952,8 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
         // okg[c] is the wave's lane mask of candidate c (a ballot: an SGPR pair, no VGPR flag per lane).
         float gv[kGroup];
         uint64_t okg[kGroup];
+        [[maybe_unused]] float gsums[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};  // GRAD: the candidates' row sums (blend_hit)
+        [[maybe_unused]] uint32_t gmask = 0;                           // GRAD: bit c: some lane blended candidate c
 #pragma unroll
         for (uint32_t c = 0; c < kGroup; ++c) {
             const float4 q2 = reinterpret_cast<const float4*>(&stg->rec[c])[2];  // ppx, ppy, A/2, B
@@ -925,11 +998,34 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
-            const uint64_t stopped = blend_hit<SH, STATS, DEPTH, FEAT>(ShFromStage{stg, c}, alpha, contrib, ray, q0.w,
-                                                                       FEAT ? feat_row(stg, c) : nullptr);
+            [[maybe_unused]] bool gany = false;
+            const uint64_t stopped = blend_hit<SH, STATS, DEPTH, FEAT, GRAD>(ShFromStage{stg, c}, alpha, contrib, ray, q0.w,
+                                                                             FEAT ? feat_row(stg, c) : nullptr,
+                                                                             GRAD ? &gsums[c] : nullptr, GRAD ? &gany : nullptr);
+            if constexpr (GRAD) gmask |= gany ? 1u << c : 0u;
             if (stopped) {
 #pragma unroll
                 for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
+            }
+        }
+        if constexpr (GRAD) {
+            if (gmask) {  // wave-uniform: a stage no lane blended adds nothing
+                const float sum = grad_stage_sums(gsums);
+                const uint32_t l = lane_here(), c = l >> 4, ch = l & 15u;
+                // a blended candidate c is below m, so ids[c] is an entry of the round's list: its id is below n and its
+                // row inside the table; channels from `channels` on (G holds +0 there) are left out
+                if (((gmask >> c) & 1u) && ch < go.channels) {
+                    const uint32_t id = lds_read_settled(go.ids + c);
+#if GSRT_GRAD_AB == 1  // timing only: the reduction without its atomic
+                    asm volatile("" ::"v"(sum), "v"(id));
+#elif GSRT_GRAD_AB == 2  // counting: channel 0 counts the adds a row receives, channel 1 the wave-instructions
+                    const float one = ch == 0 || c == (uint32_t)__builtin_ctz(gmask) ? 1.0f : 0.0f;
+                    asm volatile("" ::"v"(sum));
+                    atomicAdd(go.rows + (size_t)id * 16u + ch, one);
+#else
+                    atomicAdd(go.rows + (size_t)id * 16u + ch, sum);  // no-return global_atomic_add_f32
+#endif
+                }
             }
         }
         return;
@@ -964,18 +1060,23 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
 // Three stage buffers: while stage k is shaded, the DMAs of stages k+1 and k+2 are in flight; wait_stage waits
 // for stage k's own DMA only. No DMA stays in flight past a return (the LDS is reused by the next round or by
 // the next workgroup).
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false>
+// GRAD: every shaded stage also adds its terms to the gradient table grows (shade_stage); its atomics are younger than
+// the DMAs the counted waits wait for, so those waits only become stricter, and the last wait covers them too.
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
 __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, Stage* stA, Stage* stB, Stage* stC,
-                             const float* lut_s, CorRay& ray, const SplatRec* recs, const float* sh) {
+                             const float* lut_s, CorRay& ray, const SplatRec* recs, const float* sh,
+                             float* grows = nullptr, uint32_t gchannels = 0) {
     const uint32_t lane = lane_id();
     count = __builtin_amdgcn_readfirstlane(count);  // wave-uniform: stage bounds as scalar compares
     if (count == 0) return __ballot(ray.active) != 0;
     auto issue = [&](uint32_t g, Stage* dst) { stage_issue<SH, FEAT>(ids, count, g, lane, dst, recs, sh); };
     auto shade = [&](Stage* stg, uint32_t g) {
         const uint32_t m = count - g < kGroup ? count - g : kGroup;
-        shade_stage<SH, LUT, STATS, false, DEPTH, FEAT>(stg, m, lut_s, ray);
+        shade_stage<SH, LUT, STATS, false, DEPTH, FEAT, GRAD>(stg, m, lut_s, ray, GradOut{ids + g, grows, gchannels});
     };
-    auto shade_full = [&](Stage* stg) { shade_stage<SH, LUT, STATS, true, DEPTH, FEAT>(stg, kGroup, lut_s, ray); };
+    auto shade_full = [&](Stage* stg, uint32_t g) {
+        shade_stage<SH, LUT, STATS, true, DEPTH, FEAT, GRAD>(stg, kGroup, lut_s, ray, GradOut{ids + g, grows, gchannels});
+    };
     constexpr uint32_t kWaitTwo = 2 * kStagePieceOps<SH, FEAT>;  // the two younger stages' DMAs stay in flight
     // stages issued after stage g's DMA when it is read: those of g + kGroup and g + 2 kGroup that exist
     auto wait = [count](uint32_t g) {
@@ -993,15 +1094,15 @@ __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, St
         for (; g0 + 4 * kGroup < count; g0 += 3 * kGroup) {
             issue(g0 + 2 * kGroup, stC);
             wait_vmcnt<kWaitTwo>();
-            shade_full(stA);
+            shade_full(stA, g0);
             if (!__ballot(ray.active)) { live = false; break; }
             issue(g0 + 3 * kGroup, stA);
             wait_vmcnt<kWaitTwo>();
-            shade_full(stB);
+            shade_full(stB, g0 + kGroup);
             if (!__ballot(ray.active)) { live = false; break; }
             issue(g0 + 4 * kGroup, stB);
             wait_vmcnt<kWaitTwo>();
-            shade_full(stC);
+            shade_full(stC, g0 + 2 * kGroup);
             if (!__ballot(ray.active)) { live = false; break; }
         }
     }
@@ -1471,6 +1572,11 @@ __global__ __launch_bounds__(64) void k_collect_cor(const KArgs karg) {
 // waves/SIMD asked for the two FEAT kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
 // spill to scratch)
 constexpr uint32_t kFeatWaves = 4;
+// and for the two GRAD kernels, likewise from the register report (96 VGPRs, no spill at 5 waves; at 6 the no-LUT kernel
+// spills 12 VGPRs to scratch and the LUT kernel stays at 96; 5 measured 4-5 % faster than 4: DESIGN.md section 3). A/B builds (make ab AB_FLAGS=...,
+// never the product library) set GSRT_GRAD_WAVES, or GSRT_GRAD_AB: 1 leaves the stage's atomic out (timing only), 2 makes
+// it count adds per row and wave-instructions instead of summing (profiles/feature_grad_cost.py); defaults at the top
+constexpr uint32_t kGradWaves = GSRT_GRAD_WAVES;
 // DEPTH (GSRT_FLAG_DEPTH, never with STATS): the frame also writes its expected view depth, sum of z w over each ray's
 // blended hits (z = SplatRec::depth, w = the blend's alpha T), combined over the samples as the colour is, to
 // RenderArgs::depth_out. Everything it adds sits under if constexpr: the other instantiations' code does not change.
@@ -1478,14 +1584,21 @@ constexpr uint32_t kFeatWaves = 4;
 // candidate's 64-B feature row instead of SH rows, the blend weighs its 16 floats into ray.F, and the frame writes
 // feat_channels of them per pixel to RenderArgs::feat_out, combined over the samples as the colour is. Its RGBA is the
 // no-SH frame's (colour 1). Likewise all under if constexpr.
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false>
+// GRAD (GSRT_FLAG_FEATURE_GRAD, only as <false, LUT, false, false, false, true>): the backward of a feature frame to the
+// feature table. A lane holds its pixel's upstream gradient G[p, 0..C) / ns where a FEAT kernel holds ray.F; the stage
+// carries records only; for every blended hit the terms w G_c are summed over the wave and added to the Gaussian's row
+// of RenderArgs::grad_rows with float atomics (shade_stage). Its RGBA is the feature frame's. Likewise all under
+// if constexpr.
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
 // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
 // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
 // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FEAT ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6))))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
+    GRAD ? kGradWaves : FEAT ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6))))
 void k_render_cor(const KArgs karg) {
     static_assert(!(DEPTH && STATS), "the counting pass has no depth output");
     static_assert(!FEAT || (!SH && !STATS && !DEPTH), "a feature frame evaluates no SH, counts nothing, has no depth");
+    static_assert(!GRAD || (!SH && !STATS && !DEPTH && !FEAT), "a gradient frame is a feature frame without its table");
     // traversal buffers (keys, stack) and shading buffers (ids, two stages) are never live at once
     union CorLds {
         struct { uint64_t keys[kRBuf]; uint32_t stack[kRStack]; } t;
@@ -1597,6 +1710,24 @@ void k_render_cor(const KArgs karg) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) ray.F[q] = 0.0f;
         }
+        if constexpr (GRAD) {
+            // the pixel's upstream gradient, scaled once by 1 / ns as the forward store scales the sums; channels from
+            // grad_channels on and invalid lanes hold +0 (unrolled, a uniform guard: ray.F is never indexed dynamically)
+            const KArgs& K = kargs();
+            const uint32_t C = K.a.grad_channels, nsg = S * passes;
+            const bool pow2 = (nsg & (nsg - 1)) == 0;
+            const float nsf = (float)nsg, r = 1.0f / nsf;
+            const float* gi = K.a.grad_in + ((size_t)py * K.a.width + px) * C;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                float v = 0.0f;
+                if (valid && (uint32_t)q < C) {
+                    v = gi[q];
+                    v = pow2 ? v * r : v / nsf;
+                }
+                ray.F[q] = v;
+            }
+        }
         ray.active = valid;
         if (!valid) ray.pxs = __builtin_nanf("");  // see blend_hit
         ray.cand = ray.blended = ray.term = 0;
@@ -1693,7 +1824,12 @@ void k_render_cor(const KArgs karg) {
 #endif
             ++st_rounds;
             if (cl.total > maxc) maxc = cl.total;
-            const bool live = shade_sorted<SH, LUT, STATS, DEPTH, FEAT>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
+            bool live;
+            if constexpr (GRAD)
+                live = shade_sorted<SH, LUT, STATS, DEPTH, FEAT, GRAD>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
+                                                                       kargs().a.grad_rows, kargs().a.grad_channels);
+            else
+                live = shade_sorted<SH, LUT, STATS, DEPTH, FEAT>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
 #ifdef GSRT_DIAG
             diag_last = __builtin_amdgcn_s_memtime();
             diag_shade += diag_last - d1;
@@ -1702,7 +1838,7 @@ void k_render_cor(const KArgs karg) {
             has_lo = true;  // lo = the last (largest) key of this round
             __syncthreads();
         }
-        if constexpr (FEAT) ray.C[1] = ray.C[2] = ray.C[0];  // colour 1: the blend kept one channel (blend_hit)
+        if constexpr (FEAT || GRAD) ray.C[1] = ray.C[2] = ray.C[0];  // colour 1: the blend kept one channel (blend_hit)
         acc[0] = ray.C[0]; acc[1] = ray.C[1]; acc[2] = ray.C[2]; acc[3] = 1.0f - ray.T;  // = 0 + x exactly (x >= +0)
         if (passes > 1) {  // then S == 1 (make_plan): the lane's pixel accumulates its passes in order
             pixel(pix_in_tile, s_in, px, py, valid);
@@ -2238,9 +2374,9 @@ static bool debug_no_leaf_fp() {
     return e && e[0] == '1';
 }
 
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false>
+template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
 static void launch_cor_t(hipStream_t st, const KArgs& k) {
-    hipLaunchKernelGGL((k_render_cor<SH, LUT, STATS, DEPTH, FEAT>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
+    hipLaunchKernelGGL((k_render_cor<SH, LUT, STATS, DEPTH, FEAT, GRAD>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
 }
 
 // A rank of a sharded frame projects in sorted-leaf chunks (k_prep_cor) from this many ranks on: most 64-leaf chunks
@@ -2373,6 +2509,10 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     A.feat_out = cor && !stats && !plan.packed && sync ? sync->feat : nullptr;
     A.feat_rows = A.feat_out ? sc->d_feat_rows : nullptr;
     A.feat_channels = A.feat_out ? sc->feat_channels : 0u;
+    const bool grad = cor && !stats && !plan.packed && sync && sync->grad_rows && !A.depth_out && !A.feat_out;
+    A.grad_in = grad ? sync->grad_in : nullptr;
+    A.grad_rows = grad ? sync->grad_rows : nullptr;
+    A.grad_channels = grad ? sync->grad_channels : 0u;
     A.ray_stats = stats ? ctx->d_ray_stats : nullptr;
     A.counters = ctx->d_counters;
     A.n = sc->n;
@@ -2753,6 +2893,9 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
                     : (lut ? launch_cor_t<false, true, false, true> : launch_cor_t<false, false, false, true>);
     if (A.feat_out)  // GSRT_FLAG_FEATURES (never with stats or depth): no SH whatever the scene holds
         render = lut ? launch_cor_t<false, true, false, false, true> : launch_cor_t<false, false, false, false, true>;
+    if (A.grad_rows)  // GSRT_FLAG_FEATURE_GRAD (never with stats, depth or features): likewise no SH
+        render = lut ? launch_cor_t<false, true, false, false, false, true>
+                     : launch_cor_t<false, false, false, false, false, true>;
     k.a.cull2d = stats ? 0u : 1u;  // the counting pass keeps every AABB candidate (|C_r| of SURVEY.md 8d)
     if (A.frontier && fr != ps) {  // pipelined: the frontier ran beside the projection; join it here
         GSRT_HIP(ctx, hipEventRecord(ctx->ev_front, fr));

@@ -163,4 +163,22 @@ void launch_pad_features(hipStream_t s, float* rows, const float* src, uint32_t 
     hipLaunchKernelGGL(k_pad_features, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, s, rows, src, n16, channels);
 }
 
+// Gradient rows of a gradient frame (gsrt_render_feature_grad) to the caller's table: one thread per output float,
+// dst[g][c] = rows[g][c] of the 64-B rows the render kernel added to, or dst[g][c] += it when accumulate
+__global__ __launch_bounds__(256) void k_grad_compact(float* __restrict__ dst, const float* __restrict__ rows, size_t nc,
+                                                      uint32_t channels, uint32_t accumulate) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nc) return;
+    const size_t g = i / channels;
+    const float v = rows[g * 16 + (i - g * channels)];
+    dst[i] = accumulate ? dst[i] + v : v;
+}
+
+void launch_grad_compact(hipStream_t s, float* dst, const float* rows, uint32_t n, uint32_t channels, bool accumulate) {
+    const size_t nc = (size_t)n * channels;
+    if (!nc) return;
+    hipLaunchKernelGGL(k_grad_compact, dim3((uint32_t)((nc + 255) / 256)), dim3(256), 0, s, dst, rows, nc, channels,
+                       accumulate ? 1u : 0u);
+}
+
 }  // namespace gsrt

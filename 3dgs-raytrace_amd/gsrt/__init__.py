@@ -23,6 +23,7 @@ OK, E_ARG, E_OOM, E_DEVICE, E_IO, E_STATE, E_COMM = 0, -1, -2, -3, -4, -5, -6
 PAGE_GAUSSIANS = 4096  # GSRT_PAGE_GAUSSIANS
 MODE_REF, MODE_COR = 0, 1
 FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8, FLAG_DEPTH, FLAG_FEATURES = 0x100, 0x200, 0x400, 0x800, 0x1000
+FLAG_FEATURE_GRAD = 0x2000
 MAX_FEATURES = 16  # GSRT_MAX_FEATURES
 DUMP8_ESCAPE = 1 << 30  # GSRT_DUMP8_ESCAPE
 SYNTH_COR, SYNTH_REF, SYNTH_NEEDLE = 0, 1, 2
@@ -63,7 +64,7 @@ EXPORTS = [
     "gsrt_tile_pack_dump8_host", "gsrt_tile_unpack_dump8_host", "gsrt_timing_stride", "gsrt_partition_hash",
     "gsrt_decide_bands", "gsrt_render_depth", "gsrt_render_depth_async", "gsrt_depth_buffer", "gsrt_dump_pfm",
     "gsrt_scene_set_features", "gsrt_scene_features", "gsrt_render_features", "gsrt_render_features_async",
-    "gsrt_feature_buffer",
+    "gsrt_feature_buffer", "gsrt_render_feature_grad", "gsrt_render_feature_grad_async",
 ]
 
 
@@ -172,6 +173,8 @@ def _load():
         "gsrt_render_features": ([P, P, u32, u32, P, P], i32),
         "gsrt_render_features_async": ([P, P, u32, u32, P, P], i32),
         "gsrt_feature_buffer": ([P], P),
+        "gsrt_render_feature_grad": ([P, P, u32, u32, P, u32, P, i32], i32),
+        "gsrt_render_feature_grad_async": ([P, P, u32, u32, P, u32, P, i32], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -857,6 +860,36 @@ class Scene:
         """Enqueue one feature frame on ctx.stream; outputs are device pointers (0 = keep in the ctx buffers:
         Context.framebuffer_ptr, Context.features_ptr())."""
         _check(lib.gsrt_render_features_async(self.handle, _p(ubo), mode, k, d_rgba or None, d_feat or None), self.ctx)
+
+    def feature_grad(self, ubo, grad_image, mode=MODE_COR, k=0):
+        """The backward of a feature frame to the feature table (gsrt_render_feature_grad): grad_image is the upstream
+        gradient of the feature image, (H, W, C) or (H, W) float32 with 1 <= C <= MAX_FEATURES; returns the (n, C)
+        gradient table, grad[g, c] = sum of w * G[p, c] / ns over the hits of Gaussian g the frame blends. The sum's
+        order is unspecified (float atomics): the last bits can differ from run to run. No feature table is needed."""
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        g = np.asarray(grad_image, np.float32)
+        if g.ndim == 2:
+            g = g[:, :, None]
+        if g.ndim != 3 or g.shape[:2] != (H, W) or not 1 <= g.shape[2] <= MAX_FEATURES:
+            raise GsrtError(E_ARG, "feature_grad: an (H, W, channels) or (H, W) array, 1 <= channels <= MAX_FEATURES")
+        g = np.ascontiguousarray(g)
+        out = np.zeros((self.n, g.shape[2]), np.float32)
+        _check(lib.gsrt_render_feature_grad(self.handle, _p(ubo), mode, k, _p(g), g.shape[2], _p(out), 0), self.ctx)
+        return out
+
+    def feature_grad_async(self, ubo, d_grad_image: int, channels: int, d_grad_table: int, accumulate=False,
+                           mode=MODE_COR, k=0):
+        """Enqueue one gradient frame on ctx.stream: d_grad_image (W*H*channels floats) and d_grad_table (n*channels
+        floats, ordinary device memory) are device addresses; accumulate adds to the table instead of writing it."""
+        _check(lib.gsrt_render_feature_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
+                                                  channels, ctypes.c_void_p(d_grad_table or None),
+                                                  1 if accumulate else 0), self.ctx)
+
+    def contributions(self, ubo, mode=MODE_COR, k=0):
+        """Each Gaussian's contribution to the view, (n,): its blend weight summed over the frame's pixels (the mean
+        over a pixel's samples), i.e. feature_grad of an image of ones with one channel."""
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        return self.feature_grad(ubo, np.ones((H, W), np.float32), mode, k)[:, 0]
 
     def render_sharded(self, ubo, mode=MODE_COR, k=0, want_image=True):
         W, H = int(ubo["width"][0]), int(ubo["height"][0])

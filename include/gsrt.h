@@ -75,9 +75,11 @@ enum {
                                    (gsrt_dump8_*), 4 bytes per pixel instead of RGBA32F's 16 */
     GSRT_FLAG_DEPTH = 0x800, /* whole COR frames: also write the expected view depth per pixel (gsrt_render_depth below);
                                GSRT_E_ARG with REF, GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8 or a sharded entry point */
-    GSRT_FLAG_FEATURES = 0x1000 /* whole COR frames: blend the scene's feature table instead of colour
+    GSRT_FLAG_FEATURES = 0x1000, /* whole COR frames: blend the scene's feature table instead of colour
                                    (gsrt_render_features below); GSRT_E_ARG with REF, GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8,
                                    GSRT_FLAG_DEPTH or a sharded entry point; GSRT_E_STATE without a feature table */
+    GSRT_FLAG_FEATURE_GRAD = 0x2000 /* whole COR frames: the backward of a feature frame to the feature table; set by
+                                       gsrt_render_feature_grad (below) itself, GSRT_E_ARG through every other entry point */
 };
 /* synthetic cloud kinds */
 enum { GSRT_SYNTH_COR = 0, GSRT_SYNTH_REF = 1, GSRT_SYNTH_NEEDLE = 2 };
@@ -286,6 +288,37 @@ gsrt_status gsrt_render_features_async(gsrt_scene* scene, const gsrt_ubo* ubo, u
 /* device pointer of the last frame's feature image (W*H*C floats), or NULL when the last frame had none (after a feature
  * frame gsrt_depth_buffer reads NULL, after a depth frame this does) */
 const float* gsrt_feature_buffer(gsrt_ctx* ctx);
+/* Gradient frame (GSRT_FLAG_FEATURE_GRAD): the exact backward of a feature frame with respect to the feature table,
+ * which the frame is linear in. grad_image is the upstream gradient G of a feature image, W*H*channels floats laid out as
+ * that image is (row-major, pixel-interleaved); grad_table receives n*channels floats laid out [gauss][channel]:
+ *     grad_table[g][c] = sum over pixels p, samples s of p, hits i of ray (p, s) with id g of   w_i * (G[p][c] / ns)
+ * with ns the samples per pixel and the hits, their order, alpha and the stop exactly those of the feature frame's blend.
+ * Each term is the float32 product of the blend's own float32 weight w_i and G[p][c] / ns (G * (1/ns) when ns is a power
+ * of two, G / ns otherwise, rounded once). The terms are summed on the device with float atomic adds, so the order of the
+ * sum is unspecified and results can differ in their last bits from run to run. A non-finite G[p][c] reaches only the
+ * Gaussians pixel p blends. No feature table is needed or read; 1 <= channels <= GSRT_MAX_FEATURES.
+ * accumulate == 0: the table is written, Gaussians no ray blends get +0. accumulate != 0: this frame's gradient is added
+ * to what the table holds (batches of views); that form takes a device grad_table only, a host one is GSRT_E_ARG.
+ * grad_image / grad_table are host or device pointers. A device table must be ordinary device memory (hipMalloc, a torch
+ * tensor); host tables go through a buffer of the ctx.
+ * With channels == 1 and G == 1 everywhere the result is each Gaussian's blend weight summed over the frame's pixels
+ * (the mean over a pixel's samples): its contribution to the view, the importance score used for pruning.
+ * The frame's RGBA (gsrt_framebuffer) is the feature frame's (r = g = b = sum w, a = 1 - T). Like depth and feature frames
+ * it takes the in-order path on gsrt_stream(): gsrt_slot_streams reads 0 after it, gsrt_depth_buffer and
+ * gsrt_feature_buffer read NULL; gsrt_timing records the frame like any other.
+ * GSRT_E_ARG (gsrt_last_error names GSRT_FLAG_FEATURE_GRAD, and the context renders as before): REF mode; GSRT_FLAG_STATS,
+ * GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH or GSRT_FLAG_FEATURES with it; sharded entry points; a scene with a mesh; channels
+ * out of range; a NULL grad_image or grad_table; the flag passed to gsrt_render / gsrt_render_async (or the depth and
+ * feature forms), which have nowhere to take the image.
+ * Not provided: gradients with respect to geometry, opacity, SH or the normaliser (sum w); sharded frames; more than
+ * GSRT_MAX_FEATURES channels.
+ * gsrt_render_feature_grad blocks until the table is complete, like gsrt_render. */
+gsrt_status gsrt_render_feature_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                     const float* grad_image, uint32_t channels, float* grad_table, int accumulate);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_render_feature_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                           const float* d_grad_image, uint32_t channels, float* d_grad_table,
+                                           int accumulate);
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into
