@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "gsrt_internal.hpp"
@@ -773,7 +774,6 @@ static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mo
     const size_t px = (size_t)ubo->width * ubo->height;
     gsrt_status s = grow(ctx, &ctx->d_fb, &ctx->fb_pixels, px * 4);
     if (s != GSRT_OK) return s;
-    ctx->fb_pixels = ctx->fb_pixels;  // counted in floats
     if (mode & GSRT_FLAG_STATS) {
         s = grow(ctx, &ctx->d_ray_stats, &ctx->ray_stats_pixels, px * 4);
         if (s != GSRT_OK) return s;
@@ -802,12 +802,20 @@ struct GradFrame {
     uint32_t channels;
 };
 
-// one frame on the render stream; d_depth (a GSRT_FLAG_DEPTH frame's copy of ctx->d_depth) and d_feat (a
-// GSRT_FLAG_FEATURES frame's copy of ctx->d_feat) may be nullptr; gf: a GSRT_FLAG_FEATURE_GRAD frame's buffers, else nullptr
-static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
-                                gsrt_raystate* d_rs, float* d_depth, float* d_feat = nullptr,
-                                const GradFrame* gf = nullptr) {
-    gsrt_status s = check_render_args(sc, ubo, mode, gf != nullptr);
+// a frame's device outputs: a caller fills the ones its frame has, the others stay nullptr
+struct FrameOut {
+    float* rgba = nullptr;            // a copy of the frame (the context's framebuffer holds it either way)
+    gsrt_raystate* rs = nullptr;      // the per-ray states
+    float* depth = nullptr;           // a GSRT_FLAG_DEPTH frame: a copy of ctx->d_depth
+    float* feat = nullptr;            // a GSRT_FLAG_FEATURES frame: a copy of ctx->d_feat
+    const GradFrame* grad = nullptr;  // a GSRT_FLAG_FEATURE_GRAD frame's buffers
+};
+
+// one frame on the render stream
+static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const FrameOut& out) {
+    float* const d_rgba = out.rgba;
+    gsrt_raystate* const d_rs = out.rs;
+    gsrt_status s = check_render_args(sc, ubo, mode, out.grad != nullptr);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
@@ -861,9 +869,9 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
         if (depth) rsy.depth = ctx->d_depth;
         if (feat) rsy.feat = ctx->d_feat;
         if (grad) {
-            rsy.grad_in = gf->d_in;
-            rsy.grad_rows = gf->d_rows;
-            rsy.grad_channels = gf->channels;
+            rsy.grad_in = out.grad->d_in;
+            rsy.grad_rows = out.grad->d_rows;
+            rsy.grad_channels = out.grad->channels;
         }
         s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat && !grad ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
@@ -871,11 +879,11 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
         if (d_rgba && d_rgba != ctx->d_fb)
             GSRT_HIP(ctx, hipMemcpyAsync(d_rgba, ctx->d_fb, sizeof(float) * 4 * ubo->width * ubo->height,
                                          hipMemcpyDeviceToDevice, ctx->stream));
-        if (depth && d_depth && d_depth != ctx->d_depth)
-            GSRT_HIP(ctx, hipMemcpyAsync(d_depth, ctx->d_depth, sizeof(float) * ubo->width * ubo->height,
+        if (depth && out.depth && out.depth != ctx->d_depth)
+            GSRT_HIP(ctx, hipMemcpyAsync(out.depth, ctx->d_depth, sizeof(float) * ubo->width * ubo->height,
                                          hipMemcpyDeviceToDevice, ctx->stream));
-        if (feat && d_feat && d_feat != ctx->d_feat)
-            GSRT_HIP(ctx, hipMemcpyAsync(d_feat, ctx->d_feat,
+        if (feat && out.feat && out.feat != ctx->d_feat)
+            GSRT_HIP(ctx, hipMemcpyAsync(out.feat, ctx->d_feat,
                                          sizeof(float) * ubo->width * ubo->height * sc->feat_channels,
                                          hipMemcpyDeviceToDevice, ctx->stream));
     }
@@ -883,14 +891,43 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
     return GSRT_OK;
 }
 
+// a blocking entry point's copy of a device result into the caller's host memory (dst nullptr: none); what: the error
+struct Download {
+    void* dst;
+    const void* src;
+    size_t bytes;
+    const char* what;
+};
+
+// The tail of the blocking entry points, s the status so far: the downloads are queued only while it is GSRT_OK, the
+// render stream is drained either way (then *tmp, the call's temporary device buffer, is freed), the stream's error is
+// reported only if none came earlier, and the sticky error word is checked.
+static gsrt_status finish_blocking(gsrt_ctx* ctx, gsrt_status s, std::initializer_list<Download> downloads,
+                                   void* const* tmp = nullptr) {
+    for (const Download& d : downloads)
+        if (s == GSRT_OK && d.dst && hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, d.what);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
+        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
+    if (tmp) (void)hipFree(*tmp);
+    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
+    return s;
+}
+
 gsrt_status gsrt_render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
                               gsrt_raystate* d_rs) {
-    return render_async(sc, ubo, mode, k, d_rgba, d_rs, nullptr);
+    FrameOut out;
+    out.rgba = d_rgba;
+    out.rs = d_rs;
+    return render_async(sc, ubo, mode, k, out);
 }
 
 gsrt_status gsrt_render_depth_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
                                     float* d_depth) {
-    return render_async(sc, ubo, mode | GSRT_FLAG_DEPTH, k, d_rgba, nullptr, d_depth);
+    FrameOut out;
+    out.rgba = d_rgba;
+    out.depth = d_depth;
+    return render_async(sc, ubo, mode | GSRT_FLAG_DEPTH, k, out);
 }
 
 gsrt_status gsrt_render_depth(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
@@ -902,27 +939,24 @@ gsrt_status gsrt_render_depth(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode
     (void)hipSetDevice(ctx->device);
     const size_t px = (size_t)ubo->width * ubo->height;
     const bool rgba_dev = is_device_ptr(rgba_out), depth_dev = is_device_ptr(depth_out);
-    s = render_async(sc, ubo, mode, k, rgba_dev ? rgba_out : nullptr, nullptr, depth_dev ? depth_out : nullptr);
-    if (s == GSRT_OK && rgba_out && !rgba_dev) {
-        if (hipMemcpyAsync(rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px, hipMemcpyDeviceToHost,
-                           ctx->stream) != hipSuccess)
-            s = fail(ctx, GSRT_E_DEVICE, "framebuffer download failed");
-    }
-    if (s == GSRT_OK && depth_out && !depth_dev) {
-        if (hipMemcpyAsync(depth_out, ctx->d_depth, sizeof(float) * px, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-            s = fail(ctx, GSRT_E_DEVICE, "depth download failed");
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
-        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
-    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
-    return s;
+    FrameOut out;
+    out.rgba = rgba_dev ? rgba_out : nullptr;
+    out.depth = depth_dev ? depth_out : nullptr;
+    s = render_async(sc, ubo, mode, k, out);
+    return finish_blocking(ctx, s, {{rgba_dev ? nullptr : rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px,
+                                     "framebuffer download failed"},
+                                    {depth_dev ? nullptr : depth_out, ctx->d_depth, sizeof(float) * px,
+                                     "depth download failed"}});
 }
 
 const float* gsrt_depth_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_depth ? ctx->d_depth : nullptr; }
 
 gsrt_status gsrt_render_features_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* d_rgba,
                                        float* d_feat) {
-    return render_async(sc, ubo, mode | GSRT_FLAG_FEATURES, k, d_rgba, nullptr, nullptr, d_feat);
+    FrameOut out;
+    out.rgba = d_rgba;
+    out.feat = d_feat;
+    return render_async(sc, ubo, mode | GSRT_FLAG_FEATURES, k, out);
 }
 
 gsrt_status gsrt_render_features(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
@@ -934,21 +968,14 @@ gsrt_status gsrt_render_features(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t m
     (void)hipSetDevice(ctx->device);
     const size_t px = (size_t)ubo->width * ubo->height;
     const bool rgba_dev = is_device_ptr(rgba_out), feat_dev = is_device_ptr(feat_out);
-    s = render_async(sc, ubo, mode, k, rgba_dev ? rgba_out : nullptr, nullptr, nullptr, feat_dev ? feat_out : nullptr);
-    if (s == GSRT_OK && rgba_out && !rgba_dev) {
-        if (hipMemcpyAsync(rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px, hipMemcpyDeviceToHost,
-                           ctx->stream) != hipSuccess)
-            s = fail(ctx, GSRT_E_DEVICE, "framebuffer download failed");
-    }
-    if (s == GSRT_OK && feat_out && !feat_dev) {
-        if (hipMemcpyAsync(feat_out, ctx->d_feat, sizeof(float) * px * sc->feat_channels, hipMemcpyDeviceToHost,
-                           ctx->stream) != hipSuccess)
-            s = fail(ctx, GSRT_E_DEVICE, "feature image download failed");
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
-        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
-    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
-    return s;
+    FrameOut out;
+    out.rgba = rgba_dev ? rgba_out : nullptr;
+    out.feat = feat_dev ? feat_out : nullptr;
+    s = render_async(sc, ubo, mode, k, out);
+    return finish_blocking(ctx, s, {{rgba_dev ? nullptr : rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px,
+                                     "framebuffer download failed"},
+                                    {feat_dev ? nullptr : feat_out, ctx->d_feat, sizeof(float) * px * sc->feat_channels,
+                                     "feature image download failed"}});
 }
 
 const float* gsrt_feature_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_feat ? ctx->d_feat : nullptr; }
@@ -981,7 +1008,9 @@ gsrt_status gsrt_render_feature_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, 
     }
     GSRT_HIP(ctx, hipMemsetAsync(ctx->d_grad_rows, 0, sizeof(float) * rows, ctx->stream));
     const GradFrame gf{d_grad_image, ctx->d_grad_rows, channels};
-    s = render_async(sc, ubo, mode, k, nullptr, nullptr, nullptr, nullptr, &gf);
+    FrameOut out;
+    out.grad = &gf;
+    s = render_async(sc, ubo, mode, k, out);
     if (s != GSRT_OK) return s;
     gsrt::launch_grad_compact(ctx->stream, d_grad_table, ctx->d_grad_rows, sc->n, channels, accumulate != 0);
     GSRT_HIP(ctx, hipGetLastError());
@@ -1011,15 +1040,8 @@ gsrt_status gsrt_render_feature_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
         GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
     s = gsrt_render_feature_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in, channels,
                                        out_dev ? grad_table : ctx->d_grad_out, accumulate);
-    if (s == GSRT_OK && !out_dev && out_floats) {
-        if (hipMemcpyAsync(grad_table, ctx->d_grad_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, ctx->stream) !=
-            hipSuccess)
-            s = fail(ctx, GSRT_E_DEVICE, "gradient table download failed");
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
-        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
-    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
-    return s;
+    return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
+                                     sizeof(float) * out_floats, "gradient table download failed"}});
 }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,
@@ -1033,20 +1055,11 @@ gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint
     gsrt_raystate* d_rs = nullptr;
     if (rs_out && !rs_dev) GSRT_HIP(ctx, hipMalloc(&d_rs, sizeof(gsrt_raystate) * px));
     s = gsrt_render_async(sc, ubo, mode, k, rgba_dev ? rgba_out : nullptr, rs_out ? (rs_dev ? rs_out : d_rs) : nullptr);
-    if (s == GSRT_OK && rgba_out && !rgba_dev) {
-        if (hipMemcpyAsync(rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px, hipMemcpyDeviceToHost,
-                           ctx->stream) != hipSuccess)
-            s = fail(ctx, GSRT_E_DEVICE, "framebuffer download failed");
-    }
-    if (s == GSRT_OK && d_rs) {
-        if (hipMemcpyAsync(rs_out, d_rs, sizeof(gsrt_raystate) * px, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-            s = fail(ctx, GSRT_E_DEVICE, "raystate download failed");
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == GSRT_OK)
-        s = fail(ctx, GSRT_E_DEVICE, std::string("render: ") + hipGetErrorString(hipGetLastError()));
-    (void)hipFree(d_rs);
-    if (s == GSRT_OK) s = gsrt::check_error_word(ctx);
-    return s;
+    void* const tmp = d_rs;  // freed on every path
+    return finish_blocking(ctx, s, {{rgba_dev ? nullptr : rgba_out, gsrt::framebuffer_of(ctx), sizeof(float) * 4 * px,
+                                     "framebuffer download failed"},
+                                    {d_rs ? rs_out : nullptr, d_rs, sizeof(gsrt_raystate) * px, "raystate download failed"}},
+                           &tmp);
 }
 
 gsrt_status gsrt_timing(gsrt_ctx* ctx, uint32_t frames) {

@@ -271,6 +271,12 @@ __device__ GSRT_INLINE void sh_basis(const float d[3], float bs[16]) {
 // The mapping is a bijection whatever the dispatcher does; placement only changes the cache hit rate.
 constexpr uint32_t kSuper = 16;
 constexpr uint32_t kRun = kSuper * kSuper;
+constexpr uint32_t kXcds = 8;          // workgroup i of a launch runs on XCD i % kXcds (round-robin dispatch)
+constexpr uint32_t kDeal = kRun / 4;   // a rank share's render unit: a quarter run (xcd_local_tile_perm)
+// COR candidate lists (gsrt_render.hip), which the frame plan and the dispatch orders (gsrt_plan.cpp) size by as well
+constexpr uint32_t kCap = 256;     // tile nearest-candidate buffer (keys are double-buffered: 2*kCap)
+constexpr uint32_t kFG = 4;        // default tile group (kFG x kFG tiles) sharing one sorted candidate list
+constexpr uint32_t kSG = 4;        // super-group: kSG x kSG groups sharing one traversal frontier
 
 __host__ __device__ GSRT_INLINE void spatial_tile(uint32_t k, uint32_t tiles_x, uint32_t tiles_y, uint32_t& tx,
                                              uint32_t& ty) {

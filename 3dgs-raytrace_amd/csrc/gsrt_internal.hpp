@@ -174,7 +174,7 @@ struct gsrt_ctx {
     float* d_tri_t = nullptr;                  // REF frames of a scene with a mesh: closest triangle t per pixel
     size_t tri_t_pixels = 0;
     uint32_t* d_group_order = nullptr;         // COR k_group_list dispatch order (centre-out), per frame geometry
-    uint32_t group_order_key[5] = {};          // {groups_x, groups, mode, rank, nranks} it was built for
+    uint32_t group_order_key[5] = {};          // {groups_x, groups, row0, row1, nranks} it was built for
     uint32_t group_own = 0;                    // groups at the head of d_group_order with a tile of the rank's band
     uint32_t* d_run_order = nullptr;           // k_render_cor: centre-out order of its runs of local tiles
     uint32_t run_order_key[5] = {0, 0, 0, 0, 0};  // {local tiles, row0, row1, tiles_x, tiles_y} it was built for
@@ -301,7 +301,7 @@ gsrt_status lbvh_fit_if_stale(gsrt_scene* sc, uint32_t slot, hipStream_t st, boo
 // ---- meshes (gsrt_mesh_trace.hip): the closest triangle hit t per pixel of a REF frame (kTMax: none) into tri_t
 void launch_mesh_thit(hipStream_t s, const gsrt_ubo& ubo, const gsrt_scene* sc, float* tri_t);
 
-// ---- render (gsrt_render.hip) ----
+// ---- frame plan and dispatch orders (gsrt_plan.cpp: host arithmetic, no HIP calls), render (gsrt_render.hip) ----
 struct RenderPlan {
     uint32_t mode = GSRT_MODE_COR;  // GSRT_MODE_* | flags
     uint32_t cap = 512;             // tile nearest-hit buffer capacity
@@ -329,6 +329,18 @@ float root_weight(uint32_t nranks, uint32_t spp, uint32_t mode);
 void balance_bands(uint32_t tiles_y, uint32_t nranks, const uint32_t* row_cost, float root_w, uint32_t* out);
 // the heaviest band's cost over its weight (the balance objective)
 double band_peak(uint32_t nranks, const uint32_t* bands, const uint32_t* row_cost, float root_w);
+// k_group_list's dispatch order over a grid of groups_x x groups_y groups of fg x fg tiles: ord = every group, those with
+// a tile row of the band [row0, row1) first (all of them with one rank; their count is returned), centre-out by
+// super-group and interleaved over the XCDs
+uint32_t group_order(uint32_t groups_x, uint32_t groups_y, uint32_t fg, uint32_t row0, uint32_t row1, uint32_t nranks,
+                     std::vector<uint32_t>& ord);
+// k_render_cor's dispatch order of a rank share: perm = its R units (kDeal local tiles each) of the band centre-out;
+// unit_costs sums a whole frame's tile costs (its own local order) per unit, deal_units turns those costs and the
+// centre-out order into the deal over the XCDs (R a multiple of kXcds)
+void unit_order_centre(uint32_t R, uint32_t row0, uint32_t row1, uint32_t tiles_x, uint32_t* perm);
+void unit_costs(const uint32_t* tile_cost, uint32_t R, uint32_t row0, uint32_t row1, uint32_t tiles_x, uint32_t tiles_y,
+                double* cost);
+void deal_units(const double* cost, const uint32_t* centre, uint32_t R, uint32_t* perm);
 // how a frame's render kernel is ordered against its output buffer's other users (launch_render)
 struct RenderSync {
     bool slot = false;          // slot streams for this frame (use_slot_streams), with a private d_rgba

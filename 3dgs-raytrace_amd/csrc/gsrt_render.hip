@@ -36,12 +36,11 @@
 namespace gsrt {
 
 constexpr uint32_t kStack = 512;   // LDS node stack of the 64-wide traversal (entries)
-constexpr uint32_t kCap = 256;     // tile nearest-candidate buffer (keys are double-buffered: 2*kCap)
-constexpr uint32_t kGroup = 4;     // candidates per LDS stage
+// (kCap, kFG and kSG: gsrt_device.hpp, since the frame plan and the dispatch orders of gsrt_plan.cpp use them too)
+constexpr uint32_t kGroup = 4;    // candidates per LDS stage
 constexpr uint32_t kRCap = 128;    // k_render_cor's own traversal rounds (rare: past a group list's end)
 constexpr uint32_t kRBuf = 2 * kRCap;
 constexpr uint32_t kRStack = 256;
-constexpr uint32_t kFG = 4;        // default tile group (kFG x kFG tiles) sharing one sorted candidate list
 constexpr uint32_t kGCap = 896;    // candidates per group-list segment
 #ifndef GSRT_GROUP_SEGMENTS
 #define GSRT_GROUP_SEGMENTS 2
@@ -65,7 +64,6 @@ constexpr bool kGroupRegSort = GSRT_GROUP_REGSORT != 0;
 #ifndef GSRT_GRAD_AB
 #define GSRT_GRAD_AB 0
 #endif
-constexpr uint32_t kSG = 4;        // super-group: kSG x kSG groups sharing one traversal frontier
 constexpr uint32_t kFront = 128;   // frontier entries per super-group
 
 
@@ -160,8 +158,8 @@ __device__ GSRT_INLINE const KArgs& kargs() {
     return *(const KArgs*)p;
 }
 
-// ---- tile order: spatial_tile / spatial_index / owner_of live in gsrt_device.hpp (the projection uses them too)
-constexpr uint32_t kXcds = 8;
+// ---- tile order: spatial_tile / spatial_index / owner_of, kXcds and kDeal live in gsrt_device.hpp (the projection and
+// the host's dispatch orders use them too)
 
 // Workgroup b of a launch over nl local tiles -> local tile index. Under round-robin dispatch the
 // workgroups of XCD x are b = x, x+8, ...; they are given whole runs of kRun consecutive tiles of the
@@ -178,7 +176,6 @@ __host__ __device__ GSRT_INLINE uint32_t xcd_local_tile(uint32_t b, uint32_t nl)
 // the order perm lists (centre-out: the costly units first, so the launch ends on short tiles); perm == nullptr:
 // spatial order. A rank of a sharded frame has few runs (63 at 8 ranks, C3): dealt whole, the XCDs' shares
 // differed by 25 % in cost; quarter runs balance them better and stay spatially coherent.
-constexpr uint32_t kDeal = kRun / 4;
 __device__ GSRT_INLINE uint32_t xcd_local_tile_perm(uint32_t b, uint32_t nl, const uint32_t* perm) {
     const uint32_t round_len = kXcds * kDeal;
     if (!perm || b >= (nl / round_len) * round_len) return xcd_local_tile(b, nl);
@@ -2250,106 +2247,6 @@ uint32_t max_local_tiles(const RenderPlan& p) {  // the packed stride of the gat
     return m;
 }
 
-// Rank 0 also lands the other N-1 blocks and unpacks the whole frame, a cost that grows with the framebuffer bytes
-// (N - 1 blocks in, every pixel out) against a share's shading work (~ rays / N). Measured with the loopback stand-in
-// (profiles/r04/): the 8-rank root's extra time is 0.2 of a share at C3 (4 spp) and 0.7 at C4 (1 spp), i.e. about
-// 0.09 (N - 1) / spp of the root's frame; so rank 0 takes w0 = 1 - 0.09 (N - 1) / spp of a share (>= 1/4). A pure
-// function of N and spp: every rank computes the same weight (no per-rank input reaches the partition).
-float root_weight(uint32_t nranks, uint32_t spp, uint32_t mode) {
-    if (nranks <= 1) return 1.0f;
-    // the receive + unpack cost, in shares per (N - 1) / spp: measured for each exchange format (RGBA32F 16 B per
-    // pixel, dump codes 4 B: not a quarter of it, since the root's receive and unpack are not bound by bytes alone;
-    // the 8-rank C3 and C4 roots put it at 0.067-0.073)
-    const float per_px = (mode & GSRT_FLAG_OUT_DUMP8) ? 0.07f : 0.09f;
-    const float w0 = 1.0f - per_px * (float)(nranks - 1) / (float)(spp ? spp : 1);
-    return w0 < 0.25f ? 0.25f : (w0 > 1.0f ? 1.0f : w0);
-}
-
-static void row_prefix(uint32_t tiles_y, const uint32_t* row_cost, std::vector<uint64_t>& P) {
-    P.assign(tiles_y + 1, 0);
-    for (uint32_t i = 0; i < tiles_y; ++i) P[i + 1] = P[i] + (row_cost ? (uint64_t)row_cost[i] : 1u);
-}
-
-void balance_bands(uint32_t tiles_y, uint32_t nranks, const uint32_t* row_cost, float root_w, uint32_t* out) {
-    const uint32_t N = nranks ? nranks : 1;
-    std::vector<uint64_t> P;
-    row_prefix(tiles_y, row_cost, P);
-    const double wtot = (double)root_w + (double)(N - 1);
-    const uint32_t minrow = tiles_y >= N ? 1u : 0u;  // every band non-empty when there are enough rows
-    out[0] = 0;
-    out[N] = tiles_y;
-    double wsum = 0.0;
-    for (uint32_t r = 1; r < N; ++r) {
-        wsum += r == 1 ? (double)root_w : 1.0;
-        // the cumulative target of bands 0..r-1, met by the nearest row boundary the remaining bands leave room for
-        const double target = (double)P[tiles_y] * wsum / wtot;
-        const uint32_t lo = out[r - 1] + minrow, hi = tiles_y - (N - r) * minrow;
-        uint32_t i = (uint32_t)(std::lower_bound(P.begin() + lo, P.begin() + hi + 1, (uint64_t)std::ceil(target)) - P.begin());
-        if (i > hi) i = hi;
-        if (i > lo && (double)P[i] - target > target - (double)P[i - 1]) --i;
-        out[r] = i;
-    }
-}
-
-double band_peak(uint32_t nranks, const uint32_t* bands, const uint32_t* row_cost, float root_w) {
-    std::vector<uint64_t> P;
-    row_prefix(bands[nranks], row_cost, P);
-    double peak = 0.0;
-    for (uint32_t r = 0; r < nranks; ++r) {
-        const double c = (double)(P[bands[r + 1]] - P[bands[r]]) / (r == 0 ? (double)root_w : 1.0);
-        peak = c > peak ? c : peak;
-    }
-    return peak;
-}
-
-RenderPlan make_plan(const gsrt_ubo& ubo, uint32_t mode, uint32_t k, uint32_t rank, uint32_t nranks,
-                     const uint32_t* bands) {
-    RenderPlan p;
-    p.mode = mode;
-    p.cap = kCap;
-    (void)k;
-    p.nranks = nranks ? (nranks < kMaxRanks ? nranks : kMaxRanks) : 1;
-    p.rank = rank < p.nranks ? rank : 0;
-    const uint32_t S = ubo.samples ? ubo.samples : 1;
-    if ((mode & 0xffu) == GSRT_MODE_REF) {
-        p.tw = p.th = 8; p.s_lanes = 1; p.passes = 1;
-    } else if (S <= 64 && (S & (S - 1)) == 0) {
-        uint32_t px = 64 / S, lg = 0;
-        while ((1u << lg) < px) ++lg;
-        p.tw = 1u << ((lg + 1) / 2);
-        p.th = 1u << (lg / 2);
-        p.s_lanes = S; p.passes = 1;
-    } else {
-        p.tw = p.th = 8; p.s_lanes = 1; p.passes = S;
-    }
-    p.tiles_x = (ubo.width + p.tw - 1) / p.tw;
-    p.tiles_y = (ubo.height + p.th - 1) / p.th;
-    // the partition: the given bands (a cost-balanced partition, gsrt_comm.cpp), else rows split evenly by weight
-    p.bands.n = p.nranks;
-    if (bands) {
-        for (uint32_t r = 0; r <= p.nranks; ++r) p.bands.row[r] = bands[r];
-    } else {
-        const float w0 = (mode & 0xffu) == GSRT_MODE_COR ? root_weight(p.nranks, S, mode) : 1.0f;
-        balance_bands(p.tiles_y, p.nranks, nullptr, w0, p.bands.row);
-    }
-    // tile groups: 4x4 tiles, or 2x2 when a rank would get fewer than 1500 groups of 4x4. A rank's group lists
-    // are latency chains (traversal, sort, filter) beside the previous frame's render; with few groups there are
-    // too few of them to fill the GPU, and smaller groups shorten each chain. Measured: C3 (8160), C4 (8160) and
-    // C5 (32400) are 6-10 % faster with 4x4; the 8-rank C3 and C4 shares (1020 groups of 4x4) 15-20 % faster
-    // with 2x2; C2 and the 4-rank C3 share (2040) 5-9 % faster with 4x4 since slot streams overlap their frames
-    // (before them C2 was 9 % faster with 2x2; profiles/r02c/ab_group_tiles_slot.txt). The test switch
-    // GSRT_DEBUG_GROUP_TILES=2|4 overrides.
-    {
-        const uint32_t g4 = ((p.tiles_x + kFG - 1) / kFG) * ((p.tiles_y + kFG - 1) / kFG);
-        p.fg = g4 < 1500u * p.nranks ? 2u : kFG;
-    }
-    if (const char* e = std::getenv("GSRT_DEBUG_GROUP_TILES")) {
-        const long v = std::strtol(e, nullptr, 10);
-        if (v == 2 || v == (long)kFG) p.fg = (uint32_t)v;
-    }
-    return p;
-}
-
 // GSRT_DEBUG_NO_FRONTIER=1: groups traverse from the root (A/B measurements, tests)
 static bool debug_no_frontier() {
     const char* e = std::getenv("GSRT_DEBUG_NO_FRONTIER");
@@ -2450,74 +2347,104 @@ bool use_slot_streams(gsrt_ctx* ctx, bool share) {
     return ctx->slot_mode;
 }
 
-// The deal of a rank share's R render units (R a multiple of kXcds) over the XCDs: by cost, longest first (ties in the
-// centre-out order), each unit to the XCD with the least cost so far among those holding fewer than R / kXcds; perm
-// position k kXcds + x holds XCD x's k-th unit (xcd_local_tile_perm), so each XCD starts its longest units first
-void deal_units(const double* cost, const uint32_t* centre, uint32_t R, uint32_t* perm) {
-    std::vector<uint32_t> by(centre, centre + R);
-    std::stable_sort(by.begin(), by.end(), [&](uint32_t a, uint32_t c) { return cost[a] > cost[c]; });
-    double load[kXcds] = {};
-    uint32_t count[kXcds] = {};
-    for (uint32_t q : by) {
-        uint32_t x = kXcds;
-        for (uint32_t j = 0; j < kXcds; ++j)
-            if (count[j] < R / kXcds && (x == kXcds || load[j] < load[x])) x = j;
-        perm[count[x] * kXcds + x] = q;
-        load[x] += cost[q];
-        ++count[x];
-    }
+// ---- launch_render: one frame's launches, as a sequence of phases over what the frame is (FramePath)
+
+// What a frame is: its slot and streams, and which prep path it goes down. Fixed once (frame_path) from the plan, the
+// caller's RenderSync, the context and the scene; the phases below read it and none of them decides again.
+struct FramePath {
+    bool cor, stats;
+    // COR frames rotate over the kSlots frame slots, their prep kernels on the prep stream; REF and the counting pass
+    // run everything on the render stream in slot 0, ordered after all earlier prep work
+    bool pipelined;
+    // slot streams (use_slot_streams, gsrt_internal.hpp): the frame's prep and render kernels on its slot's stream
+    bool slot_streams;
+    uint32_t b, prev;   // the frame's slot, and the slot of the frame before this one
+    hipStream_t ps;     // the stream of the prep kernels
+    bool use_groups;    // k_group_list builds the tile lists (else k_collect_cor per tile)
+    bool frontier;      // the groups traverse from their super-group's frontier (else from the root)
+    bool leaf_fp;       // the projection writes each leaf's footprint box into its node
+    // a rank of a sharded COR frame: its projection keeps only what its band can see, its frontier kernel skips the
+    // super-groups outside the band
+    RankTiles own;
+    // the fused prep head (k_prep_cor: frontier + projection in one launch) for pipelined COR frames; otherwise the
+    // frontier runs on its own stream beside the projection (two short latency chains in parallel), except on slot
+    // streams
+    bool fused;
+    // a rank share projects in sorted-leaf chunks (k_prep_cor, kLeafOrderRanks): the slot's keyed bitmap follows the
+    // order (switching it starts the bitmap over: all ones, every key rewritten once)
+    bool leaf_order;
+    // a pipelined rank share: the slot's in-band bitmap for this camera and band (k_classify, once per AABB version and
+    // key), which its fit and projection read instead of the AABBs of the splats the band cannot see
+    bool band_frame;
+};
+
+// (also takes the frame's slot: fixes the rotation's length for this frame, ctx->nslots)
+static FramePath frame_path(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, const RenderSync* sync) {
+    gsrt_ctx* ctx = sc->ctx;
+    FramePath f{};
+    f.stats = (plan.mode & GSRT_FLAG_STATS) != 0;
+    f.cor = (plan.mode & 0xffu) == GSRT_MODE_COR;
+    f.pipelined = f.cor && !f.stats;
+    f.slot_streams = f.pipelined && sync && sync->slot && sync->private_out;
+    f.prev = ctx->prev_slot;
+    if (f.pipelined) ctx->nslots = choose_slots(f.slot_streams);
+    if (f.pipelined && ctx->next_slot >= ctx->nslots) ctx->next_slot = 0;  // (the rotation shrank: never the last slot)
+    f.b = f.pipelined ? ctx->next_slot : 0u;
+    f.ps = f.pipelined ? (f.slot_streams ? slot_stream(ctx, f.b) : ctx->pstream) : ctx->stream;
+    if (local_tiles(plan) == 0) return f;  // a band without rows launches nothing: no path to choose, no switch read
+    f.use_groups = f.cor && sc->n > 1 && !f.stats && !debug_no_groups();
+    f.frontier = f.use_groups && !debug_no_frontier();
+    f.leaf_fp = f.cor && !f.stats && sc->n >= 2 && !debug_no_leaf_fp();
+    if (f.cor && !f.stats && plan.nranks > 1 && !debug_project_all())
+        f.own = RankTiles{1u, (float)(plan.row0() * plan.th), (float)(plan.row1() * plan.th), (float)ubo.width};
+    f.fused = f.pipelined && f.frontier && sc->n >= 2;
+    f.leaf_order = f.fused && f.own.active && plan.nranks >= kLeafOrderRanks;
+    f.band_frame = f.pipelined && f.own.active && sc->n >= 2;
+    return f;
 }
 
-gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_out,
-                          gsrt_raystate* d_rs, RenderSync* sync) {
-    gsrt_ctx* ctx = sc->ctx;
-    hipStream_t st = ctx->stream;
-    if (sync) sync->stream = st;
-    const bool stats = (plan.mode & GSRT_FLAG_STATS) != 0;
-    const bool cor = (plan.mode & 0xffu) == GSRT_MODE_COR;
-    // COR frames rotate over the kSlots frame slots, their prep kernels on the prep stream; REF and the
-    // counting pass run everything on the render stream in slot 0, ordered after all earlier prep work
-    const bool pipelined = cor && !stats;
-    // slot streams (use_slot_streams, gsrt_internal.hpp): the frame's prep and render kernels on its slot's stream
-    const bool slot_streams = pipelined && sync && sync->slot && sync->private_out;
-    const uint32_t prev = ctx->prev_slot;  // the slot of the frame before this one
-    if (pipelined) ctx->nslots = choose_slots(slot_streams);
-    if (pipelined && ctx->next_slot >= ctx->nslots) ctx->next_slot = 0;  // (the rotation shrank: never the last slot)
-    const uint32_t b = pipelined ? ctx->next_slot : 0u;
-    FrameSlot& S = ctx->slot[b];
-    hipStream_t ps = pipelined ? (slot_streams ? slot_stream(ctx, b) : ctx->pstream) : st;
-    if (slot_streams && b > 0) {
-        // scene updates go on pstream: a frame on another slot stream follows those queued so far, and the next
-        // update's copies wait for this frame (order_update)
-        if (ctx->side_updates[b]) {
-            GSRT_HIP(ctx, hipEventRecord(ctx->ev_fit, ctx->pstream));
-            GSRT_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_fit, 0));
-            ctx->side_updates[b] = false;
-        }
-        ctx->side_frames[b] = true;
+// scene updates go on pstream: a frame on another slot stream follows those queued so far, and the next update's
+// copies wait for this frame (order_update)
+static gsrt_status follow_updates(gsrt_ctx* ctx, const FramePath& f) {
+    if (!f.slot_streams || f.b == 0) return GSRT_OK;
+    if (ctx->side_updates[f.b]) {
+        GSRT_HIP(ctx, hipEventRecord(ctx->ev_fit, ctx->pstream));
+        GSRT_HIP(ctx, hipStreamWaitEvent(f.ps, ctx->ev_fit, 0));
+        ctx->side_updates[f.b] = false;
     }
-    KArgs k;
+    ctx->side_frames[f.b] = true;
+    return GSRT_OK;
+}
+
+// Everything of the kernels' arguments that the plan, the camera, the caller's RenderSync and the scene decide. The
+// buffers a frame may have to grow first are bound by the ensure_* phases, each its own.
+static void fill_args(KArgs& k, const gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_out,
+                      gsrt_raystate* d_rs, const RenderSync* sync, const FramePath& f) {
+    const gsrt_ctx* ctx = sc->ctx;
     std::memset(&k, 0, sizeof k);
     k.ubo = ubo;
     RenderArgs& A = k.a;
     A.sh = sc->d_sh;
-    A.nodes = sc->d_nodes[b];
+    A.nodes = sc->d_nodes[f.b];
     A.lut = ctx->d_lut;
     A.out = d_out;
     A.rs = d_rs;
-    A.depth_out = cor && !stats && !plan.packed && sync ? sync->depth : nullptr;
-    A.feat_out = cor && !stats && !plan.packed && sync ? sync->feat : nullptr;
+    // the second outputs of a whole COR frame on the in-order path (RenderSync); frames without a RenderSync (those
+    // that write ray states, a one-rank sharded frame without a communicator) carry none, and no sampled render time
+    const bool outputs = f.cor && !f.stats && !plan.packed && sync;
+    A.depth_out = outputs ? sync->depth : nullptr;
+    A.feat_out = outputs ? sync->feat : nullptr;
     A.feat_rows = A.feat_out ? sc->d_feat_rows : nullptr;
     A.feat_channels = A.feat_out ? sc->feat_channels : 0u;
-    const bool grad = cor && !stats && !plan.packed && sync && sync->grad_rows && !A.depth_out && !A.feat_out;
+    const bool grad = outputs && sync->grad_rows && !A.depth_out && !A.feat_out;
     A.grad_in = grad ? sync->grad_in : nullptr;
     A.grad_rows = grad ? sync->grad_rows : nullptr;
     A.grad_channels = grad ? sync->grad_channels : 0u;
-    A.ray_stats = stats ? ctx->d_ray_stats : nullptr;
+    A.ray_stats = f.stats ? ctx->d_ray_stats : nullptr;
     A.counters = ctx->d_counters;
     A.n = sc->n;
     A.root_ref = sc->root_ref;
-    A.root_box = sc->d_root_box[b];
+    A.root_box = sc->d_root_box[f.b];
     A.width = ubo.width; A.height = ubo.height;
     A.tiles_x = plan.tiles_x;
     A.tiles_y = plan.tiles_y;
@@ -2537,31 +2464,38 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
         const long v = std::strtol(e, nullptr, 10);
         if (v >= 8 && v < (long)kStack) A.stack_limit = (uint32_t)v;
     }
-    if (A.ntiles_local == 0) {  // a band without rows (fewer tile rows than ranks): nothing to render
-        timing_mark(ctx, 1);
-        timing_mark(ctx, 2);
-        return GSRT_OK;
-    }
-    if (cor) {
-        A.use_groups = sc->n > 1 && !stats && !debug_no_groups();
-        if (A.use_groups) {
-            A.fg = plan.fg;
-            A.groups_x = (A.tiles_x + A.fg - 1) / A.fg;
-            A.groups = A.groups_x * ((A.tiles_y + A.fg - 1) / A.fg);
-            if (!debug_no_frontier()) {
-                A.sgroups_x = (A.groups_x + kSG - 1) / kSG;
-                A.sgroups = A.sgroups_x * ((A.groups / A.groups_x + kSG - 1) / kSG);
-            }
+    A.use_groups = f.use_groups;
+    if (f.use_groups) {
+        A.fg = plan.fg;
+        A.groups_x = (A.tiles_x + A.fg - 1) / A.fg;
+        A.groups = A.groups_x * ((A.tiles_y + A.fg - 1) / A.fg);
+        if (f.frontier) {
+            A.sgroups_x = (A.groups_x + kSG - 1) / kSG;
+            A.sgroups = A.sgroups_x * ((A.groups / A.groups_x + kSG - 1) / kSG);
         }
-        // (re)allocation of the slots' buffers: only on the first frame of a scene / frame geometry, so simply
-        // drain both streams first. Every slot is sized at once: a lazily grown second slot would drain the
-        // pipeline again on the next frame.
+    }
+    // the counting pass keeps every AABB candidate (|C_r| of SURVEY.md 8d); the prep kernels do not read it
+    A.cull2d = f.cor && !f.stats ? 1u : 0u;
+    A.leaf_fp = f.leaf_fp ? 1u : 0u;
+    A.own = f.own;
+    A.depth_unsafe = sc->d_flags;
+    // the depth cull pays where group lists overflow: groups of many samples per pixel (C5) or 32 pixels wide (C2, C4);
+    // on the smaller groups of C3 and the 8-rank shares its tests cost more than they cull (profiles/r06/depth_cull_ab.txt)
+    A.depth_cull = A.s_lanes >= kMoreLanes || plan.fg * plan.tw >= 32 ? 1u : 0u;
+}
+
+// (Re)allocation of the slots' buffers: only on the first frame of a scene / frame geometry, so simply drain every
+// stream first. Every slot is sized at once: a lazily grown second slot would drain the pipeline again on the next
+// frame. Then the frame's slot is bound.
+static gsrt_status ensure_slot_buffers(gsrt_scene* sc, const FramePath& f, RenderArgs& A) {
+    gsrt_ctx* ctx = sc->ctx;
+    if (f.cor) {
         auto slot_short = [&](uint32_t j) {
             const FrameSlot& Sj = ctx->slot[j];
             return Sj.list_tiles < A.ntiles_local || (A.use_groups && Sj.group_cap < A.groups) ||
                    (A.sgroups && Sj.frontier_cap < A.sgroups) || (sc->n && (!sc->d_recs[j] || !sc->d_footprint[j]));
         };
-        const uint32_t nslots = pipelined ? ctx->nslots : 1u;
+        const uint32_t nslots = f.pipelined ? ctx->nslots : 1u;
         bool any_short = false;
         for (uint32_t j = 0; j < nslots; ++j) any_short = any_short || slot_short(j);
         if (any_short) {
@@ -2596,85 +2530,10 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
                 if (sc->n && !sc->d_footprint[j]) GSRT_HIP(ctx, hipMalloc(&sc->d_footprint[j], kFpWords * sizeof(float4) * sc->n));
             }
         }
+        const FrameSlot& S = ctx->slot[f.b];
         A.lists = S.d_lists;
         A.list_hdr = reinterpret_cast<uint4*>(S.d_list_hdr);
         if (A.use_groups) {
-            // centre-out dispatch order (the groups with the longest lists first, the light border groups last: the
-            // kernel's tail is short groups instead of the heaviest ones started late), whole super-groups (kSG x kSG
-            // groups, one frontier) dealt round-robin over the 8 XCDs (workgroup i runs on XCD i % 8), so an XCD's
-            // consecutive groups share the top of the BVH in its L2. Measured at r03 (profiles/archive/r03/
-            // pmc_gorder.txt): k_group_list's C3 FETCH_SIZE 246 -> 139 MB per launch against single groups centre-out.
-            if (ctx->group_order_key[0] != A.groups_x || ctx->group_order_key[1] != A.groups ||
-                ctx->group_order_key[2] != A.row0 || ctx->group_order_key[3] != A.row1 ||
-                ctx->group_order_key[4] != A.nranks) {
-                gsrt_status s = sync_all(ctx);
-                if (s != GSRT_OK) return s;
-                const uint32_t gy_n = A.groups / A.groups_x;
-                // a rank of a sharded frame orders (and deals) only the groups with a tile row of its band (group_own
-                // of them); the others go last and are not launched
-                std::vector<uint8_t> own_g(A.groups);
-                for (uint32_t g = 0; g < A.groups; ++g) {
-                    const uint32_t gy = g / A.groups_x;
-                    own_g[g] = (A.nranks <= 1 || (gy * A.fg < A.row1 && (gy + 1) * A.fg > A.row0)) ? 1 : 0;
-                }
-                std::vector<uint32_t> ord;
-                ord.reserve(A.groups);
-                auto centre_d2 = [](float x, float y, float w, float h) {
-                    const float dx = x - 0.5f * w, dy = y - 0.5f * h;
-                    return dx * dx + dy * dy;
-                };
-                constexpr uint32_t kXcds = 8;
-                const uint32_t sx_n = (A.groups_x + kSG - 1) / kSG, sy_n = (gy_n + kSG - 1) / kSG;
-                std::vector<uint32_t> sgs(sx_n * sy_n);
-                std::vector<float> d2(sgs.size());
-                for (uint32_t k = 0; k < sgs.size(); ++k) {
-                    sgs[k] = k;
-                    const float cx = std::min((float)((k % sx_n) * kSG) + 0.5f * kSG, (float)A.groups_x);
-                    const float cy = std::min((float)((k / sx_n) * kSG) + 0.5f * kSG, (float)gy_n);
-                    d2[k] = centre_d2(cx, cy, (float)A.groups_x, (float)gy_n);
-                }
-                std::stable_sort(sgs.begin(), sgs.end(), [&](uint32_t a, uint32_t c) { return d2[a] < d2[c]; });
-                // super-groups with a group of this rank's, dealt round-robin over the XCDs
-                std::vector<std::vector<uint32_t>> xl(kXcds);
-                uint32_t dealt = 0, total = 0;
-                for (uint32_t j = 0; j < sgs.size(); ++j) {
-                    const uint32_t sx = sgs[j] % sx_n, sy = sgs[j] / sx_n;
-                    std::vector<uint32_t>& l = xl[dealt % kXcds];
-                    const size_t before = l.size();
-                    for (uint32_t gy = sy * kSG; gy < std::min((sy + 1) * kSG, gy_n); ++gy)
-                        for (uint32_t gx = sx * kSG; gx < std::min((sx + 1) * kSG, A.groups_x); ++gx)
-                            if (own_g[gy * A.groups_x + gx]) l.push_back(gy * A.groups_x + gx);
-                    if (l.size() > before) {
-                        total += (uint32_t)(l.size() - before);
-                        ++dealt;
-                    }
-                }
-                // workgroup i takes the next group of XCD i % 8's list (or of the longest list left)
-                std::vector<size_t> pos(kXcds, 0);
-                for (uint32_t i = 0; i < total; ++i) {
-                    uint32_t x = i % kXcds;
-                    if (pos[x] == xl[x].size()) {
-                        size_t best = 0;
-                        for (uint32_t y = 0; y < kXcds; ++y)
-                            if (xl[y].size() - pos[y] > best) { best = xl[y].size() - pos[y]; x = y; }
-                    }
-                    ord.push_back(xl[x][pos[x]++]);
-                }
-                ctx->group_own = total;
-                for (uint32_t g = 0; g < A.groups; ++g)
-                    if (!own_g[g]) ord.push_back(g);
-                (void)hipFree(ctx->d_group_order);
-                ctx->d_group_order = nullptr;
-                ctx->group_order_key[0] = ctx->group_order_key[1] = 0;
-                GSRT_HIP(ctx, hipMalloc(&ctx->d_group_order, sizeof(uint32_t) * A.groups));
-                GSRT_HIP(ctx, hipMemcpy(ctx->d_group_order, ord.data(), sizeof(uint32_t) * A.groups, hipMemcpyHostToDevice));
-                ctx->group_order_key[0] = A.groups_x;
-                ctx->group_order_key[1] = A.groups;
-                ctx->group_order_key[2] = A.row0;
-                ctx->group_order_key[3] = A.row1;
-                ctx->group_order_key[4] = A.nranks;
-            }
-            A.group_order = ctx->d_group_order;
             A.glist = reinterpret_cast<uint64_t*>(S.d_glist);
             A.ghdr = reinterpret_cast<uint4*>(S.d_ghdr);
             if (A.sgroups) A.frontier = S.d_frontier;
@@ -2682,65 +2541,72 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     } else if (sc->n && !sc->d_recs[0]) {
         GSRT_HIP(ctx, hipMalloc(&sc->d_recs[0], sizeof(SplatRec) * sc->n));
     }
-    A.recs = sc->d_recs[b];
-    A.footprint = cor ? sc->d_footprint[b] : nullptr;
-    A.depth_unsafe = sc->d_flags;
-    // the depth cull pays where group lists overflow: groups of many samples per pixel (C5) or 32 pixels wide (C2, C4);
-    // on the smaller groups of C3 and the 8-rank shares its tests cost more than they cull (profiles/r06/depth_cull_ab.txt)
-    A.depth_cull = A.s_lanes >= kMoreLanes || plan.fg * plan.tw >= 32 ? 1u : 0u;
-    // k_render_cor dispatch order of a rank of a sharded frame: the units of kDeal local tiles of the complete XCD
-    // rounds centre-out (centred on the band's middle row: the central runs cost the most; started first, the launch
-    // ends on the light border runs): 8-rank C3 share 0.308 -> 0.292 ms (r03, round-robin deal). When the context has
-    // rendered a whole COR frame of this tile grid, its measured tile costs order the units instead: longest first,
-    // each to the least-loaded XCD (8-rank C3 shares 0.3-6 % faster, C4 even: profiles/r06/deal_ab.txt; test switch
-    // GSRT_DEBUG_DEAL=0 keeps centre-out). One device keeps the spatial order (C3 -2 %, C2 -2 %, C4 +1.5 % with it).
-    if (cor && plan.nranks > 1) {
-        const uint32_t nl = A.ntiles_local, R = (nl / (kXcds * kDeal)) * kXcds;
-        const uint32_t key[5] = {nl, plan.row0(), plan.row1(), plan.tiles_x, plan.tiles_y};
-        if (R > 1 && std::memcmp(key, ctx->run_order_key, sizeof key) != 0) {
-            gsrt_status s = sync_all(ctx);
-            if (s != GSRT_OK) return s;
-            std::vector<uint32_t> perm(R);
-            std::vector<float> d2(R);
-            const float cy = 0.5f * (float)(plan.row0() + plan.row1());
-            for (uint32_t q = 0; q < R; ++q) {
-                uint32_t tx, ty;
-                band_tile(q * kDeal + kDeal / 2, plan.row0(), plan.row1(), plan.tiles_x, tx, ty);
-                const float dx = ((float)tx + 0.5f) - 0.5f * (float)plan.tiles_x, dy = ((float)ty + 0.5f) - cy;
-                d2[q] = dx * dx + dy * dy;
-                perm[q] = q;
-            }
-            std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t c) { return d2[a] < d2[c]; });
-            const char* de = std::getenv("GSRT_DEBUG_DEAL");
-            if (!(de && de[0] == '0') && ctx->tile_cost_tx == plan.tiles_x && ctx->tile_cost_ty == plan.tiles_y) {
-                // a whole frame's measured tile costs (its last one on this context): the units longest first, each to
-                // the XCD with the least cost so far among those not yet full (every XCD takes R / 8 units)
-                std::vector<uint32_t> t((size_t)plan.tiles_x * plan.tiles_y);
-                GSRT_HIP(ctx, hipMemcpy(t.data(), ctx->d_tile_cost[ctx->tile_cost_slot], sizeof(uint32_t) * t.size(),
-                                        hipMemcpyDeviceToHost));
-                std::vector<double> uc(R, 0.0);
-                for (uint32_t q = 0; q < R; ++q)
-                    for (uint32_t i = 0; i < kDeal; ++i) {
-                        uint32_t tx, ty;
-                        band_tile(q * kDeal + i, plan.row0(), plan.row1(), plan.tiles_x, tx, ty);
-                        uc[q] += t[band_index(tx, ty, 0, plan.tiles_y, plan.tiles_x)];
-                    }
-                const std::vector<uint32_t> centre(perm);
-                deal_units(uc.data(), centre.data(), R, perm.data());
-            }
-            (void)hipFree(ctx->d_run_order);
-            ctx->d_run_order = nullptr;
-            std::memset(ctx->run_order_key, 0, sizeof ctx->run_order_key);
-            GSRT_HIP(ctx, hipMalloc(&ctx->d_run_order, sizeof(uint32_t) * R));
-            GSRT_HIP(ctx, hipMemcpy(ctx->d_run_order, perm.data(), sizeof(uint32_t) * R, hipMemcpyHostToDevice));
-            std::memcpy(ctx->run_order_key, key, sizeof key);
-        }
-        if (R > 1) A.run_order = ctx->d_run_order;
-    }
+    A.recs = sc->d_recs[f.b];
+    A.footprint = f.cor ? sc->d_footprint[f.b] : nullptr;
+    return GSRT_OK;
+}
 
-    // ordering of the prep stage: after every scene change queued on the render stream (update, refit,
-    // build), and after the render that last read this slot (frame f-2); not after the render of frame f-1
-    if (pipelined) {
+// k_group_list's dispatch order (group_order, gsrt_plan.cpp), rebuilt when the group grid or the rank's band changes
+static gsrt_status ensure_group_order(gsrt_ctx* ctx, RenderArgs& A) {
+    const uint32_t key[5] = {A.groups_x, A.groups, A.row0, A.row1, A.nranks};
+    if (std::memcmp(key, ctx->group_order_key, sizeof key) != 0) {
+        gsrt_status s = sync_all(ctx);
+        if (s != GSRT_OK) return s;
+        std::vector<uint32_t> ord;
+        ctx->group_own = group_order(A.groups_x, A.groups / A.groups_x, A.fg, A.row0, A.row1, A.nranks, ord);
+        (void)hipFree(ctx->d_group_order);
+        ctx->d_group_order = nullptr;
+        ctx->group_order_key[0] = ctx->group_order_key[1] = 0;
+        GSRT_HIP(ctx, hipMalloc(&ctx->d_group_order, sizeof(uint32_t) * A.groups));
+        GSRT_HIP(ctx, hipMemcpy(ctx->d_group_order, ord.data(), sizeof(uint32_t) * A.groups, hipMemcpyHostToDevice));
+        std::memcpy(ctx->group_order_key, key, sizeof key);
+    }
+    A.group_order = ctx->d_group_order;
+    return GSRT_OK;
+}
+
+// k_render_cor's dispatch order of a rank of a sharded frame: its units of kDeal local tiles of the complete XCD rounds
+// centre-out (unit_order_centre, gsrt_plan.cpp). When the context has rendered a whole COR frame of this tile grid, its
+// measured tile costs order the units instead: longest first, each to the least-loaded XCD (deal_units; 8-rank C3 shares
+// 0.3-6 % faster, C4 even: profiles/r06/deal_ab.txt; test switch GSRT_DEBUG_DEAL=0 keeps centre-out). One device keeps
+// the spatial order (C3 -2 %, C2 -2 %, C4 +1.5 % with it).
+static gsrt_status ensure_run_order(gsrt_ctx* ctx, const RenderPlan& plan, RenderArgs& A) {
+    const uint32_t nl = A.ntiles_local, R = (nl / (kXcds * kDeal)) * kXcds;
+    if (R <= 1) return GSRT_OK;
+    const uint32_t key[5] = {nl, plan.row0(), plan.row1(), plan.tiles_x, plan.tiles_y};
+    if (std::memcmp(key, ctx->run_order_key, sizeof key) != 0) {
+        gsrt_status s = sync_all(ctx);
+        if (s != GSRT_OK) return s;
+        std::vector<uint32_t> perm(R);
+        unit_order_centre(R, plan.row0(), plan.row1(), plan.tiles_x, perm.data());
+        const char* de = std::getenv("GSRT_DEBUG_DEAL");
+        if (!(de && de[0] == '0') && ctx->tile_cost_tx == plan.tiles_x && ctx->tile_cost_ty == plan.tiles_y) {
+            // a whole frame's measured tile costs (its last one on this context)
+            std::vector<uint32_t> t((size_t)plan.tiles_x * plan.tiles_y);
+            GSRT_HIP(ctx, hipMemcpy(t.data(), ctx->d_tile_cost[ctx->tile_cost_slot], sizeof(uint32_t) * t.size(),
+                                    hipMemcpyDeviceToHost));
+            std::vector<double> uc(R);
+            unit_costs(t.data(), R, plan.row0(), plan.row1(), plan.tiles_x, plan.tiles_y, uc.data());
+            const std::vector<uint32_t> centre(perm);
+            deal_units(uc.data(), centre.data(), R, perm.data());
+        }
+        (void)hipFree(ctx->d_run_order);
+        ctx->d_run_order = nullptr;
+        std::memset(ctx->run_order_key, 0, sizeof ctx->run_order_key);
+        GSRT_HIP(ctx, hipMalloc(&ctx->d_run_order, sizeof(uint32_t) * R));
+        GSRT_HIP(ctx, hipMemcpy(ctx->d_run_order, perm.data(), sizeof(uint32_t) * R, hipMemcpyHostToDevice));
+        std::memcpy(ctx->run_order_key, key, sizeof key);
+    }
+    A.run_order = ctx->d_run_order;
+    return GSRT_OK;
+}
+
+// Ordering of the prep stage: after every scene change queued on the render stream (update, refit, build), and after
+// the render that last read this slot (frame f-2); not after the render of frame f-1. Takes the slot out of the rotation.
+static gsrt_status order_prep(gsrt_ctx* ctx, const FramePath& f) {
+    const hipStream_t st = ctx->stream, ps = f.ps;
+    const FrameSlot& S = ctx->slot[f.b];
+    if (f.pipelined) {
         // one flag per prep stream
         bool& dirty = ps == ctx->pstream ? ctx->main_dirty : ctx->main_dirty_f;
         if (dirty) {
@@ -2749,11 +2615,11 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
             dirty = false;
         }
         // (on slot streams the slot's last render kernel is on ps already, unless it ran without them)
-        if (S.render_pending && (!slot_streams || S.rstream != ps)) GSRT_HIP(ctx, hipStreamWaitEvent(ps, S.rendered, 0));
+        if (S.render_pending && (!f.slot_streams || S.rstream != ps)) GSRT_HIP(ctx, hipStreamWaitEvent(ps, S.rendered, 0));
         if (gsrt_status su = wait_updates(ctx, ps); su != GSRT_OK) return su;  // the arrays' update copies
         ++ctx->frame_no;
-        ctx->prev_slot = b;
-        ctx->next_slot = (b + 1) % ctx->nslots;
+        ctx->prev_slot = f.b;
+        ctx->next_slot = (f.b + 1) % ctx->nslots;
     } else {
         // everything on the render stream, after all prep work issued so far (both prep streams: with slot
         // streams, frames run on fstream too); the next prep waits for it, and so do scene updates and refits
@@ -2767,31 +2633,16 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
         ctx->serial_reads = true;  // an update retiring the arrays' buffers records this stream's position
         if (gsrt_status su = wait_updates(ctx, st); su != GSRT_OK) return su;
     }
-    const bool leaf_fp = cor && !stats && sc->n >= 2 && !debug_no_leaf_fp();
-    A.leaf_fp = leaf_fp ? 1u : 0u;
-    // a rank of a sharded COR frame: its projection keeps only what its band can see, its frontier kernel skips the
-    // super-groups outside the band
-    RankTiles own{};
-    if (cor && !stats && plan.nranks > 1 && !debug_project_all())
-        own = RankTiles{1u, (float)(plan.row0() * plan.th), (float)(plan.row1() * plan.th), (float)ubo.width};
-    A.own = own;
-    // the BVH frontier needs only the camera and the fitted boxes: pipelined, it runs on its own stream beside
-    // the projection (two short latency chains in parallel instead of in a row)
-    hipStream_t fr = ps;
-    uint32_t* keyed = pipelined ? sc->d_keyed[b] : nullptr;
-    // the fused prep head (k_prep_cor: frontier + projection in one launch) for pipelined COR frames; otherwise the
-    // frontier runs on its own stream beside the projection (two short latency chains in parallel), except on slot
-    // streams
-    const bool fused = pipelined && cor && A.frontier && sc->n >= 2;
-    const bool front_stream = !slot_streams;
-    // a rank share projects in sorted-leaf chunks (k_prep_cor, kLeafOrderRanks): the slot's keyed bitmap follows the
-    // order (switching it starts the bitmap over: all ones, every key rewritten once)
-    const bool leaf_order = fused && own.active && plan.nranks >= kLeafOrderRanks;
-    // the frame's tile cost profile (RenderArgs::tile_cost): a sharded frame's goes where the caller says (gsrt_comm.cpp:
-    // its profile frames), a whole COR frame's into the slot's own buffer (gsrt_row_costs)
+    return GSRT_OK;
+}
+
+// The frame's tile cost profile (RenderArgs::tile_cost): a sharded frame's goes where the caller says (gsrt_comm.cpp:
+// its profile frames), a whole COR frame's into the slot's own buffer (gsrt_row_costs)
+static gsrt_status ensure_tile_cost(gsrt_ctx* ctx, const RenderPlan& plan, const RenderSync* sync, const FramePath& f,
+                                    RenderArgs& A) {
     if (sync && sync->sharded) {
         A.tile_cost = sync->tile_cost;
-    } else if (cor) {
+    } else if (f.cor) {
         const uint32_t nt = plan.tiles_x * plan.tiles_y;
         if (ctx->tile_cost_cap < nt) {
             gsrt_status s = sync_all(ctx);
@@ -2801,23 +2652,34 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
                 if ((s = grow_slot(ctx, &ctx->d_tile_cost[j], sizeof(uint32_t) * nt)) != GSRT_OK) return s;
             ctx->tile_cost_cap = nt;
         }
-        A.tile_cost = ctx->d_tile_cost[b];
-        ctx->tile_cost_slot = b;
+        A.tile_cost = ctx->d_tile_cost[f.b];
+        ctx->tile_cost_slot = f.b;
         ctx->tile_cost_tx = plan.tiles_x;
         ctx->tile_cost_ty = plan.tiles_y;
     }
-    if (keyed && sc->slot_keyed_leaf[b] != leaf_order) {
+    return GSRT_OK;
+}
+
+// The prep head on the prep stream: the slot's bitmaps, its boxes fitted if stale, then the projection and (COR with
+// group lists) the super-groups' frontiers. fr: the stream the frontier went on when it runs beside the projection
+// (launch_lists joins it), else ps.
+static gsrt_status launch_prep(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, const FramePath& f,
+                               const KArgs& k, hipStream_t& fr) {
+    gsrt_ctx* ctx = sc->ctx;
+    const RenderArgs& A = k.a;
+    const uint32_t b = f.b;
+    const hipStream_t ps = f.ps;
+    fr = ps;
+    uint32_t* keyed = f.pipelined ? sc->d_keyed[b] : nullptr;
+    if (keyed && sc->slot_keyed_leaf[b] != f.leaf_order) {
         GSRT_HIP(ctx, hipMemsetAsync(keyed, 0xFF, sizeof(uint32_t) * ((sc->n + 31) / 32 + 1), ps));
-        sc->slot_keyed_leaf[b] = leaf_order;
+        sc->slot_keyed_leaf[b] = f.leaf_order;
     }
-    // a pipelined rank share: the slot's in-band bitmap for this camera and band (k_classify, once per AABB version and
-    // key), which its fit and projection read instead of the AABBs of the splats the band cannot see
-    const bool band_frame = pipelined && own.active && sc->n >= 2;
-    const FitBandKey bkey = band_frame ? make_band_key(ubo, own) : FitBandKey{};
-    if (band_frame) {
+    const FitBandKey bkey = f.band_frame ? make_band_key(ubo, f.own) : FitBandKey{};
+    if (f.band_frame) {
         if (!sc->d_inband[b]) GSRT_HIP(ctx, hipMalloc(&sc->d_inband[b], sizeof(uint32_t) * ((sc->n + 31) / 32 + 1)));
         if (sc->slot_inband_ver[b] != sc->aabb_version || !same_key(bkey, sc->slot_inband_key[b])) {
-            hipLaunchKernelGGL(k_classify, dim3((sc->n + 255) / 256), dim3(64), 0, ps, sc->n, ubo, own, sc->d_aabbs,
+            hipLaunchKernelGGL(k_classify, dim3((sc->n + 255) / 256), dim3(64), 0, ps, sc->n, ubo, f.own, sc->d_aabbs,
                                sc->d_inband[b]);
             sc->slot_inband_ver[b] = sc->aabb_version;
             sc->slot_inband_key[b] = bkey;
@@ -2828,96 +2690,123 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     // boxes; its projection gives their splats +inf keys anyway). COR frames put each leaf's footprint box into its node
     // (leaf_fp); REF and counting frames need the AABBs there, which the slot's fit restores
     {
-        const FitBand fb{band_frame ? sc->d_inband[b] : nullptr};
-        if (gsrt_status fs = lbvh_fit_if_stale(sc, b, ps, !leaf_fp, band_frame ? &fb : nullptr, band_frame ? &bkey : nullptr);
+        const FitBand fb{f.band_frame ? sc->d_inband[b] : nullptr};
+        if (gsrt_status fs = lbvh_fit_if_stale(sc, b, ps, !f.leaf_fp, f.band_frame ? &fb : nullptr,
+                                               f.band_frame ? &bkey : nullptr);
             fs != GSRT_OK)
             return fs;
     }
     sc->last_slot = b;
-    if (fused) {
-        k.a.cull2d = 1u;  // as set below for the non-stats render (neither part reads it)
+    if (f.fused) {
         const ProjArgs pa{sc->n, sc->d_params, sc->d_aabbs, sc->d_recs[b], sc->d_nodes[b], sc->d_gid_slot,
-                          sc->d_footprint[b], ctx->d_counters, own, keyed, A.leaf_fp,
-                          leaf_order ? sc->d_leaf_gid : nullptr, band_frame ? sc->d_inband[b] : nullptr,
+                          sc->d_footprint[b], ctx->d_counters, f.own, keyed, A.leaf_fp,
+                          f.leaf_order ? sc->d_leaf_gid : nullptr, f.band_frame ? sc->d_inband[b] : nullptr,
                           sc->d_flags};
         hipLaunchKernelGGL(k_prep_cor, dim3(A.sgroups + (sc->n + 63) / 64), dim3(64), 0, ps, k, pa);
-    } else if (front_stream && pipelined && cor && A.frontier) {
+    } else if (!f.slot_streams && f.pipelined && A.frontier) {
+        // the BVH frontier needs only the camera and the fitted boxes: it runs on its own stream beside the projection
         fr = ctx->fstream;
         GSRT_HIP(ctx, hipEventRecord(ctx->ev_fit, ps));
         GSRT_HIP(ctx, hipStreamWaitEvent(fr, ctx->ev_fit, 0));
-        k.a.cull2d = 1u;  // as set below for the non-stats render (the frontier does not read it)
         hipLaunchKernelGGL(k_frontier, dim3(A.sgroups), dim3(64), 0, fr, k);
     }
     // pipelined COR frames keep the slot's keyed bitmap; any other projection of the slot (REF, counting pass)
     // writes every record unbooked, so the bitmap goes back to all ones behind it (the next prep waits for it)
-    if (!fused)
+    if (!f.fused)
         launch_project(ps, sc->n, plan.mode, ubo, sc->d_params, sc->d_aabbs, sc->d_recs[b], sc->d_nodes[b],
-                       sc->d_gid_slot, cor ? sc->d_footprint[b] : nullptr, ctx->d_counters, &own, keyed, leaf_fp,
+                       sc->d_gid_slot, f.cor ? sc->d_footprint[b] : nullptr, ctx->d_counters, &f.own, keyed, f.leaf_fp,
                        sc->d_flags);
-    sc->slot_leaf_fp[b] = leaf_fp;  // (either projection above)
-    if (!pipelined && sc->n && sc->d_keyed[b])
+    sc->slot_leaf_fp[b] = f.leaf_fp;  // (either projection above)
+    if (!f.pipelined && sc->n && sc->d_keyed[b])
         GSRT_HIP(ctx, hipMemsetAsync(sc->d_keyed[b], 0xFF, sizeof(uint32_t) * ((sc->n + 31) / 32 + 1), ps));
-    if (!cor) {
-        if (sc->ntri) {
-            const size_t px = (size_t)ubo.width * ubo.height;
-            if (ctx->tri_t_pixels < px) {
-                gsrt_status s = sync_all(ctx);
-                if (s != GSRT_OK) return s;
-                ctx->tri_t_pixels = 0;
-                if ((s = grow_slot(ctx, &ctx->d_tri_t, sizeof(float) * px)) != GSRT_OK) return s;
-                ctx->tri_t_pixels = px;
-            }
-            launch_mesh_thit(st, ubo, sc, ctx->d_tri_t);
-            k.a.tri_t = ctx->d_tri_t;
+    return GSRT_OK;
+}
+
+// A REF frame's render kernel on the render stream, after the mesh's closest hits where the scene holds triangles
+static gsrt_status launch_ref(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, const FramePath& f,
+                              RenderSync* sync, KArgs& k) {
+    gsrt_ctx* ctx = sc->ctx;
+    const hipStream_t st = ctx->stream;
+    if (sc->ntri) {
+        const size_t px = (size_t)ubo.width * ubo.height;
+        if (ctx->tri_t_pixels < px) {
+            gsrt_status s = sync_all(ctx);
+            if (s != GSRT_OK) return s;
+            ctx->tri_t_pixels = 0;
+            if ((s = grow_slot(ctx, &ctx->d_tri_t, sizeof(float) * px)) != GSRT_OK) return s;
+            ctx->tri_t_pixels = px;
         }
-        if (sync && sync->wait) GSRT_HIP(ctx, hipStreamWaitEvent(st, sync->wait, 0));
-        if (sync) sync->stream = st;
-        timing_mark(ctx, 1);
-        if (stats) hipLaunchKernelGGL((k_render_ref<true>), dim3(A.ntiles_local), dim3(64), 0, st, k);
-        else hipLaunchKernelGGL((k_render_ref<false>), dim3(A.ntiles_local), dim3(64), 0, st, k);
-        if (stats && A.ray_stats && !plan.packed)  // VS-style traversal statistics (gsrt_vs_stats)
-            hipLaunchKernelGGL(k_ref_node_stats, dim3(((ubo.width + 7) / 8) * ((ubo.height + 7) / 8)), dim3(64), 0, st, k);
-        timing_mark(ctx, 2);
-        GSRT_HIP(ctx, hipGetLastError());
-        return GSRT_OK;
+        launch_mesh_thit(st, ubo, sc, ctx->d_tri_t);
+        k.a.tri_t = ctx->d_tri_t;
     }
-    const bool sh = sc->d_sh != nullptr;
-    const bool lut = (plan.mode & GSRT_FLAG_LUT) != 0;
-    void (*render)(hipStream_t, const KArgs&) =
-        sh ? (lut ? (stats ? launch_cor_t<true, true, true> : launch_cor_t<true, true, false>)
-                  : (stats ? launch_cor_t<true, false, true> : launch_cor_t<true, false, false>))
-           : (lut ? (stats ? launch_cor_t<false, true, true> : launch_cor_t<false, true, false>)
-                  : (stats ? launch_cor_t<false, false, true> : launch_cor_t<false, false, false>));
-    if (A.depth_out)  // GSRT_FLAG_DEPTH (never with stats, gsrt_api.cpp check_render_args)
-        render = sh ? (lut ? launch_cor_t<true, true, false, true> : launch_cor_t<true, false, false, true>)
-                    : (lut ? launch_cor_t<false, true, false, true> : launch_cor_t<false, false, false, true>);
-    if (A.feat_out)  // GSRT_FLAG_FEATURES (never with stats or depth): no SH whatever the scene holds
-        render = lut ? launch_cor_t<false, true, false, false, true> : launch_cor_t<false, false, false, false, true>;
-    if (A.grad_rows)  // GSRT_FLAG_FEATURE_GRAD (never with stats, depth or features): likewise no SH
-        render = lut ? launch_cor_t<false, true, false, false, false, true>
-                     : launch_cor_t<false, false, false, false, false, true>;
-    k.a.cull2d = stats ? 0u : 1u;  // the counting pass keeps every AABB candidate (|C_r| of SURVEY.md 8d)
+    if (sync && sync->wait) GSRT_HIP(ctx, hipStreamWaitEvent(st, sync->wait, 0));
+    if (sync) sync->stream = st;
+    timing_mark(ctx, 1);
+    if (f.stats) hipLaunchKernelGGL((k_render_ref<true>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
+    else hipLaunchKernelGGL((k_render_ref<false>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
+    if (f.stats && k.a.ray_stats && !plan.packed)  // VS-style traversal statistics (gsrt_vs_stats)
+        hipLaunchKernelGGL(k_ref_node_stats, dim3(((ubo.width + 7) / 8) * ((ubo.height + 7) / 8)), dim3(64), 0, st, k);
+    timing_mark(ctx, 2);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+// The k_render_cor instantiation of a frame: every one the library holds is named here and nowhere else. Feature and
+// gradient frames blend no SH whatever the scene holds (never with stats or depth, gsrt_api.cpp check_render_args).
+enum class CorKind { plain, stats, depth, feat, grad };
+using CorLaunch = void (*)(hipStream_t, const KArgs&);
+static CorLaunch cor_kernel(CorKind kind, bool sh, bool lut) {
+    // rows: the scene's SH, none; columns: the ExpLUT, the exact exponential (the order the code object holds them in)
+    static const CorLaunch colour[2][2][2] = {  // {counting pass, plain}
+        {{launch_cor_t<true, true, true>, launch_cor_t<true, true, false>},
+         {launch_cor_t<true, false, true>, launch_cor_t<true, false, false>}},
+        {{launch_cor_t<false, true, true>, launch_cor_t<false, true, false>},
+         {launch_cor_t<false, false, true>, launch_cor_t<false, false, false>}}};
+    static const CorLaunch with_depth[2][2] = {
+        {launch_cor_t<true, true, false, true>, launch_cor_t<true, false, false, true>},
+        {launch_cor_t<false, true, false, true>, launch_cor_t<false, false, false, true>}};
+    static const CorLaunch features[2] = {launch_cor_t<false, true, false, false, true>,
+                                          launch_cor_t<false, false, false, false, true>};
+    static const CorLaunch gradients[2] = {launch_cor_t<false, true, false, false, false, true>,
+                                           launch_cor_t<false, false, false, false, false, true>};
+    const uint32_t row = sh ? 0 : 1, col = lut ? 0 : 1;
+    switch (kind) {
+        case CorKind::plain: return colour[row][col][1];
+        case CorKind::stats: return colour[row][col][0];
+        case CorKind::depth: return with_depth[row][col];
+        case CorKind::feat: return features[col];
+        case CorKind::grad: return gradients[col];
+    }
+    return nullptr;
+}
+
+// The frame's candidate lists: the frontier joined (or run here), then the first-round lists on the prep stream beside
+// the previous frame's render kernel. ls: the stream they went on.
+static gsrt_status launch_lists(gsrt_ctx* ctx, const FramePath& f, const RenderSync* sync, const KArgs& k, hipStream_t fr,
+                                hipStream_t& ls) {
+    const RenderArgs& A = k.a;
+    const hipStream_t ps = f.ps;
     if (A.frontier && fr != ps) {  // pipelined: the frontier ran beside the projection; join it here
         GSRT_HIP(ctx, hipEventRecord(ctx->ev_front, fr));
         GSRT_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_front, 0));
-    } else if (A.frontier && !fused) {
+    } else if (A.frontier && !f.fused) {
         hipLaunchKernelGGL(k_frontier, dim3(A.sgroups), dim3(64), 0, ps, k);
     }
-    // the first-round lists, on the prep stream beside the previous frame's render kernel. Side lists: a rank share of
-    // a moving scene (an update or refit came before this frame, and likely comes before the next) runs them on the
-    // other prep stream, which idles on the two-stream scheme, so that the next frame's update copies, refit and
-    // projection on the prep stream (which read and write none of this slot's lists) need not wait for them: the rank's
-    // serial chain is then max(lists, copies) + fit + projection instead of their sum. The lists read only this
-    // slot's nodes, records and footprints, and the render kernel waits for them through `prepared` (recorded there)
-    const bool side_lists = pipelined && !slot_streams && sync && sync->sharded && ctx->scene_moved && A.use_groups &&
+    // Side lists: a rank share of a moving scene (an update or refit came before this frame, and likely comes before the
+    // next) runs them on the other prep stream, which idles on the two-stream scheme, so that the next frame's update
+    // copies, refit and projection on the prep stream (which read and write none of this slot's lists) need not wait for
+    // them: the rank's serial chain is then max(lists, copies) + fit + projection instead of their sum. The lists read
+    // only this slot's nodes, records and footprints, and the render kernel waits for them through `prepared` (recorded
+    // there)
+    const bool side_lists = f.pipelined && !f.slot_streams && sync && sync->sharded && ctx->scene_moved && A.use_groups &&
                             ps == ctx->pstream;
-    hipStream_t ls = ps;
+    ls = ps;
     if (side_lists) {
         ls = ctx->fstream;
         GSRT_HIP(ctx, hipEventRecord(ctx->ev_lists, ps));
         GSRT_HIP(ctx, hipStreamWaitEvent(ls, ctx->ev_lists, 0));
     }
-    if (pipelined) ctx->scene_moved = false;
+    if (f.pipelined) ctx->scene_moved = false;
     if (A.use_groups) {
         // only the groups with a tile of this rank's band (the head of group_order); the others would return at once
         const uint32_t ng = std::max(1u, std::min(ctx->group_own, A.groups));
@@ -2930,14 +2819,26 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     }
     else hipLaunchKernelGGL(k_collect_cor, dim3(A.ntiles_local), dim3(64), 0, ps, k);
     GSRT_HIP(ctx, hipGetLastError());
-    // the render kernel: on the render stream after the lists (cross-stream), or (slot streams) on the slot's
-    // stream right behind them, after the previous frame's render kernel (cross-stream)
+    return GSRT_OK;
+}
+
+// The render kernel: on the render stream after the lists (cross-stream), or (slot streams) on the slot's stream right
+// behind them, after the previous frame's render kernel (cross-stream); then the slot's `rendered` bookkeeping
+static gsrt_status launch_cor(gsrt_scene* sc, const RenderPlan& plan, const FramePath& f, RenderSync* sync, KArgs& k,
+                              hipStream_t ls) {
+    gsrt_ctx* ctx = sc->ctx;
+    const hipStream_t st = ctx->stream;
+    FrameSlot& S = ctx->slot[f.b];
+    const RenderArgs& A = k.a;
+    const CorKind kind = A.grad_rows ? CorKind::grad : A.feat_out ? CorKind::feat : A.depth_out ? CorKind::depth
+                         : f.stats   ? CorKind::stats : CorKind::plain;
+    const CorLaunch render = cor_kernel(kind, sc->d_sh != nullptr, (plan.mode & GSRT_FLAG_LUT) != 0);
     hipStream_t rs = st;
-    if (slot_streams) {
-        rs = ps;
-        const FrameSlot& O = ctx->slot[prev];
+    if (f.slot_streams) {
+        rs = f.ps;
+        const FrameSlot& O = ctx->slot[f.prev];
         if (O.render_pending && !(sync && sync->private_out)) GSRT_HIP(ctx, hipStreamWaitEvent(rs, O.rendered, 0));
-    } else if (pipelined) {
+    } else if (f.pipelined) {
         GSRT_HIP(ctx, hipEventRecord(S.prepared, ls));
         GSRT_HIP(ctx, hipStreamWaitEvent(st, S.prepared, 0));
     }
@@ -2945,7 +2846,7 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
     if (sync) sync->stream = rs;
     k.a.prelisted = 1;
     // sampled render kernel time for the slot-stream and prep-priority decisions (use_slot_streams)
-    const bool sample = pipelined && sync && !S.timed && ctx->frame_no % kTimedEvery == 1 &&
+    const bool sample = f.pipelined && sync && !S.timed && ctx->frame_no % kTimedEvery == 1 &&
                         S.t0 && S.t1;
     if (sample) GSRT_HIP(ctx, hipEventRecord(S.t0, rs));
     timing_mark(ctx, 1, rs);  // the timed kernel is the shading/continuation kernel k_render_cor
@@ -2962,15 +2863,41 @@ gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan&
         GSRT_HIP(ctx, hipEventRecord(S.t1, rs));
         S.timed = true;
     }
-    if (pipelined) {
+    if (f.pipelined) {
         GSRT_HIP(ctx, hipEventRecord(S.rendered, rs));
         S.render_pending = true;
         S.rstream = rs;
     }
-    ctx->last_slot_streams = slot_streams;
+    ctx->last_slot_streams = f.slot_streams;
     // whatever follows on the render stream (copies, gathers, downloads) comes after this frame
-    if (slot_streams) GSRT_HIP(ctx, hipStreamWaitEvent(st, S.rendered, 0));
+    if (f.slot_streams) GSRT_HIP(ctx, hipStreamWaitEvent(st, S.rendered, 0));
     return GSRT_OK;
+}
+
+gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_out,
+                          gsrt_raystate* d_rs, RenderSync* sync) {
+    gsrt_ctx* ctx = sc->ctx;
+    if (sync) sync->stream = ctx->stream;
+    const FramePath f = frame_path(sc, ubo, plan, sync);
+    gsrt_status s = follow_updates(ctx, f);
+    if (s != GSRT_OK) return s;
+    KArgs k;
+    fill_args(k, sc, ubo, plan, d_out, d_rs, sync, f);
+    if (k.a.ntiles_local == 0) {  // a band without rows (fewer tile rows than ranks): nothing to render
+        timing_mark(ctx, 1);
+        timing_mark(ctx, 2);
+        return GSRT_OK;
+    }
+    if ((s = ensure_slot_buffers(sc, f, k.a)) != GSRT_OK) return s;
+    if (f.use_groups && (s = ensure_group_order(ctx, k.a)) != GSRT_OK) return s;
+    if (f.cor && plan.nranks > 1 && (s = ensure_run_order(ctx, plan, k.a)) != GSRT_OK) return s;
+    if ((s = order_prep(ctx, f)) != GSRT_OK) return s;
+    if ((s = ensure_tile_cost(ctx, plan, sync, f, k.a)) != GSRT_OK) return s;
+    hipStream_t fr, ls;
+    if ((s = launch_prep(sc, ubo, plan, f, k, fr)) != GSRT_OK) return s;
+    if (!f.cor) return launch_ref(sc, ubo, plan, f, sync, k);
+    if ((s = launch_lists(ctx, f, sync, k, fr, ls)) != GSRT_OK) return s;
+    return launch_cor(sc, plan, f, sync, k, ls);
 }
 
 // a band's row costs from its tiles' (k_render_cor's tile_cost, local order): one wave per row
@@ -3036,14 +2963,3 @@ extern "C" int gsrt_diag_wave_times(uint32_t kind, void* out, uint32_t n) {
                                hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 #endif
-
-extern "C" gsrt_status gsrt_deal_units(const double* cost, const uint32_t* centre, uint32_t units, uint32_t* perm) {
-    if (!cost || !centre || !perm || units % gsrt::kXcds) return GSRT_E_ARG;
-    std::vector<uint8_t> seen(units, 0);  // centre must be a permutation of the units
-    for (uint32_t i = 0; i < units; ++i) {
-        if (centre[i] >= units || seen[centre[i]]) return GSRT_E_ARG;
-        seen[centre[i]] = 1;
-    }
-    gsrt::deal_units(cost, centre, units, perm);
-    return GSRT_OK;
-}

@@ -64,7 +64,8 @@ EXPORTS = [
     "gsrt_tile_pack_dump8_host", "gsrt_tile_unpack_dump8_host", "gsrt_timing_stride", "gsrt_partition_hash",
     "gsrt_decide_bands", "gsrt_render_depth", "gsrt_render_depth_async", "gsrt_depth_buffer", "gsrt_dump_pfm",
     "gsrt_scene_set_features", "gsrt_scene_features", "gsrt_render_features", "gsrt_render_features_async",
-    "gsrt_feature_buffer", "gsrt_render_feature_grad", "gsrt_render_feature_grad_async",
+    "gsrt_feature_buffer", "gsrt_render_feature_grad", "gsrt_render_feature_grad_async", "gsrt_group_order",
+    "gsrt_unit_order",
 ]
 
 
@@ -164,6 +165,8 @@ def _load():
         "gsrt_debug_row_profile": ([P, P, u32, P], i32),
         "gsrt_debug_streams": ([P, P, P], i32),
         "gsrt_deal_units": ([P, P, u32, P], i32),
+        "gsrt_group_order": ([u32, u32, u32, u32, u32, u32, P, P], i32),
+        "gsrt_unit_order": ([u32, u32, u32, u32, P], i32),
         "gsrt_render_depth": ([P, P, u32, u32, P, P], i32),
         "gsrt_render_depth_async": ([P, P, u32, u32, P, P], i32),
         "gsrt_depth_buffer": ([P], P),
@@ -386,6 +389,22 @@ def deal_units(cost, centre=None) -> np.ndarray:
     ctr = np.arange(c.size, dtype=np.uint32) if centre is None else np.ascontiguousarray(centre, np.uint32)
     out = np.zeros(c.size, np.uint32)
     _check(lib.gsrt_deal_units(_p(c), _p(ctr), c.size, _p(out)))
+    return out
+
+
+def group_order(groups_x, groups_y, fg, row0, row1, nranks):
+    """k_group_list's dispatch order over groups_x x groups_y tile groups of fg x fg tiles (gsrt_group_order): (ord, own),
+    the first own entries of ord being the groups with a tile row of the band [row0, row1)"""
+    ord_ = np.zeros(groups_x * groups_y, np.uint32)
+    own = ctypes.c_uint32(0)
+    _check(lib.gsrt_group_order(groups_x, groups_y, fg, row0, row1, nranks, _p(ord_), ctypes.byref(own)))
+    return ord_, int(own.value)
+
+
+def unit_order(units, row0, row1, tiles_x) -> np.ndarray:
+    """the centre-out order of a rank share's render units of 64 local tiles of the band [row0, row1) (gsrt_unit_order)"""
+    out = np.zeros(units, np.uint32)
+    _check(lib.gsrt_unit_order(units, row0, row1, tiles_x, _p(out)))
     return out
 
 

@@ -3,8 +3,8 @@
  *
  * Nothing here is part of the reference boundary: a reference-side caller links gsrt.h alone. These
  * entry points serve the test suite, the bench and multi-process transports other than RCCL: diagnostic counters,
- * host mirrors of the sharded layout and of the partition rule, emulated gathers on one device, and the synthetic
- * clouds of SURVEY.md §8d. They are exported by the same library.
+ * host mirrors of the sharded layout and of the partition rule, the host's dispatch orders (gsrt_deal_units,
+ * gsrt_group_order, gsrt_unit_order), emulated gathers on one device, and the synthetic clouds of SURVEY.md §8d. They are exported by the same library.
  */
 #ifndef GSRT_TEST_H
 #define GSRT_TEST_H
@@ -28,10 +28,22 @@ gsrt_status gsrt_debug_counters_hi(gsrt_ctx* ctx, uint64_t out[16]);
  * automatic balancing of an N-rank job all-reduces. */
 gsrt_status gsrt_debug_share_costs(gsrt_ctx* ctx, int on);
 gsrt_status gsrt_debug_row_profile(gsrt_ctx* ctx, uint32_t* rows, uint32_t cap, uint32_t* n);
-/* the render-unit deal of a rank share (launch_render, host logic): units (a multiple of 8) with costs cost[units], ties
+/* the render-unit deal of a rank share (gsrt_plan.cpp, host logic): units (a multiple of 8) with costs cost[units], ties
  * broken in the order centre[] lists them (a permutation); perm[k * 8 + x] = XCD x's k-th unit. Longest first, each unit
  * to the XCD with the least cost so far among those holding fewer than units / 8 */
 gsrt_status gsrt_deal_units(const double* cost, const uint32_t* centre, uint32_t units, uint32_t* perm);
+/* the two dispatch orders a COR frame uploads (gsrt_plan.cpp, host logic; no device).
+ * gsrt_group_order: the order k_group_list's workgroups take the groups_x x groups_y tile groups (fg x fg tiles each) in:
+ * ord[groups_x * groups_y], *own = the groups at its head with a tile row in the band [row0, row1) (nranks <= 1: every
+ * group, the band is not read). Super-groups of 4 x 4 groups centre-out, those with a group of the band dealt round-robin
+ * over the 8 XCDs, workgroup i taking the next group of XCD i % 8's list (or of the longest list left); the groups
+ * outside the band follow in row-major order.
+ * gsrt_unit_order: the centre-out order of a rank share's `units` (a multiple of 8) render units of 64 local tiles of the
+ * band [row0, row1) of a frame tiles_x tiles wide, which must hold them: by the distance of a unit's middle tile from
+ * the band's centre, nearest first, ties by index. */
+gsrt_status gsrt_group_order(uint32_t groups_x, uint32_t groups_y, uint32_t fg, uint32_t row0, uint32_t row1,
+                             uint32_t nranks, uint32_t* ord, uint32_t* own);
+gsrt_status gsrt_unit_order(uint32_t units, uint32_t row0, uint32_t row1, uint32_t tiles_x, uint32_t* perm);
 /* the context's streams (hipStream_t) in creation order: render, prep H 0, prep L 0, prep H 1, prep L 1, update, comm
  * (NULL before gsrt_comm_init); *n = 7. For the hardware-queue map (profiles/probes/gsrt_queue_map.py) */
 gsrt_status gsrt_debug_streams(gsrt_ctx* ctx, void* out[8], uint32_t* n);

@@ -1,6 +1,7 @@
 """Host-side checks that need no GPU: the C-ABI library loads and exports every declared symbol, the
 host logic behind the boundary (camera / UBO, synthetic clouds, frame dumps, tile plan) agrees with
 the oracle or the reference's formats, and the product refuses to run without a device."""
+import ctypes
 import json
 import os
 import re
@@ -317,3 +318,120 @@ def test_deal_units(units, seed):
     assert loads.max() - loads.min() <= cost.max() + 1e-9
     with pytest.raises(gsrt.GsrtError):
         gsrt.deal_units(cost[:units - 1] if units > 8 else cost[:7])
+
+
+XCDS, SG, SUPER, DEAL = 8, 4, 16, 64  # kXcds, kSG, kSuper, kDeal (gsrt_device.hpp)
+
+
+def _group_order_py(gx_n, gy_n, fg, row0, row1, nranks):
+    """a restatement of k_group_list's dispatch order: super-groups of SG x SG groups by the float32 distance of their
+    centre (clipped to the grid) from the grid's centre, nearest first (sorted() is stable: ties by index); those holding
+    a group with a tile row of the band dealt round-robin over the XCDs; workgroup i takes the next group of XCD
+    i % 8's list, or of the longest list left (lowest XCD on ties); the groups outside the band follow row-major"""
+    f = np.float32
+    own = [nranks <= 1 or any(r // fg == g // gx_n for r in range(row0, row1)) for g in range(gx_n * gy_n)]
+    sx_n, sy_n = -(-gx_n // SG), -(-gy_n // SG)
+
+    def d2(k):
+        cx = min(f((k % sx_n) * SG) + f(0.5) * f(SG), f(gx_n))
+        cy = min(f((k // sx_n) * SG) + f(0.5) * f(SG), f(gy_n))
+        dx, dy = cx - f(0.5) * f(gx_n), cy - f(0.5) * f(gy_n)
+        return dx * dx + dy * dy
+
+    lists, dealt = [[] for _ in range(XCDS)], 0
+    for k in sorted(range(sx_n * sy_n), key=d2):
+        sx, sy = k % sx_n, k // sx_n
+        mine = [gy * gx_n + gx for gy in range(sy * SG, min((sy + 1) * SG, gy_n))
+                for gx in range(sx * SG, min((sx + 1) * SG, gx_n)) if own[gy * gx_n + gx]]
+        if mine:
+            lists[dealt % XCDS] += mine
+            dealt += 1
+    total, pos, order = sum(len(l) for l in lists), [0] * XCDS, []
+    for i in range(total):
+        x = i % XCDS
+        if pos[x] == len(lists[x]):
+            x = max(range(XCDS), key=lambda y: (len(lists[y]) - pos[y], -y))
+        order.append(lists[x][pos[x]])
+        pos[x] += 1
+    return order + [g for g in range(gx_n * gy_n) if not own[g]], total
+
+
+# (groups_x, groups_y, fg, row0, row1, nranks): 1x1; 5x3 (no multiple of kSG); the 1080p grids of 8x8 tiles (240 x 135)
+# at fg 4 and fg 2; the 60x34 grid as rank 3 of 8 with even bands, with a band thinner than a group row, with an empty
+# band (inside a group row, and on a group boundary)
+GROUP_GRIDS = [
+    (1, 1, 4, 0, 1, 1), (5, 3, 4, 0, 12, 1), (60, 34, 4, 0, 135, 1), (120, 68, 2, 0, 135, 1),
+    (60, 34, 4, 51, 68, 8), (60, 34, 4, 51, 52, 8), (5, 3, 4, 5, 6, 2), (60, 34, 4, 51, 51, 8), (60, 34, 4, 52, 52, 8),
+]
+
+
+@pytest.mark.parametrize("gx_n,gy_n,fg,row0,row1,nranks", GROUP_GRIDS)
+def test_group_order(gx_n, gy_n, fg, row0, row1, nranks):
+    """gsrt_group_order (the order launch_render uploads for k_group_list) against the restatement: a permutation of all
+    groups whose first `own` entries are exactly the groups with a tile row in [row0, row1); every group with one rank"""
+    order, own = gsrt.group_order(gx_n, gy_n, fg, row0, row1, nranks)
+    want, want_own = _group_order_py(gx_n, gy_n, fg, row0, row1, nranks)
+    assert own == want_own and order.tolist() == want
+    groups = gx_n * gy_n
+    assert sorted(order.tolist()) == list(range(groups))
+    band_rows = set(range(gy_n)) if nranks == 1 else {r // fg for r in range(row0, row1)}
+    assert sorted(order[:own].tolist()) == [g for g in range(groups) if g // gx_n in band_rows]
+    if nranks == 1:
+        assert own == groups
+    if row0 == row1:
+        assert own == 0
+
+
+def _band_tile_py(lt, row0, row1, tiles_x):
+    """band_tile (gsrt_device.hpp): local tile lt of the band -> (tx, ty); super-tiles of SUPER x SUPER tiles row-major,
+    row-major inside each, over the band's own grid"""
+    tiles_y = row1 - row0
+    R = lt // (SUPER * tiles_x)
+    hR = min(tiles_y - R * SUPER, SUPER)
+    k1 = lt - R * SUPER * tiles_x
+    C = k1 // (hR * SUPER)
+    wC = min(tiles_x - C * SUPER, SUPER)
+    k2 = k1 - C * hR * SUPER
+    return C * SUPER + k2 % wC, R * SUPER + k2 // wC + row0
+
+
+def _unit_d2_py(units, row0, row1, tiles_x):
+    f = np.float32
+    cy = f(0.5) * f(row0 + row1)
+    out = []
+    for q in range(units):
+        tx, ty = _band_tile_py(q * DEAL + DEAL // 2, row0, row1, tiles_x)
+        dx, dy = (f(tx) + f(0.5)) - f(0.5) * f(tiles_x), (f(ty) + f(0.5)) - cy
+        out.append(dx * dx + dy * dy)
+    return out
+
+
+# bands off the frame's centre (a 240 x 135 tile frame: rows 0..135), each holding its units: 8 units in 3 rows, 16 in a
+# band with a partial super-tile row, 224 (an 8-rank 1080p share at 4 spp has 252) in 60 rows
+@pytest.mark.parametrize("units,row0,row1,tiles_x", [(8, 7, 10, 240), (16, 100, 121, 50), (224, 70, 130, 240)])
+def test_unit_order(units, row0, row1, tiles_x):
+    """gsrt_unit_order (a rank share's centre-out render-unit order) against the restatement: a permutation by the
+    float32 distance of each unit's middle tile from the band's centre, ties by index; the nearest unit first"""
+    d2 = _unit_d2_py(units, row0, row1, tiles_x)
+    perm = gsrt.unit_order(units, row0, row1, tiles_x)
+    assert perm.tolist() == sorted(range(units), key=lambda q: d2[q])  # sorted() is stable
+    assert sorted(perm.tolist()) == list(range(units))
+    assert int(perm[0]) == int(np.argmin(d2))
+
+
+def test_dispatch_order_hooks_refuse_bad_arguments():
+    u32 = ctypes.c_uint32
+    buf, own = (u32 * 64)(), u32(0)
+    go, uo = gsrt.lib.gsrt_group_order, gsrt.lib.gsrt_unit_order
+    assert go(4, 4, 4, 0, 16, 1, buf, ctypes.byref(own)) == gsrt.OK
+    assert go(4, 4, 4, 0, 16, 1, None, ctypes.byref(own)) == gsrt.E_ARG
+    assert go(4, 4, 4, 0, 16, 1, buf, None) == gsrt.E_ARG
+    assert go(0, 4, 4, 0, 16, 1, buf, ctypes.byref(own)) == gsrt.E_ARG
+    assert go(4, 0, 4, 0, 16, 1, buf, ctypes.byref(own)) == gsrt.E_ARG
+    assert go(4, 4, 0, 0, 16, 1, buf, ctypes.byref(own)) == gsrt.E_ARG
+    assert uo(8, 0, 16, 32, buf) == gsrt.OK
+    assert uo(8, 0, 16, 32, None) == gsrt.E_ARG
+    assert uo(12, 0, 16, 48, buf) == gsrt.E_ARG  # not a multiple of 8
+    assert uo(8, 0, 16, 0, buf) == gsrt.E_ARG
+    assert uo(8, 0, 15, 32, buf) == gsrt.E_ARG  # the band holds fewer than 8 units of 64 tiles
+    assert uo(8, 16, 16, 32, buf) == gsrt.E_ARG
