@@ -716,18 +716,52 @@ struct Stage {
 };
 static_assert(sizeof(Stage) == kGroup * 256 && sizeof(Stage) % 1024 == 0, "whole wave-instructions of 16-B pieces");
 
-// DMA instructions per stage (one 16-B piece per lane each), and the wait for the stage issued `younger`
-// stages before the most recent one: vmcnt counts VMEM operations in issue order, so vmcnt(younger * ops)
-// leaves the younger stages' DMAs in flight (any other younger VMEM operation only makes the wait stricter)
-template <bool SH, bool FEAT = false>
-constexpr uint32_t kStagePieces = SH ? 16 * kGroup : (FEAT ? 8 * kGroup : 4 * kGroup);
-template <bool SH, bool FEAT = false>
-constexpr uint32_t kStagePieceOps = (kStagePieces<SH, FEAT> + 63) / 64;
+// ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
+// with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
+// or a gradient frame, the backward of a feature frame to the feature table (GSRT_FLAG_FEATURE_GRAD, grad_rows). SH: the
+// scene's SH-3 rows are blended; LUT: the ExpLUT instead of the exact exponential. Sixteen kernels: {plain, stats,
+// depth} x SH x LUT and {feat, grad} x LUT, named by cor_kernel and nowhere else. What a kind adds (blend_hit) sits under
+// if constexpr on these members: the other kinds' code does not change. The RGBA of feat and grad is the no-SH frame's.
+enum class CorKind { plain, stats, depth, feat, grad };
+// waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
+// spill to scratch, DESIGN.md section 3)
+constexpr uint32_t kFeatWaves = 4;
+// and for the two grad kernels, likewise (96 VGPRs, no spill at 5 waves; at 6 the no-LUT kernel spills 12 VGPRs to scratch
+// and the LUT kernel stays at 96; 5 measured 4-5 % faster than 4: DESIGN.md section 3). A/B builds (make ab AB_FLAGS=...,
+// never the product library) set GSRT_GRAD_WAVES, or GSRT_GRAD_AB: 1 leaves the stage's atomic out (timing only), 2
+// makes it count adds per row and wave-instructions instead of summing (profiles/feature_grad_cost.py); defaults at the top
+constexpr uint32_t kGradWaves = GSRT_GRAD_WAVES;
+struct NoPayload {};
+struct DepthPayload { float D; };      // sum of z w over the blended hits (expected view depth, premultiplied)
+struct ChannelPayload { float F[16]; };  // feat: sum of f_k w over the blended hits per channel; grad: the lane's G_k / ns
+template <CorKind K, bool SH, bool LUT>
+struct CorVariant {
+    static constexpr bool sh = SH, lut = LUT;
+    static constexpr bool stats = K == CorKind::stats, depth = K == CorKind::depth;
+    static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad;
+    static_assert(!(feat || grad) || !SH, "feature and gradient frames evaluate no SH");
+    // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
+    // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
+    // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
+    static constexpr uint32_t waves = grad ? kGradWaves : feat ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6);
+    // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
+    // stage, and DMA instructions per stage (one piece per lane each)
+    static constexpr uint32_t row_pieces = feat ? 4u : 12u;
+    static constexpr uint32_t stage_pieces = SH ? 16 * kGroup : (feat ? 8 * kGroup : 4 * kGroup);
+    static constexpr uint32_t stage_ops = (stage_pieces + 63) / 64;
+    // what the kind adds to a ray's state (CorRay) and to a pixel's sums (PixelSums); empty where it adds nothing
+    using RayPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat || grad, ChannelPayload, NoPayload>>;
+    using SumPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat, ChannelPayload, NoPayload>>;
+};
+
+// The wait for the stage issued `younger` stages before the most recent one: vmcnt counts VMEM operations in issue
+// order, so vmcnt(younger * stage_ops) leaves the younger stages' DMAs in flight (any other younger VMEM operation only
+// makes the wait stricter)
 template <uint32_t N>
 __device__ GSRT_INLINE void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <bool SH, bool FEAT = false>
+template <class V>
 __device__ GSRT_INLINE void wait_stage(uint32_t younger) {
-    constexpr uint32_t P = kStagePieceOps<SH, FEAT>;
+    constexpr uint32_t P = V::stage_ops;
     if (younger >= 2) wait_vmcnt<2 * P>();
     else if (younger == 1) wait_vmcnt<P>();
     else wait_vmcnt<0>();
@@ -746,13 +780,12 @@ __device__ GSRT_INLINE uint32_t lds_read_settled(const uint32_t* p) {
 // issue the LDS-DMA of group g0 of ids[0..count) into dst: piece p < 4*kGroup is quarter p&3 of record p>>2,
 // the next 12*kGroup pieces are the SH rows (12 pieces each); piece p lands at byte 16 p of the stage. Every
 // lane computes its piece's address the same way (base, row stride and offset selected, no divergent paths).
-// Waited for by wait_stage before the stage is read. FEAT: sh is the feature table and a row is 4 pieces (64 B), so
+// Waited for by wait_stage before the stage is read. feat: sh is the feature table and a row is 4 pieces (64 B), so
 // the stage is 4 kGroup record pieces and 4 kGroup feature pieces, one DMA instruction.
-template <bool SH, bool FEAT = false>
+template <class V>
 __device__ GSRT_INLINE void stage_issue(const uint32_t* ids, uint32_t count, uint32_t g0, uint32_t lane, Stage* dst,
                                    const SplatRec* recs, const float* sh) {
-    constexpr uint32_t kRecPieces = 4 * kGroup, kPieces = kStagePieces<SH, FEAT>;
-    constexpr uint32_t kRowPieces = FEAT ? 4u : 12u;  // 16-B pieces of a row of sh
+    constexpr uint32_t kRecPieces = 4 * kGroup, kPieces = V::stage_pieces, kRowPieces = V::row_pieces;
 #pragma unroll
     for (uint32_t i = 0; i < (kPieces + 63) / 64; ++i) {
         const uint32_t p = i * 64 + lane;
@@ -760,7 +793,7 @@ __device__ GSRT_INLINE void stage_issue(const uint32_t* ids, uint32_t count, uin
         const uint32_t q = p - kRecPieces;
         uint32_t c = g0 + (is_rec ? p >> 2 : q / kRowPieces);
         c = c < count ? c : g0;  // past the list's end: a copy of candidate g0 (never read; keeps lane 0 active)
-        if (p < kPieces) {       // lane 0 always loads: each stage is exactly kStagePieceOps DMA instructions
+        if (p < kPieces) {       // lane 0 always loads: each stage is exactly stage_ops DMA instructions
             const uint32_t id = lds_read_settled(ids + c);
             const char* base = is_rec ? reinterpret_cast<const char*>(recs) : reinterpret_cast<const char*>(sh);
             const uint32_t stride = is_rec ? 64u : kRowPieces * 16u, off = is_rec ? (p & 3) * 16u : (q % kRowPieces) * 16u;
@@ -781,13 +814,13 @@ __device__ GSRT_INLINE void list_issue(uint32_t lt, uint32_t lane, uint32_t* ids
                                          (void*)hdr, 4, 0, 0);
 }
 
+template <class V>
 struct CorRay {
     ObjRay R;
     float pxs, pys;
     float bs[16];
     float T, C[3];
-    float D;  // DEPTH instantiations only: sum of z w over the blended hits (expected view depth, premultiplied)
-    float F[16];  // FEAT instantiations only (no bs there): sum of f_k w over the blended hits, per feature channel
+    typename V::RayPayload k;  // the kind's own: depth D, feat / grad F[16] (no bs there)
     bool active;
     uint32_t cand, blended, term;
 #ifdef GSRT_DIAG
@@ -866,67 +899,76 @@ __device__ GSRT_INLINE float grad_stage_sums(const float (&gs)[kGroup]) {
     const u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(u), __float_as_uint(v), false, false);
     return __uint_as_float(r.x) + __uint_as_float(r.y);
 }
-// GRAD: where a stage's gradient goes: the stage's candidate ids (ids + g0 of the round's list in LDS), the gradient
-// table's rows and the channel count. Empty in every other instantiation.
-struct GradOut {
-    const uint32_t* ids = nullptr;
-    float* rows = nullptr;
-    uint32_t channels = 0;
+// grad only: where a round's gradient goes (the gradient table's rows and the channel count), and one stage's share of
+// it: the stage's candidate ids (ids + g0 of the round's list in LDS), the candidates' row sums (blend_hit) and the mask
+// of the candidates some lane blended. The other kinds pass neither.
+struct GradDst { float* rows; uint32_t channels; };
+struct GradStage {
+    const uint32_t* ids;
+    GradDst dst;
+    float sums[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t mask = 0;  // bit c: some lane blended candidate c
 };
-// DEPTH: z is the candidate's view depth (SplatRec::depth); the blend's own w also weighs it into ray.D
-// FEAT: frow is the candidate's staged feature row (feat_row); w weighs its 16 floats into ray.F, and the colour
-// (1, as without SH) into C[0] alone: r = g = b, replicated once the ray is done (k_render_cor)
-// GRAD: ray.F holds the lane's upstream gradient G_c / ns (k_render_cor); the candidate's terms t_c = w G_c of the
-// blending lanes (+0, selected, on every other lane) are summed over each 16-lane row into *gsum (grad_row_sums), and
-// the colour is the feature frame's
-template <bool SH, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false, class ShSrc>
-__device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint64_t contrib, CorRay& ray, float z = 0.0f,
-                                          const float4* frow = nullptr, float* gsum = nullptr, bool* gany = nullptr) {
+template <class T>
+__device__ GSRT_INLINE T& only(T& t) { return t; }  // the one element of a pack that holds one
+// z: the candidate's view depth (SplatRec::depth), already in a register from shade_stage's read of the record (a read
+// of its own from the stage here measured 1.5 % on the depth kernel). depth: the blend's own w also weighs it into ray.k.D
+// feat: w weighs the 16 floats of the candidate's staged feature row (feat_row) into ray.k.F, and the colour (1, as
+// without SH) into C[0] alone: r = g = b, replicated once the ray is done (PixelSums::take)
+// grad: ray.k.F holds the lane's upstream gradient G_c / ns (k_render_cor); the candidate's terms t_c = w G_c of the
+// blending lanes (+0, selected, on every other lane) are summed over each 16-lane row into the stage's sums
+// (grad_row_sums), and the colour is the feature frame's. G: the stage's GradStage there, nothing elsewhere.
+template <class V, class... G>
+__device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z, float alpha, uint64_t contrib,
+                                          CorRay<V>& ray, G&... grad) {
+    static_assert(sizeof...(G) == (V::grad ? 1 : 0), "a gradient frame's stage, and only that");
     const float tn = ray.T * (1.0f - alpha);
     const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
     const uint64_t term = contrib & low;
     const uint64_t blend = contrib & ~low;  // the wave-uniform branch and the mask of the accumulate
     if (blend) {
         float col[3] = {1.0f, 1.0f, 1.0f};
-        if (SH) shsrc(ray.bs, col);
-        if constexpr (GRAD) {
+        if (V::sh) ShFromStage{stg, c}(ray.bs, col);
+        if constexpr (V::grad) {
             const float w = alpha * ray.T;  // the blend's own weight (T is updated below)
             const bool mine = lane_of(blend);
             float t[16];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) t[q] = mine ? w * ray.F[q] : 0.0f;  // a select: another lane's G never enters
-            *gsum = grad_row_sums(t);
-            *gany = true;  // wave-uniform: some lane blended this candidate
+            for (int q = 0; q < 16; ++q) t[q] = mine ? w * ray.k.F[q] : 0.0f;  // a select: another lane's G never enters
+            GradStage& gs = only(grad...);
+            gs.sums[c] = grad_row_sums(t);
+            gs.mask |= 1u << c;  // wave-uniform: some lane blended this candidate
         }
         if (lane_of(blend)) {
             const float w = alpha * ray.T;
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
-            if constexpr (!FEAT && !GRAD) {
+            if constexpr (!V::feat && !V::grad) {
                 ray.C[1] = fmaf(col[1], w, ray.C[1]);
                 ray.C[2] = fmaf(col[2], w, ray.C[2]);
             }
-            if constexpr (DEPTH) ray.D = fmaf(z, w, ray.D);
-            if constexpr (FEAT) {
+            if constexpr (V::depth) ray.k.D = fmaf(z, w, ray.k.D);
+            if constexpr (V::feat) {
                 // the row's address is wave-uniform: four broadcast ds_read_b128, under the lane mask (only the
                 // blending lanes use the values)
+                const float4* frow = feat_row(stg, c);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float4 f = frow[q];
-                    ray.F[4 * q + 0] = fmaf(f.x, w, ray.F[4 * q + 0]);
-                    ray.F[4 * q + 1] = fmaf(f.y, w, ray.F[4 * q + 1]);
-                    ray.F[4 * q + 2] = fmaf(f.z, w, ray.F[4 * q + 2]);
-                    ray.F[4 * q + 3] = fmaf(f.w, w, ray.F[4 * q + 3]);
+                    ray.k.F[4 * q + 0] = fmaf(f.x, w, ray.k.F[4 * q + 0]);
+                    ray.k.F[4 * q + 1] = fmaf(f.y, w, ray.k.F[4 * q + 1]);
+                    ray.k.F[4 * q + 2] = fmaf(f.z, w, ray.k.F[4 * q + 2]);
+                    ray.k.F[4 * q + 3] = fmaf(f.w, w, ray.k.F[4 * q + 3]);
                 }
             }
             ray.T = tn;
-            if (STATS) ++ray.blended;
+            if (V::stats) ++ray.blended;
         }
     }
     if (term) {  // wave-uniform: a ray stops once
         if (lane_of(term)) {
             ray.active = false;
             ray.pxs = __builtin_nanf("");  // every later g is NaN: the g-first test fails without an active flag
-            if (STATS) ++ray.term;
+            if (V::stats) ++ray.term;
         }
     }
     return term;
@@ -934,12 +976,12 @@ __device__ GSRT_INLINE uint64_t blend_hit(const ShSrc& shsrc, float alpha, uint6
 
 // Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
 // compile time (the steady state of shade_sorted), so no candidate is tested against m.
-// GRAD: the stage's terms w G go to the gradient table (go) in one atomic wave-instruction, lane 16 c + ch adding the
-// wave's sum for candidate c and channel ch, masked to the candidates some lane blended and to the channels in use.
-template <bool SH, bool LUT, bool STATS, bool FULL = false, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
-__device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay& ray,
-                                        const GradOut& go = GradOut{}) {
-    if (!STATS) {
+// grad: the stage's terms w G go to the gradient table (go.dst) in one atomic wave-instruction, lane 16 c + ch adding
+// the wave's sum for candidate c and channel ch, masked to the candidates some lane blended and to the channels in use.
+template <class V, bool FULL, class... G>
+__device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay<V>& ray, G... grad) {
+    constexpr bool LUT = V::lut;
+    if constexpr (!V::stats) {
         // Phase 1, g of all kGroup candidates at once (independent chains, one LDS wait): g first because lanes
         // that miss mostly fail it, and a candidate no lane passes is skipped with one wave-uniform branch.
         // g <= gcut = max(0, min(kGMax, ln(255 op) + 0.01)) drops only alphas <= 1/255: the result is
@@ -949,8 +991,6 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
         // okg[c] is the wave's lane mask of candidate c (a ballot: an SGPR pair, no VGPR flag per lane).
         float gv[kGroup];
         uint64_t okg[kGroup];
-        [[maybe_unused]] float gsums[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};  // GRAD: the candidates' row sums (blend_hit)
-        [[maybe_unused]] uint32_t gmask = 0;                           // GRAD: bit c: some lane blended candidate c
 #pragma unroll
         for (uint32_t c = 0; c < kGroup; ++c) {
             const float4 q2 = reinterpret_cast<const float4*>(&stg->rec[c])[2];  // ppx, ppy, A/2, B
@@ -970,7 +1010,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             if (!okg[c]) continue;
             float4 q0 = reinterpret_cast<const float4*>(&stg->rec[c])[0];  // lo or near, depth
             const float4 q1 = reinterpret_cast<const float4*>(&stg->rec[c])[1];  // hi or far, +-opacity
-            // q0.w (depth) is unused without DEPTH, but reading all 16 B keeps one ds_read_b128 (4 LDS-array cycles)
+            // q0.w (depth) is unused outside depth frames, but reading all 16 B keeps one ds_read_b128 (4 LDS-array cycles)
             // instead of a ds_read_b96 (8)
             asm volatile("" : "+v"(q0.w));
             // the slab test and exp run for the whole wave; a lane keeps alpha only if it passed both tests. The
@@ -995,60 +1035,58 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
-            [[maybe_unused]] bool gany = false;
-            const uint64_t stopped = blend_hit<SH, STATS, DEPTH, FEAT, GRAD>(ShFromStage{stg, c}, alpha, contrib, ray, q0.w,
-                                                                             FEAT ? feat_row(stg, c) : nullptr,
-                                                                             GRAD ? &gsums[c] : nullptr, GRAD ? &gany : nullptr);
-            if constexpr (GRAD) gmask |= gany ? 1u << c : 0u;
+            const uint64_t stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad...);
             if (stopped) {
 #pragma unroll
                 for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
             }
         }
-        if constexpr (GRAD) {
+        if constexpr (V::grad) {
+            const GradStage& go = only(grad...);
+            const uint32_t gmask = go.mask;
             if (gmask) {  // wave-uniform: a stage no lane blended adds nothing
-                const float sum = grad_stage_sums(gsums);
+                const float sum = grad_stage_sums(go.sums);
                 const uint32_t l = lane_here(), c = l >> 4, ch = l & 15u;
                 // a blended candidate c is below m, so ids[c] is an entry of the round's list: its id is below n and its
                 // row inside the table; channels from `channels` on (G holds +0 there) are left out
-                if (((gmask >> c) & 1u) && ch < go.channels) {
+                if (((gmask >> c) & 1u) && ch < go.dst.channels) {
                     const uint32_t id = lds_read_settled(go.ids + c);
 #if GSRT_GRAD_AB == 1  // timing only: the reduction without its atomic
                     asm volatile("" ::"v"(sum), "v"(id));
 #elif GSRT_GRAD_AB == 2  // counting: channel 0 counts the adds a row receives, channel 1 the wave-instructions
                     const float one = ch == 0 || c == (uint32_t)__builtin_ctz(gmask) ? 1.0f : 0.0f;
                     asm volatile("" ::"v"(sum));
-                    atomicAdd(go.rows + (size_t)id * 16u + ch, one);
+                    atomicAdd(go.dst.rows + (size_t)id * 16u + ch, one);
 #else
-                    atomicAdd(go.rows + (size_t)id * 16u + ch, sum);  // no-return global_atomic_add_f32
+                    atomicAdd(go.dst.rows + (size_t)id * 16u + ch, sum);  // no-return global_atomic_add_f32
 #endif
                 }
             }
         }
-        return;
-    }
-    for (uint32_t c = 0; c < m; ++c) {
-        // counting pass: every AABB candidate of every active ray is counted (no g-first skip)
-        const float4* r4 = reinterpret_cast<const float4*>(&stg->rec[c]);
-        float4 q0 = r4[0], q1 = r4[1], q2 = r4[2], q3 = r4[3];
-        asm volatile("" : "+v"(q1.w), "+v"(q2.x), "+v"(q2.y), "+v"(q2.z), "+v"(q2.w), "+v"(q3.x), "+v"(q3.z));
-        float alpha = 0.0f;
-        if (ray.active) {
-            const float lo[3] = {q0.x, q0.y, q0.z}, hi[3] = {q1.x, q1.y, q1.z};  // relative to the origin
-            if (slab_hit_rel(ray.R, lo, hi)) {
-                ++ray.cand;
-                const float dx = ray.pxs - q2.x, dy = ray.pys - q2.y;  // ppx, ppy
-                // A/2 = q2.z, B = q2.w, C/2 = q3.x: = 0.5 fma(C dy, dy, fma(2B dx, dy, (A dx) dx)) exactly
-                const float g = fmaf(q3.x * dy, dy, fmaf(q2.w * dx, dy, (q2.z * dx) * dx));
-                if (g >= 0.0f && g <= kGMax) {
-                    const float e = LUT ? linear_exp(lut_s, g) : exp_neg(-g);
-                    float a = fabsf(q1.w) * e;  // opacity (negated on a general-layout record, k_project)
-                    if (a > 0.99f) a = 0.99f;
-                    if (a > kAlphaMin) alpha = a;
+    } else {
+        for (uint32_t c = 0; c < m; ++c) {
+            // counting pass: every AABB candidate of every active ray is counted (no g-first skip)
+            const float4* r4 = reinterpret_cast<const float4*>(&stg->rec[c]);
+            float4 q0 = r4[0], q1 = r4[1], q2 = r4[2], q3 = r4[3];
+            asm volatile("" : "+v"(q1.w), "+v"(q2.x), "+v"(q2.y), "+v"(q2.z), "+v"(q2.w), "+v"(q3.x), "+v"(q3.z));
+            float alpha = 0.0f;
+            if (ray.active) {
+                const float lo[3] = {q0.x, q0.y, q0.z}, hi[3] = {q1.x, q1.y, q1.z};  // relative to the origin
+                if (slab_hit_rel(ray.R, lo, hi)) {
+                    ++ray.cand;
+                    const float dx = ray.pxs - q2.x, dy = ray.pys - q2.y;  // ppx, ppy
+                    // A/2 = q2.z, B = q2.w, C/2 = q3.x: = 0.5 fma(C dy, dy, fma(2B dx, dy, (A dx) dx)) exactly
+                    const float g = fmaf(q3.x * dy, dy, fmaf(q2.w * dx, dy, (q2.z * dx) * dx));
+                    if (g >= 0.0f && g <= kGMax) {
+                        const float e = LUT ? linear_exp(lut_s, g) : exp_neg(-g);
+                        float a = fabsf(q1.w) * e;  // opacity (negated on a general-layout record, k_project)
+                        if (a > 0.99f) a = 0.99f;
+                        if (a > kAlphaMin) alpha = a;
+                    }
                 }
             }
+            blend_hit<V>(stg, c, q0.w, alpha, __ballot(alpha > 0.0f), ray);
         }
-        blend_hit<SH, STATS>(ShFromStage{stg, c}, alpha, __ballot(alpha > 0.0f), ray);
     }
 }
 
@@ -1057,27 +1095,26 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
 // Three stage buffers: while stage k is shaded, the DMAs of stages k+1 and k+2 are in flight; wait_stage waits
 // for stage k's own DMA only. No DMA stays in flight past a return (the LDS is reused by the next round or by
 // the next workgroup).
-// GRAD: every shaded stage also adds its terms to the gradient table grows (shade_stage); its atomics are younger than
+// grad: every shaded stage also adds its terms to the gradient table gdst (shade_stage); its atomics are younger than
 // the DMAs the counted waits wait for, so those waits only become stricter, and the last wait covers them too.
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
+template <class V, class... G>
 __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, Stage* stA, Stage* stB, Stage* stC,
-                             const float* lut_s, CorRay& ray, const SplatRec* recs, const float* sh,
-                             float* grows = nullptr, uint32_t gchannels = 0) {
+                             const float* lut_s, CorRay<V>& ray, const SplatRec* recs, const float* sh, G... gdst) {
     const uint32_t lane = lane_id();
     count = __builtin_amdgcn_readfirstlane(count);  // wave-uniform: stage bounds as scalar compares
     if (count == 0) return __ballot(ray.active) != 0;
-    auto issue = [&](uint32_t g, Stage* dst) { stage_issue<SH, FEAT>(ids, count, g, lane, dst, recs, sh); };
+    auto issue = [&](uint32_t g, Stage* dst) { stage_issue<V>(ids, count, g, lane, dst, recs, sh); };
     auto shade = [&](Stage* stg, uint32_t g) {
         const uint32_t m = count - g < kGroup ? count - g : kGroup;
-        shade_stage<SH, LUT, STATS, false, DEPTH, FEAT, GRAD>(stg, m, lut_s, ray, GradOut{ids + g, grows, gchannels});
+        shade_stage<V, false>(stg, m, lut_s, ray, GradStage{ids + g, gdst}...);
     };
     auto shade_full = [&](Stage* stg, uint32_t g) {
-        shade_stage<SH, LUT, STATS, true, DEPTH, FEAT, GRAD>(stg, kGroup, lut_s, ray, GradOut{ids + g, grows, gchannels});
+        shade_stage<V, true>(stg, kGroup, lut_s, ray, GradStage{ids + g, gdst}...);
     };
-    constexpr uint32_t kWaitTwo = 2 * kStagePieceOps<SH, FEAT>;  // the two younger stages' DMAs stay in flight
+    constexpr uint32_t kWaitTwo = 2 * V::stage_ops;  // the two younger stages' DMAs stay in flight
     // stages issued after stage g's DMA when it is read: those of g + kGroup and g + 2 kGroup that exist
     auto wait = [count](uint32_t g) {
-        wait_stage<SH, FEAT>((g + kGroup < count ? 1u : 0u) + (g + 2 * kGroup < count ? 1u : 0u));
+        wait_stage<V>((g + kGroup < count ? 1u : 0u) + (g + 2 * kGroup < count ? 1u : 0u));
     };
     issue(0, stA);
     if (kGroup < count) issue(kGroup, stB);
@@ -1087,7 +1124,7 @@ __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, St
     // stage shaded here is full and has two younger stages in flight: unconditional issues, a constant wait, no
     // test against the list's end. It leaves the state the general loop below starts from (stage g0 in stA and, issued
     // after it, stage g0 + kGroup in stB), which shades the rest: at most four stages.
-    if (!STATS) {
+    if (!V::stats) {
         for (; g0 + 4 * kGroup < count; g0 += 3 * kGroup) {
             issue(g0 + 2 * kGroup, stC);
             wait_vmcnt<kWaitTwo>();
@@ -1566,36 +1603,218 @@ __global__ __launch_bounds__(64) void k_collect_cor(const KArgs karg) {
         K.a.list_hdr[lt] = make_uint4(cl.count | (cl.more ? 0x80000000u : 0u), cl.total, (uint32_t)last, (uint32_t)(last >> 32));
 }
 
-// waves/SIMD asked for the two FEAT kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
-// spill to scratch, DESIGN.md section 3)
-constexpr uint32_t kFeatWaves = 4;
-// and for the two GRAD kernels, likewise from the register report (96 VGPRs, no spill at 5 waves; at 6 the no-LUT kernel
-// spills 12 VGPRs to scratch and the LUT kernel stays at 96; 5 measured 4-5 % faster than 4: DESIGN.md section 3). A/B builds (make ab AB_FLAGS=...,
-// never the product library) set GSRT_GRAD_WAVES, or GSRT_GRAD_AB: 1 leaves the stage's atomic out (timing only), 2 makes
-// it count adds per row and wave-instructions instead of summing (profiles/feature_grad_cost.py); defaults at the top
-constexpr uint32_t kGradWaves = GSRT_GRAD_WAVES;
-// DEPTH (GSRT_FLAG_DEPTH, never with STATS): the frame also writes its expected view depth, sum of z w over each ray's
-// blended hits (z = SplatRec::depth, w = the blend's alpha T), combined over the samples as the colour is, to
-// RenderArgs::depth_out. Everything it adds sits under if constexpr: the other instantiations' code does not change.
-// FEAT (GSRT_FLAG_FEATURES, only as <false, LUT, false, false, true>): a feature frame. The stage carries each
-// candidate's 64-B feature row instead of SH rows, the blend weighs its 16 floats into ray.F, and the frame writes
-// feat_channels of them per pixel to RenderArgs::feat_out, combined over the samples as the colour is. Its RGBA is the
-// no-SH frame's (colour 1). Likewise all under if constexpr.
-// GRAD (GSRT_FLAG_FEATURE_GRAD, only as <false, LUT, false, false, false, true>): the backward of a feature frame to the
-// feature table. A lane holds its pixel's upstream gradient G[p, 0..C) / ns where a FEAT kernel holds ray.F; the stage
-// carries records only; for every blended hit the terms w G_c are summed over the wave and added to the Gaussian's row
-// of RenderArgs::grad_rows with float atomics (shade_stage). Its RGBA is the feature frame's. Likewise all under
-// if constexpr.
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
-// waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
-// at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
-// third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(
-    GRAD ? kGradWaves : FEAT ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6))))
+// The tile of a k_render_cor workgroup: wave-uniform values. tw, th and S are powers of two (make_plan): shifts instead
+// of divisions. The lane's pixel, its validity and the tile's rectangle are recomputed where they are used (ray setup,
+// rare continuation rounds, the store) from these and a laundered lane id, so that none of them lives (spilled) across
+// the shading loop.
+struct CorTile {
+    uint32_t lt;  // packed slot of the tile
+    uint32_t x0, y0, tw, th, S, lgS, lgtw, lgth;
+    struct Pixel { uint32_t in_tile, s, x, y; bool valid; };  // the lane's pixel, its sample within the pass, inside the frame
+    __device__ GSRT_INLINE Pixel pixel() const {
+        uint32_t l = lane_id();
+        asm volatile("" : "+v"(l));  // a fresh lane id: no live range across the shading loop
+        Pixel p;
+        p.in_tile = l >> lgS;
+        p.s = l & (S - 1u);
+        p.x = x0 + (p.in_tile & (tw - 1u));
+        p.y = y0 + (p.in_tile >> lgtw);
+        p.valid = p.x < kargs().a.width && p.y < kargs().a.height;
+        return p;
+    }
+    __device__ GSRT_INLINE TileRect rect_here() const {
+        uint32_t tx = x0 >> lgtw, ty = y0 >> lgth;
+        asm volatile("" : "+s"(tx), "+s"(ty));  // recomputed at the (rare) use, not hoisted and spilled
+        return tile_rect(tx, ty, tw, th);
+    }
+};
+
+// x summed over ns samples to their mean: x * (1 / ns) for a power of two (x / 2^k == x * 2^-k exactly), else x / ns
+__device__ GSRT_INLINE float over_samples(float x, uint32_t ns) {
+    const float nsf = (float)ns;
+    return (ns & (ns - 1)) == 0 ? x * (1.0f / nsf) : x / nsf;
+}
+
+// What a pixel outputs, summed over its samples: the colour and what the kind adds (depth: D, feat: 16 channels).
+// each visits every float in a fixed order (rgba, depth, channels 0..15), unrolled: nothing is indexed dynamically.
+template <class V>
+struct PixelSums {
+    float rgba[4];
+    typename V::SumPayload k;
+    template <class Op>
+    __device__ GSRT_INLINE void each(Op op) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) op(rgba[q]);
+        if constexpr (V::depth) op(k.D);
+        if constexpr (V::feat) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) op(k.F[q]);
+        }
+    }
+    // the floats beyond the colour with their entries in the frame's other image, pixel pix of a row-major frame (a depth
+    // or feature frame is never packed): depth_out, or feat_channels floats per pixel of feat_out, and only those
+    // (a uniform guard)
+    template <class Op>
+    __device__ GSRT_INLINE void each_extra_at(size_t pix, Op op) {
+        if constexpr (V::depth) op(k.D, kargs().a.depth_out + pix);
+        if constexpr (V::feat) {
+            const uint32_t C = kargs().a.feat_channels;
+            float* of = kargs().a.feat_out + pix * C;
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if ((uint32_t)q < C) op(k.F[q], of + q);
+        }
+    }
+    // every float with its entry in its own image; colour: the pixel's four floats
+    template <class Op>
+    __device__ GSRT_INLINE void each_at(float* colour, size_t pix, Op op) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) op(rgba[q], colour + q);
+        each_extra_at(pix, op);
+    }
+    // a finished pass's results (= 0 + x exactly, x >= +0). feat, grad: colour 1, the blend kept one channel (blend_hit)
+    __device__ GSRT_INLINE void take(const CorRay<V>& ray) {
+        constexpr bool grey = V::feat || V::grad;
+        rgba[0] = ray.C[0]; rgba[1] = ray.C[grey ? 0 : 1]; rgba[2] = ray.C[grey ? 0 : 2]; rgba[3] = 1.0f - ray.T;
+        if constexpr (V::depth) k.D = ray.k.D;
+        if constexpr (V::feat) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) k.F[q] = ray.k.F[q];
+        }
+    }
+};
+
+// The ray of the lane's pixel p and sample for one pass, nothing blended yet
+template <class V>
+__device__ GSRT_INLINE CorRay<V> cor_ray(const CorTile::Pixel& p, uint32_t S, uint32_t pass, uint32_t passes) {
+    CorRay<V> ray;
+    {
+        const KArgs& K = kargs();
+        // sample sidx takes draws 2*sidx, 2*sidx+1 of the pixel LCG seeded with Camera.RandomSeed
+        // (RayTracing.rgen:27,39: the same sequence for every pixel)
+        const uint32_t sidx = pass * S + p.s;
+        uint32_t seed = K.ubo.random_seed;
+        for (uint32_t q = 0; q < sidx; ++q) { random_float(&seed); random_float(&seed); }
+        const float jx = random_float(&seed);
+        const float jy = random_float(&seed);
+        ray.pxs = (float)p.x + jx;
+        ray.pys = (float)p.y + jy;
+        float o[3], d[3];
+        gen_ray(K.ubo, ray.pxs, ray.pys, o, d);
+        ray.R = make_obj_ray(d);
+        if (V::sh) sh_basis(d, ray.bs);
+    }
+    ray.T = 1.0f;
+    ray.C[0] = ray.C[1] = ray.C[2] = 0.0f;
+    if constexpr (V::depth) ray.k.D = 0.0f;
+    if constexpr (V::feat) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) ray.k.F[q] = 0.0f;
+    }
+    if constexpr (V::grad) {
+        // the pixel's upstream gradient, scaled once by 1 / ns as the forward store scales the sums; channels from
+        // grad_channels on and invalid lanes hold +0 (unrolled, a uniform guard: F is never indexed dynamically)
+        const KArgs& K = kargs();
+        const uint32_t C = K.a.grad_channels, ns = S * passes;
+        const float* gi = K.a.grad_in + ((size_t)p.y * K.a.width + p.x) * C;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) ray.k.F[q] = p.valid && (uint32_t)q < C ? over_samples(gi[q], ns) : 0.0f;
+    }
+    ray.active = p.valid;
+    if (!p.valid) ray.pxs = __builtin_nanf("");  // see blend_hit
+    ray.cand = ray.blended = ray.term = 0;
+#ifdef GSRT_DIAG
+    ray.dg_staged = ray.dg_gpass = ray.dg_contrib = ray.dg_blend = ray.dg_lanes_g = ray.dg_lanes_blend = 0;
+#endif
+    return ray;
+}
+
+// ---- the three sources of a round's candidates. Each leaves the round's ids, sorted front to back, in ids[0..count),
+// lo at the last key considered (the next round continues after it) and gpos where the tile resumes in its group's list.
+// The first round: the list k_group_list / k_collect_cor wrote, its header and first 128 ids already on their way into
+// LDS (list_issue) when prefetched
+__device__ GSRT_INLINE Collected round_from_list(const CorTile& t, bool& prefetched, uint32_t* ids, const uint32_t* lhdr,
+                                                 uint64_t& lo, uint32_t& gpos) {
+    Collected cl{};
+    if (!prefetched) list_issue(t.lt, lane_here(), ids, const_cast<uint32_t*>(lhdr));  // later passes: ids[] was reused
+    prefetched = false;
+    __syncthreads();  // vmcnt(0): header and ids[0..128) landed
+    const uint4 h = make_uint4(lhdr[0], lhdr[1], lhdr[2], lhdr[3]);
+    const uint32_t* src = kargs().a.lists + (size_t)t.lt * kCap;
+    cl.count = h.x & 0x7fffffffu;
+    cl.more = (h.x >> 31) != 0;
+    for (uint32_t i = 128u + lane_here(); i < cl.count; i += 64) ids[i] = src[i];
+    cl.total = cl.count;
+    lo = ((uint64_t)h.w << 32) | h.z;
+    gpos = h.y;
+    __syncthreads();
+    return cl;
+}
+// Continuation inside the group list: the next entries after gpos that meet this tile's footprint test, in order;
+// lo = the last entry considered. found: the list had entries left (else the tile traverses for itself)
+__device__ GSRT_INLINE Collected round_from_group(const CorTile& t, uint32_t* ids, uint64_t& lo, uint32_t& gpos, bool& found) {
+    Collected cl{};
+    const KArgs& K = kargs();
+    const uint32_t g = (t.y0 / t.th / K.a.fg) * K.a.groups_x + (t.x0 / t.tw / K.a.fg);
+    const uint4 gh = K.a.ghdr[g];
+    const uint32_t gcount = gh.x & 0x7fffffffu;
+    found = gpos < gcount;
+    if (!found) return cl;
+    const uint64_t* gl = K.a.glist + (size_t)g * kGStride;
+    const float4* fps = K.a.footprint;
+    const TileRect rect_c = t.rect_here();
+    uint32_t out = 0;
+    while (gpos < gcount && out < kCap) {
+        const uint32_t i = gpos + lane_here();
+        bool keep = false;
+        uint64_t key = 0;
+        if (i < gcount) {
+            key = gl[i];
+            keep = fp_meets(fps, (uint32_t)key, rect_c);
+        }
+        const uint64_t b = __ballot(keep);
+        const uint32_t rank = popc_below(b), n = (uint32_t)__popcll(b), room = kCap - out;
+        if (keep && rank < room) ids[out + rank] = (uint32_t)key;
+        if (n > room) {  // cut: resume after the last entry taken
+            const uint64_t kb = __ballot(keep && rank < room);
+            gpos += (uint32_t)(63 - __builtin_clzll(kb)) + 1u;
+            out = kCap;
+        } else {
+            gpos = gpos + 64u < gcount ? gpos + 64u : gcount;
+            out += n;
+        }
+    }
+    cl.count = cl.total = out;
+    cl.more = gpos < gcount || (gh.x >> 31) != 0;
+    lo = gl[gpos - 1];  // every group entry up to here was considered for this tile
+    __syncthreads();
+    return cl;
+}
+// The tile's own traversal for the keys after lo (no group list, or past the end of an overflowing one), the sorted
+// keys narrowed to ids
+template <class V>
+__device__ GSRT_INLINE Collected round_from_traversal(const CorTile& t, uint64_t* keys, uint32_t* stack, uint32_t* ids,
+                                                      uint64_t& lo, bool has_lo, uint32_t& restarts) {
+    const uint32_t lim = kargs().a.stack_limit < kRStack ? kargs().a.stack_limit : kRStack;
+    const Collected cl = collect_robust<kRCap, kRBuf>(t.rect_here(), lo, has_lo, keys, stack, KeyCorRec{}, restarts,
+                                                      !V::stats && kargs().a.cull2d, lim, FrontRegs{}, !V::stats);
+    lo = cl.count ? keys[cl.count - 1] : lo;
+    // narrow the sorted keys to ids in place (ids[i] overlays keys[i/2]: already read, in order)
+    const uint32_t ln = lane_here();
+    for (uint32_t base = 0; base < cl.count; base += 64) {
+        const uint32_t i = base + ln;
+        const uint32_t v = i < cl.count ? (uint32_t)keys[i] : 0u;
+        asm volatile("" ::: "memory");
+        if (i < cl.count) ids[i] = v;
+        asm volatile("" ::: "memory");
+    }
+    __syncthreads();
+    return cl;
+}
+
+template <class V>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(V::waves)))
 void k_render_cor(const KArgs karg) {
-    static_assert(!(DEPTH && STATS), "the counting pass has no depth output");
-    static_assert(!FEAT || (!SH && !STATS && !DEPTH), "a feature frame evaluates no SH, counts nothing, has no depth");
-    static_assert(!GRAD || (!SH && !STATS && !DEPTH && !FEAT), "a gradient frame is a feature frame without its table");
     // traversal buffers (keys, stack) and shading buffers (ids, two stages) are never live at once
     union CorLds {
         struct { uint64_t keys[kRBuf]; uint32_t stack[kRStack]; } t;
@@ -1603,20 +1822,20 @@ void k_render_cor(const KArgs karg) {
     };
     __shared__ CorLds L;
     __shared__ Stage stA, stB, stC;
-    __shared__ float lut_s[LUT ? 512 : 1];
+    __shared__ float lut_s[V::lut ? 512 : 1];
     uint64_t* const keys = L.t.keys;
     uint32_t* const stack = L.t.stack;
     uint32_t* const ids = L.l.ids;
     uint32_t* const lhdr = L.l.hdr;
     const SplatRec* const recs = kargs().a.recs;  // stage DMA sources, read once (kargs() is not hoisted)
-    const float* const shp = FEAT ? kargs().a.feat_rows : kargs().a.sh;
+    const float* const shp = V::feat ? kargs().a.feat_rows : kargs().a.sh;
     (void)karg;  // read through kargs()
     const uint32_t lane = lane_id();
 #ifdef GSRT_DIAG
     const unsigned long long diag_entry = __builtin_amdgcn_s_memtime();
     unsigned long long diag_setup = 0, diag_last = 0;
 #endif
-    if (LUT) {
+    if (V::lut) {
         const float* lut = kargs().a.lut;
         for (uint32_t i = lane; i < 512; i += 64) lut_s[i] = lut[i];
         __syncthreads();
@@ -1627,110 +1846,43 @@ void k_render_cor(const KArgs karg) {
     // an 8-rank C3 frame 28 % slower than the outer ones at equal counts: time also follows the continuation rounds'
     // traversals, the blending depth and the L2 hit rate of the region
     const uint32_t t_tile0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    // ---- tile and ray setup
-    uint32_t lt, x0, y0, tw, th, S, passes;
+    // ---- tile setup
+    CorTile tile;
+    uint32_t passes;
     {
         const KArgs& K = kargs();
         const uint32_t t = blockIdx.x;
         if (t >= K.a.ntiles_local) return;
-        lt = xcd_local_tile_perm(t, K.a.ntiles_local, K.a.run_order);  // packed slot of this tile
+        tile.lt = xcd_local_tile_perm(t, K.a.ntiles_local, K.a.run_order);
         uint32_t tx, ty;
-        band_tile(lt, K.a.row0, K.a.row1, K.a.tiles_x, tx, ty);
-        tw = K.a.tw; th = K.a.th; S = K.a.s_lanes; passes = K.a.passes;
-        x0 = tx * tw; y0 = ty * th;
+        band_tile(tile.lt, K.a.row0, K.a.row1, K.a.tiles_x, tx, ty);
+        tile.tw = K.a.tw; tile.th = K.a.th; tile.S = K.a.s_lanes; passes = K.a.passes;
+        tile.x0 = tx * tile.tw; tile.y0 = ty * tile.th;
     }
     // the first round's list (k_group_list / k_collect_cor wrote it): its header and first 128 ids go straight
     // into LDS (LDS-DMA: no VGPRs held across the setup), issued here so that their latency hides behind the
     // ray setup (the tile's list slot holds kCap entries, so the loads stay inside it whatever the count)
-    lt = __builtin_amdgcn_readfirstlane(lt);
+    tile.lt = __builtin_amdgcn_readfirstlane(tile.lt);
     bool prefetched = false;
     if (kargs().a.prelisted) {
-        list_issue(lt, lane, ids, lhdr);
+        list_issue(tile.lt, lane, ids, lhdr);
         prefetched = true;
     }
-    // tw, th and S are powers of two (make_plan): shifts instead of divisions. The lane's pixel, its validity
-    // and the tile's rectangle are recomputed where they are used (ray setup, rare continuation rounds, the
-    // store) from uniform values and a laundered lane id, so that none of them lives (spilled) across the loop.
-    x0 = __builtin_amdgcn_readfirstlane(x0);
-    y0 = __builtin_amdgcn_readfirstlane(y0);
-    const uint32_t lgS = (uint32_t)__builtin_ctz(S), lgtw = (uint32_t)__builtin_ctz(tw), lgth = (uint32_t)__builtin_ctz(th);
-    auto pixel = [&](uint32_t& pit, uint32_t& si, uint32_t& qx, uint32_t& qy, bool& ok) {
-        uint32_t l = lane_id();
-        asm volatile("" : "+v"(l));  // a fresh lane id: no live range across the shading loop
-        pit = l >> lgS;
-        si = l & (S - 1u);
-        qx = x0 + (pit & (tw - 1u));
-        qy = y0 + (pit >> lgtw);
-        ok = qx < kargs().a.width && qy < kargs().a.height;
-    };
-    auto tile_rect_here = [&]() {
-        uint32_t tx = x0 >> lgtw, ty = y0 >> lgth;
-        asm volatile("" : "+s"(tx), "+s"(ty));  // recomputed at the (rare) use, not hoisted and spilled
-        return tile_rect(tx, ty, tw, th);
-    };
-    uint32_t pix_in_tile, s_in, px, py;
-    bool valid;
-    pixel(pix_in_tile, s_in, px, py, valid);
-    // the pixel's sum over its samples: with one pass (spp <= 64) the pass's own values; with several passes
-    // (spp > 64: one pixel per lane) the framebuffer entry holds the running sum between passes, so that no
-    // accumulator lives (spilled) across the shading loop. The sums are formed in the same order either way.
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    [[maybe_unused]] float acc_d = 0.0f;  // DEPTH: the depth's sum, carried beside acc
-    [[maybe_unused]] float acc_f[16];     // FEAT: the channels' sums, likewise (set after every pass)
+    tile.x0 = __builtin_amdgcn_readfirstlane(tile.x0);
+    tile.y0 = __builtin_amdgcn_readfirstlane(tile.y0);
+    tile.lgS = (uint32_t)__builtin_ctz(tile.S);
+    tile.lgtw = (uint32_t)__builtin_ctz(tile.tw); tile.lgth = (uint32_t)__builtin_ctz(tile.th);
+    const uint32_t S = tile.S;
+    // the pixel's sums over its samples: with one pass (spp <= 64) the pass's own values; with several passes
+    // (spp > 64: one pixel per lane) the pixel's entries in the output images hold the running sums between passes, so
+    // that no accumulator lives (spilled) across the shading loop. The sums are formed in the same order either way.
+    PixelSums<V> sums{};
     uint32_t st_cand = 0, st_blend = 0, st_term = 0, st_rounds = 0, restarts = 0, maxc = 0;
 #ifdef GSRT_DIAG  // diagnostic build only: per-wave cycle split between traversal+sort and shading
     unsigned long long diag_collect = 0, diag_shade = 0;
 #endif
     for (uint32_t pass = 0; pass < passes; ++pass) {
-        CorRay ray;
-        pixel(pix_in_tile, s_in, px, py, valid);  // recomputed per pass (see pixel)
-        {
-            const KArgs& K = kargs();
-            // sample sidx takes draws 2*sidx, 2*sidx+1 of the pixel LCG seeded with Camera.RandomSeed
-            // (RayTracing.rgen:27,39: the same sequence for every pixel)
-            const uint32_t sidx = pass * S + s_in;
-            uint32_t seed = K.ubo.random_seed;
-            for (uint32_t q = 0; q < sidx; ++q) { random_float(&seed); random_float(&seed); }
-            const float jx = random_float(&seed);
-            const float jy = random_float(&seed);
-            ray.pxs = (float)px + jx;
-            ray.pys = (float)py + jy;
-            float o[3], d[3];
-            gen_ray(K.ubo, ray.pxs, ray.pys, o, d);
-            ray.R = make_obj_ray(d);
-            if (SH) sh_basis(d, ray.bs);
-        }
-        ray.T = 1.0f;
-        ray.C[0] = ray.C[1] = ray.C[2] = 0.0f;
-        if constexpr (DEPTH) ray.D = 0.0f;
-        if constexpr (FEAT) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) ray.F[q] = 0.0f;
-        }
-        if constexpr (GRAD) {
-            // the pixel's upstream gradient, scaled once by 1 / ns as the forward store scales the sums; channels from
-            // grad_channels on and invalid lanes hold +0 (unrolled, a uniform guard: ray.F is never indexed dynamically)
-            const KArgs& K = kargs();
-            const uint32_t C = K.a.grad_channels, nsg = S * passes;
-            const bool pow2 = (nsg & (nsg - 1)) == 0;
-            const float nsf = (float)nsg, r = 1.0f / nsf;
-            const float* gi = K.a.grad_in + ((size_t)py * K.a.width + px) * C;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                float v = 0.0f;
-                if (valid && (uint32_t)q < C) {
-                    v = gi[q];
-                    v = pow2 ? v * r : v / nsf;
-                }
-                ray.F[q] = v;
-            }
-        }
-        ray.active = valid;
-        if (!valid) ray.pxs = __builtin_nanf("");  // see blend_hit
-        ray.cand = ray.blended = ray.term = 0;
-#ifdef GSRT_DIAG
-        ray.dg_staged = ray.dg_gpass = ray.dg_contrib = ray.dg_blend = ray.dg_lanes_g = ray.dg_lanes_blend = 0;
-#endif
+        CorRay<V> ray = cor_ray<V>(tile.pixel(), S, pass, passes);
         uint64_t lo = 0;
         bool has_lo = false;
         uint32_t gpos = 0;  // with group lists: where this tile resumes in its group's sorted list
@@ -1740,81 +1892,14 @@ void k_render_cor(const KArgs karg) {
             if (!has_lo) diag_setup += d0 - (pass == 0 ? diag_entry : diag_last);
 #endif
             Collected cl;
-            bool listed = false;
-            {
-                const KArgs& K = kargs();
-                if (K.a.prelisted && !has_lo) {  // first round: the list k_group_list / k_collect_cor wrote
-                    if (!prefetched) list_issue(lt, lane_here(), ids, lhdr);  // later passes: ids[] was reused
-                    prefetched = false;
-                    __syncthreads();  // vmcnt(0): header and ids[0..128) landed
-                    const uint4 h = make_uint4(lhdr[0], lhdr[1], lhdr[2], lhdr[3]);
-                    const uint32_t* src = K.a.lists + (size_t)lt * kCap;
-                    cl.count = h.x & 0x7fffffffu;
-                    cl.more = (h.x >> 31) != 0;
-                    for (uint32_t i = 128u + lane_here(); i < cl.count; i += 64) ids[i] = src[i];
-                    cl.total = cl.count;
-                    cl.restart = false;
-                    lo = ((uint64_t)h.w << 32) | h.z;
-                    gpos = h.y;
-                    listed = true;
-                    __syncthreads();
-                } else if (K.a.use_groups) {
-                    // continuation inside the group list: the next entries after gpos that meet this tile's
-                    // footprint test, in order; lo = the last entry considered
-                    const uint32_t g = (y0 / th / K.a.fg) * K.a.groups_x + (x0 / tw / K.a.fg);
-                    const uint4 gh = K.a.ghdr[g];
-                    const uint32_t gcount = gh.x & 0x7fffffffu;
-                    if (gpos < gcount) {
-                        const uint64_t* gl = K.a.glist + (size_t)g * kGStride;
-                        const float4* fps = K.a.footprint;
-                        const TileRect rect_c = tile_rect_here();
-                        uint32_t out = 0;
-                        while (gpos < gcount && out < kCap) {
-                            const uint32_t i = gpos + lane_here();
-                            bool keep = false;
-                            uint64_t key = 0;
-                            if (i < gcount) {
-                                key = gl[i];
-                                keep = fp_meets(fps, (uint32_t)key, rect_c);
-                            }
-                            const uint64_t b = __ballot(keep);
-                            const uint32_t rank = popc_below(b), n = (uint32_t)__popcll(b), room = kCap - out;
-                            if (keep && rank < room) ids[out + rank] = (uint32_t)key;
-                            if (n > room) {  // cut: resume after the last entry taken
-                                const uint64_t kb = __ballot(keep && rank < room);
-                                gpos += (uint32_t)(63 - __builtin_clzll(kb)) + 1u;
-                                out = kCap;
-                            } else {
-                                gpos = gpos + 64u < gcount ? gpos + 64u : gcount;
-                                out += n;
-                            }
-                        }
-                        cl.count = out;
-                        cl.total = out;
-                        cl.restart = false;
-                        cl.more = gpos < gcount || (gh.x >> 31) != 0;
-                        lo = gl[gpos - 1];  // every group entry up to here was considered for this tile
-                        listed = true;
-                        __syncthreads();
-                    }
-                }
+            bool listed = true;
+            if (kargs().a.prelisted && !has_lo) {
+                cl = round_from_list(tile, prefetched, ids, lhdr, lo, gpos);
+            } else {
+                listed = false;
+                if (kargs().a.use_groups) cl = round_from_group(tile, ids, lo, gpos, listed);
             }
-            if (!listed) {  // traverse for the keys after lo (no group list, or past the end of an overflowing one)
-                const uint32_t lim = kargs().a.stack_limit < kRStack ? kargs().a.stack_limit : kRStack;
-                cl = collect_robust<kRCap, kRBuf>(tile_rect_here(), lo, has_lo, keys, stack, KeyCorRec{}, restarts,
-                                                  !STATS && kargs().a.cull2d, lim, FrontRegs{}, !STATS);
-                lo = cl.count ? keys[cl.count - 1] : lo;
-                // narrow the sorted keys to ids in place (ids[i] overlays keys[i/2]: already read, in order)
-                const uint32_t ln = lane_here();
-                for (uint32_t base = 0; base < cl.count; base += 64) {
-                    const uint32_t i = base + ln;
-                    const uint32_t v = i < cl.count ? (uint32_t)keys[i] : 0u;
-                    asm volatile("" ::: "memory");
-                    if (i < cl.count) ids[i] = v;
-                    asm volatile("" ::: "memory");
-                }
-                __syncthreads();
-            }
+            if (!listed) cl = round_from_traversal<V>(tile, keys, stack, ids, lo, has_lo, restarts);
 #ifdef GSRT_DIAG
             const unsigned long long d1 = __builtin_amdgcn_s_memtime();
             diag_collect += d1 - d0;
@@ -1822,11 +1907,11 @@ void k_render_cor(const KArgs karg) {
             ++st_rounds;
             if (cl.total > maxc) maxc = cl.total;
             bool live;
-            if constexpr (GRAD)
-                live = shade_sorted<SH, LUT, STATS, DEPTH, FEAT, GRAD>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
-                                                                       kargs().a.grad_rows, kargs().a.grad_channels);
+            if constexpr (V::grad)
+                live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
+                                       GradDst{kargs().a.grad_rows, kargs().a.grad_channels});
             else
-                live = shade_sorted<SH, LUT, STATS, DEPTH, FEAT>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
+                live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
 #ifdef GSRT_DIAG
             diag_last = __builtin_amdgcn_s_memtime();
             diag_shade += diag_last - d1;
@@ -1835,117 +1920,44 @@ void k_render_cor(const KArgs karg) {
             has_lo = true;  // lo = the last (largest) key of this round
             __syncthreads();
         }
-        if constexpr (FEAT || GRAD) ray.C[1] = ray.C[2] = ray.C[0];  // colour 1: the blend kept one channel (blend_hit)
-        acc[0] = ray.C[0]; acc[1] = ray.C[1]; acc[2] = ray.C[2]; acc[3] = 1.0f - ray.T;  // = 0 + x exactly (x >= +0)
-        if (passes > 1) {  // then S == 1 (make_plan): the lane's pixel accumulates its passes in order
-            pixel(pix_in_tile, s_in, px, py, valid);
-            if (valid) {
+        sums.take(ray);
+        if (passes > 1) {  // then S == 1 (make_plan): the lane's pixel accumulates its passes in order, prev + pass
+            const CorTile::Pixel p = tile.pixel();
+            if (p.valid) {
                 const KArgs& K = kargs();
+                const size_t pix = (size_t)p.y * K.a.width + p.x;
                 float4* o = (K.a.dump8 ? K.a.accum : reinterpret_cast<float4*>(K.a.out)) +
-                            (K.a.packed ? (size_t)lt * (tw * th) + pix_in_tile : (size_t)py * K.a.width + px);
-                if (pass > 0) {
-                    const float4 prev = *o;
-                    acc[0] = prev.x + acc[0]; acc[1] = prev.y + acc[1]; acc[2] = prev.z + acc[2]; acc[3] = prev.w + acc[3];
-                }
-                if (pass + 1 < passes) *o = make_float4(acc[0], acc[1], acc[2], acc[3]);
-            }
-        }
-        if constexpr (DEPTH) {
-            acc_d = ray.D;
-            if (passes > 1) {  // as the colour above: the depth image's own entry holds the running sum between passes
-                pixel(pix_in_tile, s_in, px, py, valid);
-                if (valid) {
-                    float* od = kargs().a.depth_out + ((size_t)py * kargs().a.width + px);
-                    if (pass > 0) acc_d = *od + acc_d;
-                    if (pass + 1 < passes) *od = acc_d;
-                }
-            }
-        }
-        if constexpr (FEAT) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc_f[q] = ray.F[q];
-            if (passes > 1) {  // as the colour above: the feature image's own entry holds the running sums between passes
-                pixel(pix_in_tile, s_in, px, py, valid);
-                if (valid) {
-                    const uint32_t C = kargs().a.feat_channels;
-                    float* of = kargs().a.feat_out + ((size_t)py * kargs().a.width + px) * C;
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {  // unrolled, a uniform guard: acc_f is never indexed dynamically
-                        if ((uint32_t)q < C) {
-                            if (pass > 0) acc_f[q] = of[q] + acc_f[q];
-                            if (pass + 1 < passes) of[q] = acc_f[q];
-                        }
-                    }
-                }
+                            (K.a.packed ? (size_t)tile.lt * (tile.tw * tile.th) + p.in_tile : pix);
+                if (pass > 0) sums.each_at(&o->x, pix, [](float& v, const float* home) { v = *home + v; });
+                if (pass + 1 < passes) sums.each_at(&o->x, pix, [](float v, float* home) { *home = v; });
             }
         }
         st_cand += ray.cand; st_blend += ray.blended; st_term += ray.term;
 #ifdef GSRT_DIAG
-        if (!STATS && lane == 0) {
-            unsigned long long* dc = kargs().a.counters + 16;
-            atomicAdd(dc + 0, (unsigned long long)ray.dg_staged);
-            atomicAdd(dc + 1, (unsigned long long)ray.dg_gpass);
-            atomicAdd(dc + 2, (unsigned long long)ray.dg_contrib);
-            atomicAdd(dc + 3, (unsigned long long)ray.dg_blend);
-            atomicAdd(dc + 4, (unsigned long long)ray.dg_lanes_g);
-            atomicAdd(dc + 5, (unsigned long long)ray.dg_lanes_blend);
-
+        if (!V::stats && lane == 0) {
+            const uint32_t dg[6] = {ray.dg_staged, ray.dg_gpass, ray.dg_contrib, ray.dg_blend, ray.dg_lanes_g, ray.dg_lanes_blend};
+            for (int q = 0; q < 6; ++q) atomicAdd(kargs().a.counters + 16 + q, (unsigned long long)dg[q]);
         }
 #endif
     }
     // pairwise reduction over the S in-wave samples of a pixel (the oracle sums in the same tree); partners 1 and
     // 2 lanes away by DPP quad permutes (no LDS round trip), farther ones by shuffles
-    if (S > 1) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            acc[q] = acc[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[q]), 0xB1, 0xF, 0xF, false));
-        if constexpr (DEPTH)
-            acc_d = acc_d + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_d), 0xB1, 0xF, 0xF, false));
-        if constexpr (FEAT) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                acc_f[q] = acc_f[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_f[q]), 0xB1, 0xF, 0xF, false));
-        }
-    }
-    if (S > 2) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            acc[q] = acc[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[q]), 0x4E, 0xF, 0xF, false));
-        if constexpr (DEPTH)
-            acc_d = acc_d + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_d), 0x4E, 0xF, 0xF, false));
-        if constexpr (FEAT) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                acc_f[q] = acc_f[q] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc_f[q]), 0x4E, 0xF, 0xF, false));
-        }
-    }
-    for (uint32_t off = 4; off < S; off <<= 1) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = acc[q] + __shfl_xor(acc[q], (int)off);
-        if constexpr (DEPTH) acc_d = acc_d + __shfl_xor(acc_d, (int)off);
-        if constexpr (FEAT) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc_f[q] = acc_f[q] + __shfl_xor(acc_f[q], (int)off);
-        }
-    }
-    for (uint32_t off = 1; STATS && off < S; off <<= 1) {
+    if (S > 1) sums.each([](float& v) { v = v + dpp_from<0xB1>(v); });
+    if (S > 2) sums.each([](float& v) { v = v + dpp_from<0x4E>(v); });
+    for (uint32_t off = 4; off < S; off <<= 1) sums.each([off](float& v) { v = v + __shfl_xor(v, (int)off); });
+    for (uint32_t off = 1; V::stats && off < S; off <<= 1) {
         st_cand += __shfl_xor(st_cand, (int)off);
         st_blend += __shfl_xor(st_blend, (int)off);
         st_term += __shfl_xor(st_term, (int)off);
     }
     const KArgs& K = kargs();
     const uint32_t ns = S * passes;
-    const float nsamp = (float)ns;
-    pixel(pix_in_tile, s_in, px, py, valid);
-    if (valid && s_in == 0) {
-        float4 v;
-        if ((ns & (ns - 1)) == 0) {  // x / 2^k == x * 2^-k exactly
-            const float r = 1.0f / nsamp;
-            v = make_float4(acc[0] * r, acc[1] * r, acc[2] * r, acc[3] * r);
-        } else {
-            v = make_float4(acc[0] / nsamp, acc[1] / nsamp, acc[2] / nsamp, acc[3] / nsamp);
-        }
-        const size_t idx = K.a.packed ? (size_t)lt * (tw * th) + pix_in_tile : (size_t)py * K.a.width + px;
+    const CorTile::Pixel p = tile.pixel();
+    if (p.valid && p.s == 0) {
+        sums.each([ns](float& v) { v = over_samples(v, ns); });
+        const float4 v = make_float4(sums.rgba[0], sums.rgba[1], sums.rgba[2], sums.rgba[3]);
+        const size_t pix = (size_t)p.y * K.a.width + p.x;
+        const size_t idx = K.a.packed ? (size_t)tile.lt * (tile.tw * tile.th) + p.in_tile : pix;
         if (K.a.dump8) {  // the integers the frame dump prints (Dump8), exact values of the rest in the escape list
             const uint32_t code = dump8_code(v);
             reinterpret_cast<uint32_t*>(K.a.out)[idx] = code;
@@ -1957,19 +1969,9 @@ void k_render_cor(const KArgs karg) {
         } else {
             reinterpret_cast<float4*>(K.a.out)[idx] = v;
         }
-        if constexpr (DEPTH)  // row-major whatever the colour's layout (a depth frame is never packed)
-            K.a.depth_out[(size_t)py * K.a.width + px] = (ns & (ns - 1)) == 0 ? acc_d * (1.0f / nsamp) : acc_d / nsamp;
-        if constexpr (FEAT) {  // feat_channels floats per pixel, and only those
-            const uint32_t C = K.a.feat_channels;
-            float* of = K.a.feat_out + ((size_t)py * K.a.width + px) * C;
-            const bool pow2 = (ns & (ns - 1)) == 0;
-            const float r = 1.0f / nsamp;
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if ((uint32_t)q < C) of[q] = pow2 ? acc_f[q] * r : acc_f[q] / nsamp;
-        }
-        if (STATS && K.a.ray_stats)
-            reinterpret_cast<uint4*>(K.a.ray_stats)[(size_t)py * K.a.width + px] = make_uint4(st_cand, st_blend, st_rounds, st_term);
+        sums.each_extra_at(pix, [](float x, float* home) { *home = x; });
+        if (V::stats && K.a.ray_stats)
+            reinterpret_cast<uint4*>(K.a.ray_stats)[pix] = make_uint4(st_cand, st_blend, st_rounds, st_term);
     }
 #ifdef GSRT_DIAG
     if (lane == 0) {
@@ -1983,13 +1985,13 @@ void k_render_cor(const KArgs karg) {
 #endif
     // the partition's cost profile: one store per tile (device-scope atomics on a few row words serialise at the
     // memory side and slowed the frame by several percent)
-    if (K.a.tile_cost && lane == 0) K.a.tile_cost[lt] = (uint32_t)__builtin_amdgcn_s_memrealtime() - t_tile0;
-    if (STATS) {
-        const uint32_t lead = (valid && s_in == 0) ? 1u : 0u;
-        add_counters(wave_sum(valid ? 1u : 0u) * passes, wave_sum(lead ? st_cand : 0u), wave_sum(lead ? st_blend : 0u),
+    if (K.a.tile_cost && lane == 0) K.a.tile_cost[tile.lt] = (uint32_t)__builtin_amdgcn_s_memrealtime() - t_tile0;
+    if (V::stats) {
+        const uint32_t lead = (p.valid && p.s == 0) ? 1u : 0u;
+        add_counters(wave_sum(p.valid ? 1u : 0u) * passes, wave_sum(lead ? st_cand : 0u), wave_sum(lead ? st_blend : 0u),
                      wave_sum(lead ? st_term : 0u), st_rounds, restarts, maxc);
     }
-    GSRT_WT_END(0, lt);
+    GSRT_WT_END(0, tile.lt);
 }
 
 // ----------------------------------------------------------------------------------------- REF
@@ -2271,9 +2273,9 @@ static bool debug_no_leaf_fp() {
     return e && e[0] == '1';
 }
 
-template <bool SH, bool LUT, bool STATS, bool DEPTH = false, bool FEAT = false, bool GRAD = false>
+template <class V>
 static void launch_cor_t(hipStream_t st, const KArgs& k) {
-    hipLaunchKernelGGL((k_render_cor<SH, LUT, STATS, DEPTH, FEAT, GRAD>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
+    hipLaunchKernelGGL((k_render_cor<V>), dim3(k.a.ntiles_local), dim3(64), 0, st, k);
 }
 
 // A rank of a sharded frame projects in sorted-leaf chunks (k_prep_cor) from this many ranks on: most 64-leaf chunks
@@ -2753,29 +2755,22 @@ static gsrt_status launch_ref(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderP
 
 // The k_render_cor instantiation of a frame: every one the library holds is named here and nowhere else. Feature and
 // gradient frames blend no SH whatever the scene holds (never with stats or depth, gsrt_api.cpp check_render_args).
-enum class CorKind { plain, stats, depth, feat, grad };
 using CorLaunch = void (*)(hipStream_t, const KArgs&);
+template <CorKind K>
+static CorLaunch cor_kernel_of(bool sh, bool lut) {
+    if constexpr (K == CorKind::feat || K == CorKind::grad)
+        return lut ? launch_cor_t<CorVariant<K, false, true>> : launch_cor_t<CorVariant<K, false, false>>;
+    else
+        return sh ? (lut ? launch_cor_t<CorVariant<K, true, true>> : launch_cor_t<CorVariant<K, true, false>>)
+                  : (lut ? launch_cor_t<CorVariant<K, false, true>> : launch_cor_t<CorVariant<K, false, false>>);
+}
 static CorLaunch cor_kernel(CorKind kind, bool sh, bool lut) {
-    // rows: the scene's SH, none; columns: the ExpLUT, the exact exponential (the order the code object holds them in)
-    static const CorLaunch colour[2][2][2] = {  // {counting pass, plain}
-        {{launch_cor_t<true, true, true>, launch_cor_t<true, true, false>},
-         {launch_cor_t<true, false, true>, launch_cor_t<true, false, false>}},
-        {{launch_cor_t<false, true, true>, launch_cor_t<false, true, false>},
-         {launch_cor_t<false, false, true>, launch_cor_t<false, false, false>}}};
-    static const CorLaunch with_depth[2][2] = {
-        {launch_cor_t<true, true, false, true>, launch_cor_t<true, false, false, true>},
-        {launch_cor_t<false, true, false, true>, launch_cor_t<false, false, false, true>}};
-    static const CorLaunch features[2] = {launch_cor_t<false, true, false, false, true>,
-                                          launch_cor_t<false, false, false, false, true>};
-    static const CorLaunch gradients[2] = {launch_cor_t<false, true, false, false, false, true>,
-                                           launch_cor_t<false, false, false, false, false, true>};
-    const uint32_t row = sh ? 0 : 1, col = lut ? 0 : 1;
     switch (kind) {
-        case CorKind::plain: return colour[row][col][1];
-        case CorKind::stats: return colour[row][col][0];
-        case CorKind::depth: return with_depth[row][col];
-        case CorKind::feat: return features[col];
-        case CorKind::grad: return gradients[col];
+        case CorKind::plain: return cor_kernel_of<CorKind::plain>(sh, lut);
+        case CorKind::stats: return cor_kernel_of<CorKind::stats>(sh, lut);
+        case CorKind::depth: return cor_kernel_of<CorKind::depth>(sh, lut);
+        case CorKind::feat: return cor_kernel_of<CorKind::feat>(sh, lut);
+        case CorKind::grad: return cor_kernel_of<CorKind::grad>(sh, lut);
     }
     return nullptr;
 }

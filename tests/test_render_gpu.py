@@ -114,6 +114,34 @@ def test_stats_match_oracle(ctx):
     assert st["candidates"] == int(want[..., 0].sum()) and st["blended"] == int(want[..., 1].sum())
 
 
+@pytest.mark.parametrize("spp", [1, 4, 3])
+@pytest.mark.parametrize("with_sh", [False, True])
+def test_stats_with_lut_match_oracle(ctx, with_sh, spp):
+    """The counting pass with the ExpLUT (the two stats x LUT instantiations of k_render_cor), with and without SH rows:
+    300 Gaussians in the plane z = -4 whose boxes cover an 18x18 frame (ragged tiles), in-wave samples (1, 4 spp) and
+    passes (3 spp). Every ray counts more than kCap = 256 candidates, so continuation rounds run. Frame and per-ray
+    counts are the oracle's, bit for bit."""
+    k = 300
+    c = np.zeros((k, 3), np.float32)
+    c[:, 2] = -4.0
+    r = np.tile(np.asarray((1.0, 0.0, 0.0, 0.0), np.float32), (k, 1))
+    sh = gsrt.synth_cloud(gsrt.SYNTH_COR, k, 3, True)[4][:k] if with_sh else None
+    sc = gsrt.Scene.from_model(ctx, c, r, np.full((k, 3), 6.0, np.float32), np.full(k, 0.02, np.float32), sh)
+    sc.build_bvh()
+    p, a = sc.download()
+    mv = gsrt.lookat((0, 0, 0), (0, 0, -1))
+    rgba, _ = sc.render(gsrt.camera_from_modelview(mv, 60.0, 18, 18, 1.0, spp, 16),
+                        gsrt.MODE_COR | gsrt.FLAG_STATS | gsrt.FLAG_LUT)
+    st = ctx.last_stats((18, 18))
+    ref = O.render(p, a, O.make_ubo(mv, 60.0, 18, 18, 1.0, spp, 16), O.MODE_COR | O.FLAG_LUT, sh=sh, bvh=O.Bvh(a),
+                   want_stats=True)
+    want = ref["stats"]
+    assert want[..., 0].min() > 256 * spp and want[..., 1].min() > 256 * spp
+    assert rgba.tobytes() == ref["rgba"].tobytes()
+    for col in (0, 1, 3):
+        np.testing.assert_array_equal(st["per_ray"][..., col], want[..., col])
+
+
 # ------------------------------------------------------------------------- golden fixtures (pinned bytes)
 
 GOLD = __import__("os").path.join(__import__("os").path.dirname(__import__("os").path.abspath(__file__)), "golden")
