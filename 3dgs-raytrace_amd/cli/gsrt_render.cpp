@@ -19,7 +19,11 @@
 // C outside 1..16, one option of the pair without the other), --feature-grad FILE --feature-channels C
 // --feature-grad-out FILE (COR: a gradient frame, gsrt_render_feature_grad: the upstream gradient of a feature image, raw
 // float32 W*H*C, in; the gradient of the feature table, raw float32 n*C, out; no image is dumped; usage errors: --mode ref
-// or a REF-default scene, --stats, --depth, --features, C outside 1..16, one option without the others).
+// or a REF-default scene, --stats, --depth, --features, C outside 1..16, one option without the others),
+// --sh-grad FILE --sh-grad-out FILE (COR, a scene with SH rows: an SH gradient frame, gsrt_render_sh_grad: the upstream
+// gradient of the RGBA frame, raw float32 W*H*4, in; the gradient of the SH table, raw float32 n*48 laid out
+// [gauss][coef][rgb], out; no image is dumped; usage errors: --mode ref or a REF-default scene, --stats, --depth,
+// --features, --feature-grad, one option without the other).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +46,7 @@ struct Options {
     int device = 0;
     float fov = 0.0f;  // 0: scene default
     std::string camera, out, binary, text, ply, depth, features, features_out, feature_grad, feature_grad_out;
+    std::string sh_grad, sh_grad_out;
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
 };
@@ -54,7 +59,8 @@ struct Options {
                  "                   [--sh] [--camera FILE] [--fov DEG] [--out PPM] [--binary FILE] [--no-dump]\n"
                  "                   [--text FILE] [--ply FILE] [--device D] [--frames F] [--stats]\n"
                  "                   [--depth PFM] [--features FILE --feature-channels C --features-out FILE]\n"
-                 "                   [--feature-grad FILE --feature-channels C --feature-grad-out FILE]\n");
+                 "                   [--feature-grad FILE --feature-channels C --feature-grad-out FILE]\n"
+                 "                   [--sh-grad FILE --sh-grad-out FILE]\n");
     std::exit(2);
 }
 
@@ -100,6 +106,8 @@ Options parse(int argc, char** argv) {
         else if (a == "--features-out") o.features_out = val();
         else if (a == "--feature-grad") o.feature_grad = val();
         else if (a == "--feature-grad-out") o.feature_grad_out = val();
+        else if (a == "--sh-grad") o.sh_grad = val();
+        else if (a == "--sh-grad-out") o.sh_grad_out = val();
         else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
@@ -110,6 +118,14 @@ Options parse(int argc, char** argv) {
     if (!o.width || !o.height) usage("empty frame");
     if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
     if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
+    if (!o.sh_grad.empty() || !o.sh_grad_out.empty()) {
+        if (o.sh_grad.empty() || o.sh_grad_out.empty()) usage("--sh-grad and --sh-grad-out go together");
+        if (o.mode != "cor") usage("--sh-grad needs --mode cor (REF frames blend nothing)");
+        if (o.stats) usage("--sh-grad cannot be combined with --stats");
+        if (!o.depth.empty()) usage("--sh-grad cannot be combined with --depth");
+        if (!o.features.empty() || !o.features_out.empty()) usage("--sh-grad cannot be combined with --features");
+        if (!o.feature_grad.empty() || !o.feature_grad_out.empty()) usage("--sh-grad cannot be combined with --feature-grad");
+    }
     if (!o.feature_grad.empty() || !o.feature_grad_out.empty()) {
         if (o.feature_grad.empty() || o.feature_grad_out.empty() || !o.feature_channels_given)
             usage("--feature-grad, --feature-channels and --feature-grad-out go together");
@@ -251,6 +267,24 @@ int main(int argc, char** argv) {
             if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.feature_grad_out.c_str());
         }
         if (!rc) std::printf("wrote %s\n", o.feature_grad_out.c_str());
+    } else if (!rc && !o.sh_grad.empty()) {
+        // the upstream gradient of the RGBA frame: W * H * 4 raw float32; the SH table's gradient: n * 48 raw float32
+        std::vector<float> gimg((size_t)o.width * o.height * 4), gtab((size_t)gsrt_scene_size(scene) * 48);
+        FILE* f = std::fopen(o.sh_grad.c_str(), "rb");
+        const bool whole = f && std::fread(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size() &&
+                           std::fgetc(f) == EOF;
+        if (f) std::fclose(f);
+        if (!whole) {
+            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x 4)\n", o.sh_grad.c_str(), gimg.size());
+            rc = 1;
+        }
+        if (!rc) rc = check(gsrt_render_sh_grad(scene, &ubo, mode, 0, gimg.data(), gtab.data(), 0), ctx, "render");
+        if (!rc) {
+            f = std::fopen(o.sh_grad_out.c_str(), "wb");
+            const bool ok = f && std::fwrite(gtab.data(), sizeof(float), gtab.size(), f) == gtab.size();
+            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.sh_grad_out.c_str());
+        }
+        if (!rc) std::printf("wrote %s\n", o.sh_grad_out.c_str());
     } else if (!rc) {
         rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
     }
@@ -273,7 +307,7 @@ int main(int argc, char** argv) {
         const double rays = (double)o.width * o.height * o.samples * frames;
         if (!rc) std::printf("%u frames %.3f ms/frame %.1f Mrays/s\n", frames, dt / frames * 1e3, rays / dt / 1e6);
     }
-    if (!rc && !o.no_dump && o.feature_grad.empty()) {  // a gradient run writes its table only
+    if (!rc && !o.no_dump && o.feature_grad.empty() && o.sh_grad.empty()) {  // a gradient run writes its table only
         std::string path = o.out;
         if (path.empty()) {
             char name[128];

@@ -419,6 +419,37 @@ gsrt_status gsrt_scene_set_features(gsrt_scene* sc, const float* feat, uint32_t 
 
 uint32_t gsrt_scene_features(const gsrt_scene* sc) { return sc && sc->d_feat_rows ? sc->feat_channels : 0u; }
 
+// The SH rows in upload_common's device layout and fold: a host source is transposed here with upload_common's own
+// expression, a device source by a small kernel (k_sh_rows, the same two float32 operations). No frame is in flight while
+// the rows change (sync_all first).
+gsrt_status gsrt_scene_set_sh(gsrt_scene* sc, const float* sh) {
+    if (!sc) return GSRT_E_ARG;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (gsrt_status s = gsrt::sync_all(ctx); s != GSRT_OK) return s;  // queued frames read the old rows
+    if (!sh) {
+        (void)hipFree(sc->d_sh);
+        sc->d_sh = nullptr;
+        return GSRT_OK;
+    }
+    const size_t n = sc->n;
+    if (!sc->d_sh) GSRT_HIP(ctx, hipMalloc(&sc->d_sh, sizeof(float) * 48 * (n ? n : 1)));
+    if (is_device_ptr(sh)) {
+        gsrt::launch_sh_rows(ctx->stream, sc->d_sh, sh, sc->n);
+        GSRT_HIP(ctx, hipGetLastError());
+    } else if (n) {
+        std::vector<float> t(48 * n);
+        for (size_t i = 0; i < n; ++i)
+            for (int c = 0; c < 3; ++c) {
+                t[48 * i + 16 * c] = sh[48 * i + c] * gsrt::kShY0 + 0.5f;
+                for (int k = 1; k < 16; ++k) t[48 * i + 16 * c + k] = sh[48 * i + 3 * k + c];
+            }
+        GSRT_HIP(ctx, hipMemcpyAsync(sc->d_sh, t.data(), sizeof(float) * 48 * n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    GSRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the source (and t above) may go once the call returns
+    return GSRT_OK;
+}
+
 void gsrt_destroy_scene(gsrt_scene* sc) {
     if (!sc) return;
     if (sc->ctx) {
@@ -731,14 +762,28 @@ gsrt_status gsrt_bvh_download(gsrt_scene* sc, uint32_t* nodes, uint32_t* leaf_gi
     return GSRT_OK;
 }
 
-// grad_call: the caller is gsrt_render_feature_grad(_async), the only entry point that may carry GSRT_FLAG_FEATURE_GRAD
-static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, bool grad_call = false) {
+// grad_call: the caller is gsrt_render_feature_grad(_async), the only entry point that may carry GSRT_FLAG_FEATURE_GRAD,
+// or gsrt_render_sh_grad(_async), the only one that may carry GSRT_FLAG_SH_GRAD
+enum class GradCall { none, feature, sh };
+static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, GradCall grad_call = GradCall::none) {
     if (!sc || !ubo) return GSRT_E_ARG;
     if (ubo->width == 0 || ubo->height == 0 || ubo->width > 32768 || ubo->height > 32768)
         return fail(sc->ctx, GSRT_E_ARG, "bad frame size");
+    if (mode & GSRT_FLAG_SH_GRAD) {  // a whole COR colour frame that scatters its gradient to the SH rows it blends
+        const char* why = nullptr;
+        if (grad_call != GradCall::sh) why = "GSRT_FLAG_SH_GRAD: only through gsrt_render_sh_grad (the gradient image goes there)";
+        else if ((mode & 0xffu) != GSRT_MODE_COR) why = "GSRT_FLAG_SH_GRAD: COR frames only";
+        else if (mode & GSRT_FLAG_STATS) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_STATS";
+        else if (mode & GSRT_FLAG_OUT_DUMP8) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_OUT_DUMP8";
+        else if (mode & GSRT_FLAG_DEPTH) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_DEPTH";
+        else if (mode & GSRT_FLAG_FEATURES) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_FEATURES";
+        else if (mode & GSRT_FLAG_FEATURE_GRAD) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_FEATURE_GRAD";
+        else if (sc->ntri) why = "GSRT_FLAG_SH_GRAD: not for a scene with a triangle mesh";
+        if (why) return fail(sc->ctx, GSRT_E_ARG, why);
+    }
     if (mode & GSRT_FLAG_FEATURE_GRAD) {  // a whole COR frame that scatters a gradient image to the Gaussians it blends
         const char* why = nullptr;
-        if (!grad_call) why = "GSRT_FLAG_FEATURE_GRAD: only through gsrt_render_feature_grad (the gradient image goes there)";
+        if (grad_call != GradCall::feature) why = "GSRT_FLAG_FEATURE_GRAD: only through gsrt_render_feature_grad (the gradient image goes there)";
         else if ((mode & 0xffu) != GSRT_MODE_COR) why = "GSRT_FLAG_FEATURE_GRAD: COR frames only";
         else if (mode & GSRT_FLAG_STATS) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_STATS";
         else if (mode & GSRT_FLAG_OUT_DUMP8) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_OUT_DUMP8";
@@ -759,7 +804,8 @@ static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
         if (mode & GSRT_FLAG_DEPTH) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_DEPTH");
     }
     if ((mode & 0xffu) > GSRT_MODE_COR ||
-        (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH | GSRT_FLAG_FEATURES | GSRT_FLAG_FEATURE_GRAD)))
+        (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH | GSRT_FLAG_FEATURES | GSRT_FLAG_FEATURE_GRAD |
+                  GSRT_FLAG_SH_GRAD)))
         return fail(sc->ctx, GSRT_E_ARG, "bad mode");
     if ((mode & 0xffu) == GSRT_MODE_COR && ubo->samples == 0) return fail(sc->ctx, GSRT_E_ARG, "samples == 0");
     if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
@@ -767,6 +813,8 @@ static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
         return fail(sc->ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     if ((mode & GSRT_FLAG_FEATURES) && !gsrt_scene_features(sc))
         return fail(sc->ctx, GSRT_E_STATE, "GSRT_FLAG_FEATURES: the scene has no feature table (gsrt_scene_set_features)");
+    if ((mode & GSRT_FLAG_SH_GRAD) && !sc->d_sh)
+        return fail(sc->ctx, GSRT_E_STATE, "GSRT_FLAG_SH_GRAD: the scene has no SH rows (gsrt_scene_set_sh)");
     return GSRT_OK;
 }
 
@@ -800,6 +848,7 @@ struct GradFrame {
     const float* d_in;   // the upstream gradient image, W x H x channels floats
     float* d_rows;       // the zeroed gradient table, n rows of 16 floats
     uint32_t channels;
+    bool sh = false;     // a GSRT_FLAG_SH_GRAD frame's: the RGBA frame's gradient (channels = 4), n rows of 48 floats
 };
 
 // a frame's device outputs: a caller fills the ones its frame has, the others stay nullptr
@@ -815,7 +864,8 @@ struct FrameOut {
 static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const FrameOut& out) {
     float* const d_rgba = out.rgba;
     gsrt_raystate* const d_rs = out.rs;
-    gsrt_status s = check_render_args(sc, ubo, mode, out.grad != nullptr);
+    gsrt_status s = check_render_args(sc, ubo, mode,
+                                      !out.grad ? GradCall::none : out.grad->sh ? GradCall::sh : GradCall::feature);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
@@ -828,7 +878,7 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
     // ray states are one buffer, so frames that write them stay in order; so are the depth image (GSRT_FLAG_DEPTH) and
     // the feature image (GSRT_FLAG_FEATURES) and a gradient frame's table (GSRT_FLAG_FEATURE_GRAD)
     const bool depth = (mode & GSRT_FLAG_DEPTH) != 0, feat = (mode & GSRT_FLAG_FEATURES) != 0;
-    const bool grad = (mode & GSRT_FLAG_FEATURE_GRAD) != 0;
+    const bool grad = (mode & (GSRT_FLAG_FEATURE_GRAD | GSRT_FLAG_SH_GRAD)) != 0;
     const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth && !feat && !grad &&
                       gsrt::use_slot_streams(ctx, false);
     if (slot) {
@@ -872,6 +922,7 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
             rsy.grad_in = out.grad->d_in;
             rsy.grad_rows = out.grad->d_rows;
             rsy.grad_channels = out.grad->channels;
+            rsy.grad_sh = out.grad->sh;
         }
         s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat && !grad ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
@@ -990,7 +1041,7 @@ static gsrt_status check_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t
         return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: channels must be 1..GSRT_MAX_FEATURES");
     if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: grad_image is NULL");
     if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: grad_table is NULL");
-    return check_render_args(sc, ubo, mode, true);
+    return check_render_args(sc, ubo, mode, GradCall::feature);
 }
 
 gsrt_status gsrt_render_feature_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
@@ -1040,6 +1091,66 @@ gsrt_status gsrt_render_feature_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
         GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
     s = gsrt_render_feature_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in, channels,
                                        out_dev ? grad_table : ctx->d_grad_out, accumulate);
+    return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
+                                     sizeof(float) * out_floats, "gradient table download failed"}});
+}
+
+// An SH gradient frame goes the same way through the same buffers of the ctx (such frames and feature-gradient frames stay
+// in order on the render stream): the rows are n x 48 floats, 192-B rows in the SH rows' own [rgb][coef] layout, and
+// launch_sh_grad_compact transposes them into the caller's [gauss][coef][rgb] table.
+static gsrt_status check_sh_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const float* grad_image,
+                                      const float* grad_table) {
+    if (!sc || !ubo) return GSRT_E_ARG;
+    if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: grad_image is NULL");
+    if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: grad_table is NULL");
+    return check_render_args(sc, ubo, mode, GradCall::sh);
+}
+
+gsrt_status gsrt_render_sh_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                      const float* d_grad_image, float* d_grad_table, int accumulate) {
+    mode |= GSRT_FLAG_SH_GRAD;
+    gsrt_status s = check_sh_grad_args(sc, ubo, mode, d_grad_image, d_grad_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const size_t rows = (size_t)48 * (sc->n ? sc->n : 1);
+    if (ctx->grad_rows_floats < rows || !ctx->d_grad_rows) {  // a queued frame may still use the old rows
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_rows, &ctx->grad_rows_floats, rows)) != GSRT_OK) return s;
+    }
+    GSRT_HIP(ctx, hipMemsetAsync(ctx->d_grad_rows, 0, sizeof(float) * rows, ctx->stream));
+    const GradFrame gf{d_grad_image, ctx->d_grad_rows, 4u, true};
+    FrameOut out;
+    out.grad = &gf;
+    s = render_async(sc, ubo, mode, k, out);
+    if (s != GSRT_OK) return s;
+    gsrt::launch_sh_grad_compact(ctx->stream, d_grad_table, ctx->d_grad_rows, sc->n, accumulate != 0);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_render_sh_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const float* grad_image,
+                                float* grad_table, int accumulate) {
+    mode |= GSRT_FLAG_SH_GRAD;
+    gsrt_status s = check_sh_grad_args(sc, ubo, mode, grad_image, grad_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
+    if (accumulate && !out_dev) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: accumulate needs a device grad_table");
+    const size_t in_floats = (size_t)ubo->width * ubo->height * 4, out_floats = (size_t)sc->n * 48;
+    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
+    }
+    if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_out, &ctx->grad_out_floats, out_floats ? out_floats : 1)) != GSRT_OK) return s;
+    }
+    if (!in_dev)
+        GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
+    s = gsrt_render_sh_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in,
+                                  out_dev ? grad_table : ctx->d_grad_out, accumulate);
     return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
                                      sizeof(float) * out_floats, "gradient table download failed"}});
 }

@@ -157,7 +157,8 @@ struct gsrt_ctx {
     size_t feat_floats = 0;
     bool last_feat = false;                    // the last frame wrote d_feat (gsrt_feature_buffer)
     // GSRT_FLAG_FEATURE_GRAD frames (one set of buffers: such frames stay in order): the gradient table the render
-    // kernel adds to, n rows of 16 floats; a host gradient image's device copy; a host table's compact device copy
+    // kernel adds to, n rows of 16 floats; a host gradient image's device copy; a host table's compact device copy.
+    // GSRT_FLAG_SH_GRAD frames use the same three, in order with them: n rows of 48 floats, W x H x 4, n x 48
     float* d_grad_rows = nullptr;
     size_t grad_rows_floats = 0;
     float* d_grad_in = nullptr;
@@ -361,9 +362,11 @@ struct RenderSync {
     float* feat = nullptr;
     // GSRT_FLAG_FEATURE_GRAD (likewise): the upstream gradient image, W x H x grad_channels floats, and the zeroed
     // gradient table the frame adds to, n rows of 16 floats; or nullptr
+    // GSRT_FLAG_SH_GRAD (grad_sh): the upstream gradient of the RGBA frame (grad_channels = 4) and n rows of 48 floats
     const float* grad_in = nullptr;
     float* grad_rows = nullptr;
     uint32_t grad_channels = 0;
+    bool grad_sh = false;
 };
 gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_rgba,
                           gsrt_raystate* d_rs, RenderSync* sync = nullptr);
@@ -390,6 +393,11 @@ void launch_copy_d2d(hipStream_t s, void* dst, const void* src, size_t bytes);
 void launch_pad_features(hipStream_t s, float* rows, const float* src, uint32_t n, uint32_t channels);
 // gradient rows (gsrt_scene.hip): dst[g][0..channels) = rows[g][0..channels), or += when accumulate
 void launch_grad_compact(hipStream_t s, float* dst, const float* rows, uint32_t n, uint32_t channels, bool accumulate);
+// SH rows (gsrt_scene.hip): rows[g][rgb][coef] = src[g][coef][rgb] of a device source in the API layout, word 0 of a channel
+// folded as upload_common folds it
+void launch_sh_rows(hipStream_t s, float* rows, const float* src, uint32_t n);
+// SH gradient rows (gsrt_scene.hip): dst[g][coef][rgb] = rows[g][rgb][coef], or += when accumulate
+void launch_sh_grad_compact(hipStream_t s, float* dst, const float* rows, uint32_t n, bool accumulate);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into
 inline float* framebuffer_of(gsrt_ctx* ctx) { return ctx->fb_view ? ctx->fb_view : ctx->d_fb; }
 // the prep stream must not overtake what is on ctx->stream now (scene upload/update, BVH build/refit)

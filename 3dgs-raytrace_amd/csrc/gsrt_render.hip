@@ -64,6 +64,9 @@ constexpr bool kGroupRegSort = GSRT_GROUP_REGSORT != 0;
 #ifndef GSRT_GRAD_AB
 #define GSRT_GRAD_AB 0
 #endif
+#ifndef GSRT_SHGRAD_WAVES
+#define GSRT_SHGRAD_WAVES 4
+#endif
 constexpr uint32_t kFront = 128;   // frontier entries per super-group
 
 
@@ -120,6 +123,9 @@ struct RenderArgs {
     // COR gradient frames (GSRT_FLAG_FEATURE_GRAD, k_render_cor GRAD), likewise appended: the upstream gradient image,
     // width x height x grad_channels floats laid out as a feature image, and the gradient table the frame adds to, one
     // 64-B row of 16 floats per Gaussian id (zeroed before the frame, compacted after it: launch_grad_compact)
+    // An SH gradient frame (GSRT_FLAG_SH_GRAD, k_render_cor shgrad) uses the same three: grad_in is the upstream gradient of
+    // the RGBA frame (grad_channels = 4, the image's stride; alpha's is not read), grad_rows one 192-B row of 48 floats
+    // per Gaussian id, [rgb][coef] as the SH rows are (compacted by launch_sh_grad_compact)
     const float* grad_in;
     float* grad_rows;
     uint32_t grad_channels;
@@ -719,10 +725,12 @@ static_assert(sizeof(Stage) == kGroup * 256 && sizeof(Stage) % 1024 == 0, "whole
 // ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
 // with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
 // or a gradient frame, the backward of a feature frame to the feature table (GSRT_FLAG_FEATURE_GRAD, grad_rows). SH: the
-// scene's SH-3 rows are blended; LUT: the ExpLUT instead of the exact exponential. Sixteen kernels: {plain, stats,
-// depth} x SH x LUT and {feat, grad} x LUT, named by cor_kernel and nowhere else. What a kind adds (blend_hit) sits under
-// if constexpr on these members: the other kinds' code does not change. The RGBA of feat and grad is the no-SH frame's.
-enum class CorKind { plain, stats, depth, feat, grad };
+// scene's SH-3 rows are blended; LUT: the ExpLUT instead of the exact exponential. Eighteen kernels: {plain, stats,
+// depth} x SH x LUT and {feat, grad, shgrad} x LUT, named by cor_kernel and nowhere else. What a kind adds (blend_hit)
+// sits under if constexpr on these members: the other kinds' code does not change. The RGBA of feat and grad is the
+// no-SH frame's. shgrad (GSRT_FLAG_SH_GRAD, grad_rows with RenderSync::grad_sh) is the backward of a plain colour frame
+// to the SH table: SH rows always, and the plain frame's RGBA.
+enum class CorKind { plain, stats, depth, feat, grad, shgrad };
 // waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
 // spill to scratch)
 constexpr uint32_t kFeatWaves = 4;
@@ -731,26 +739,32 @@ constexpr uint32_t kFeatWaves = 4;
 // never the product library) set GSRT_GRAD_WAVES, or GSRT_GRAD_AB: 1 leaves the stage's atomic out (timing only), 2
 // makes it count adds per row and wave-instructions instead of summing (profiles/feature_grad_cost.py); defaults at the top
 constexpr uint32_t kGradWaves = GSRT_GRAD_WAVES;
+// and for the two shgrad kernels, likewise (GSRT_SHGRAD_WAVES)
+constexpr uint32_t kShGradWaves = GSRT_SHGRAD_WAVES;
 struct NoPayload {};
 struct DepthPayload { float D; };      // sum of z w over the blended hits (expected view depth, premultiplied)
 struct ChannelPayload { float F[16]; };  // feat: sum of f_k w over the blended hits per channel; grad: the lane's G_k / ns
+struct RgbGradPayload { float G[3]; };   // shgrad: the lane's upstream colour gradient G_ch / ns
 template <CorKind K, bool SH, bool LUT>
 struct CorVariant {
     static constexpr bool sh = SH, lut = LUT;
     static constexpr bool stats = K == CorKind::stats, depth = K == CorKind::depth;
-    static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad;
+    static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad, shgrad = K == CorKind::shgrad;
     static_assert(!(feat || grad) || !SH, "feature and gradient frames evaluate no SH");
+    static_assert(!shgrad || SH, "an SH gradient frame blends the SH rows");
     // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
     // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
     // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
-    static constexpr uint32_t waves = grad ? kGradWaves : feat ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6);
+    static constexpr uint32_t waves =
+        shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6);
     // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
     // stage, and DMA instructions per stage (one piece per lane each)
     static constexpr uint32_t row_pieces = feat ? 4u : 12u;
     static constexpr uint32_t stage_pieces = SH ? 16 * kGroup : (feat ? 8 * kGroup : 4 * kGroup);
     static constexpr uint32_t stage_ops = (stage_pieces + 63) / 64;
     // what the kind adds to a ray's state (CorRay) and to a pixel's sums (PixelSums); empty where it adds nothing
-    using RayPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat || grad, ChannelPayload, NoPayload>>;
+    using RayPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat || grad, ChannelPayload,
+                                          std::conditional_t<shgrad, RgbGradPayload, NoPayload>>>;
     using SumPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat, ChannelPayload, NoPayload>>;
 };
 
@@ -909,6 +923,18 @@ struct GradStage {
     float sums[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
     uint32_t mask = 0;  // bit c: some lane blended candidate c
 };
+// shgrad only, likewise: the SH gradient table's rows (192 B per Gaussian id, [rgb][coef] as the SH rows are), and a
+// stage's share: per colour channel the candidates' row sums over the coefficients
+struct ShGradDst { float* rows; };
+struct ShGradStage {
+    const uint32_t* ids;
+    ShGradDst dst;
+    float sums[3][kGroup] = {};
+    uint32_t mask = 0;  // bit c: some lane blended candidate c
+};
+// a stage's share of a round's destination
+__device__ GSRT_INLINE GradStage stage_of(const uint32_t* ids, const GradDst& dst) { return GradStage{ids, dst}; }
+__device__ GSRT_INLINE ShGradStage stage_of(const uint32_t* ids, const ShGradDst& dst) { return ShGradStage{ids, dst}; }
 template <class T>
 __device__ GSRT_INLINE T& only(T& t) { return t; }  // the one element of a pack that holds one
 // z: the candidate's view depth (SplatRec::depth), already in a register from shade_stage's read of the record (a read
@@ -918,10 +944,12 @@ __device__ GSRT_INLINE T& only(T& t) { return t; }  // the one element of a pack
 // grad: ray.k.F holds the lane's upstream gradient G_c / ns (k_render_cor); the candidate's terms t_c = w G_c of the
 // blending lanes (+0, selected, on every other lane) are summed over each 16-lane row into the stage's sums
 // (grad_row_sums), and the colour is the feature frame's. G: the stage's GradStage there, nothing elsewhere.
+// shgrad: ray.k.G holds the lane's upstream colour gradient G_ch / ns; per colour channel the terms (w G_ch) Y_q of the
+// blending lanes whose channel is not clamped go the same way into the stage's ShGradStage; the colour is the plain frame's
 template <class V, class... G>
 __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z, float alpha, uint64_t contrib,
                                           CorRay<V>& ray, G&... grad) {
-    static_assert(sizeof...(G) == (V::grad ? 1 : 0), "a gradient frame's stage, and only that");
+    static_assert(sizeof...(G) == (V::grad || V::shgrad ? 1 : 0), "a gradient frame's stage, and only that");
     const float tn = ray.T * (1.0f - alpha);
     const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
     const uint64_t term = contrib & low;
@@ -938,6 +966,24 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
             GradStage& gs = only(grad...);
             gs.sums[c] = grad_row_sums(t);
             gs.mask |= 1u << c;  // wave-uniform: some lane blended this candidate
+        }
+        if constexpr (V::shgrad) {
+            // per channel the terms t_q = (w G_ch) Y_q of the blending lanes whose channel the clamp let through
+            // (col[ch] > 0 exactly when sh_channel's chain ended above 0), +0, selected, on every other lane; Y_q is the
+            // ray's own basis, bs[0] = kShY0: the gradient is with respect to the API's s_0, not the folded word
+            const float w = alpha * ray.T;  // the blend's own weight (T is updated below)
+            const bool mine = lane_of(blend);
+            ShGradStage& gs = only(grad...);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const bool on = mine && col[ch] > 0.0f;
+                const float wg = w * ray.k.G[ch];
+                float t[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) t[q] = on ? wg * ray.bs[q] : 0.0f;
+                gs.sums[ch][c] = grad_row_sums(t);
+            }
+            gs.mask |= 1u << c;
         }
         if (lane_of(blend)) {
             const float w = alpha * ray.T;
@@ -978,6 +1024,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
 // compile time (the steady state of shade_sorted), so no candidate is tested against m.
 // grad: the stage's terms w G go to the gradient table (go.dst) in one atomic wave-instruction, lane 16 c + ch adding
 // the wave's sum for candidate c and channel ch, masked to the candidates some lane blended and to the channels in use.
+// shgrad: likewise three wave-instructions, one per colour channel, lane 16 c + q adding coefficient q.
 template <class V, bool FULL, class... G>
 __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay<V>& ray, G... grad) {
     constexpr bool LUT = V::lut;
@@ -1063,6 +1110,26 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
                 }
             }
         }
+        if constexpr (V::shgrad) {
+            // three atomic wave-instructions per stage, one per colour channel: lane 16 c + q adds the wave's sum for
+            // candidate c and coefficient q to the row's channel, masked to the candidates some lane blended
+            const ShGradStage& go = only(grad...);
+            const uint32_t gmask = go.mask;
+            if (gmask) {  // wave-uniform: a stage no lane blended adds nothing
+                float sum[3];
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) sum[ch] = grad_stage_sums(go.sums[ch]);
+                const uint32_t l = lane_here(), c = l >> 4, q = l & 15u;
+                // a blended candidate c is below m, so ids[c] is an entry of the round's list: its id is below n and its
+                // 48-float row inside the table
+                if ((gmask >> c) & 1u) {
+                    const uint32_t id = lds_read_settled(go.ids + c);
+                    float* row = go.dst.rows + (size_t)id * 48u + q;
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) atomicAdd(row + 16 * ch, sum[ch]);  // no-return global_atomic_add_f32
+                }
+            }
+        }
     } else {
         for (uint32_t c = 0; c < m; ++c) {
             // counting pass: every AABB candidate of every active ray is counted (no g-first skip)
@@ -1106,10 +1173,10 @@ __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, St
     auto issue = [&](uint32_t g, Stage* dst) { stage_issue<V>(ids, count, g, lane, dst, recs, sh); };
     auto shade = [&](Stage* stg, uint32_t g) {
         const uint32_t m = count - g < kGroup ? count - g : kGroup;
-        shade_stage<V, false>(stg, m, lut_s, ray, GradStage{ids + g, gdst}...);
+        shade_stage<V, false>(stg, m, lut_s, ray, stage_of(ids + g, gdst)...);
     };
     auto shade_full = [&](Stage* stg, uint32_t g) {
-        shade_stage<V, true>(stg, kGroup, lut_s, ray, GradStage{ids + g, gdst}...);
+        shade_stage<V, true>(stg, kGroup, lut_s, ray, stage_of(ids + g, gdst)...);
     };
     constexpr uint32_t kWaitTwo = 2 * V::stage_ops;  // the two younger stages' DMAs stay in flight
     // stages issued after stage g's DMA when it is read: those of g + kGroup and g + 2 kGroup that exist
@@ -1720,6 +1787,15 @@ __device__ GSRT_INLINE CorRay<V> cor_ray(const CorTile::Pixel& p, uint32_t S, ui
 #pragma unroll
         for (int q = 0; q < 16; ++q) ray.k.F[q] = p.valid && (uint32_t)q < C ? over_samples(gi[q], ns) : 0.0f;
     }
+    if constexpr (V::shgrad) {
+        // the pixel's upstream colour gradient (an RGBA image's first three floats: alpha does not depend on SH), scaled
+        // once by 1 / ns; invalid lanes hold +0
+        const KArgs& K = kargs();
+        const uint32_t ns = S * passes;
+        const float* gi = K.a.grad_in + ((size_t)p.y * K.a.width + p.x) * 4;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) ray.k.G[ch] = p.valid ? over_samples(gi[ch], ns) : 0.0f;
+    }
     ray.active = p.valid;
     if (!p.valid) ray.pxs = __builtin_nanf("");  // see blend_hit
     ray.cand = ray.blended = ray.term = 0;
@@ -1910,6 +1986,8 @@ void k_render_cor(const KArgs karg) {
             if constexpr (V::grad)
                 live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
                                        GradDst{kargs().a.grad_rows, kargs().a.grad_channels});
+            else if constexpr (V::shgrad)
+                live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, ShGradDst{kargs().a.grad_rows});
             else
                 live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
 #ifdef GSRT_DIAG
@@ -2438,7 +2516,8 @@ static void fill_args(KArgs& k, const gsrt_scene* sc, const gsrt_ubo& ubo, const
     A.feat_out = outputs ? sync->feat : nullptr;
     A.feat_rows = A.feat_out ? sc->d_feat_rows : nullptr;
     A.feat_channels = A.feat_out ? sc->feat_channels : 0u;
-    const bool grad = outputs && sync->grad_rows && !A.depth_out && !A.feat_out;
+    // (an SH gradient frame of a scene without SH rows is refused before it gets here, gsrt_api.cpp check_render_args)
+    const bool grad = outputs && sync->grad_rows && !A.depth_out && !A.feat_out && (!sync->grad_sh || sc->d_sh);
     A.grad_in = grad ? sync->grad_in : nullptr;
     A.grad_rows = grad ? sync->grad_rows : nullptr;
     A.grad_channels = grad ? sync->grad_channels : 0u;
@@ -2760,6 +2839,8 @@ template <CorKind K>
 static CorLaunch cor_kernel_of(bool sh, bool lut) {
     if constexpr (K == CorKind::feat || K == CorKind::grad)
         return lut ? launch_cor_t<CorVariant<K, false, true>> : launch_cor_t<CorVariant<K, false, false>>;
+    else if constexpr (K == CorKind::shgrad)  // only for a scene with SH rows (gsrt_api.cpp: GSRT_E_STATE without)
+        return lut ? launch_cor_t<CorVariant<K, true, true>> : launch_cor_t<CorVariant<K, true, false>>;
     else
         return sh ? (lut ? launch_cor_t<CorVariant<K, true, true>> : launch_cor_t<CorVariant<K, true, false>>)
                   : (lut ? launch_cor_t<CorVariant<K, false, true>> : launch_cor_t<CorVariant<K, false, false>>);
@@ -2771,6 +2852,7 @@ static CorLaunch cor_kernel(CorKind kind, bool sh, bool lut) {
         case CorKind::depth: return cor_kernel_of<CorKind::depth>(sh, lut);
         case CorKind::feat: return cor_kernel_of<CorKind::feat>(sh, lut);
         case CorKind::grad: return cor_kernel_of<CorKind::grad>(sh, lut);
+        case CorKind::shgrad: return cor_kernel_of<CorKind::shgrad>(sh, lut);
     }
     return nullptr;
 }
@@ -2825,7 +2907,8 @@ static gsrt_status launch_cor(gsrt_scene* sc, const RenderPlan& plan, const Fram
     const hipStream_t st = ctx->stream;
     FrameSlot& S = ctx->slot[f.b];
     const RenderArgs& A = k.a;
-    const CorKind kind = A.grad_rows ? CorKind::grad : A.feat_out ? CorKind::feat : A.depth_out ? CorKind::depth
+    const CorKind kind = A.grad_rows ? (sync->grad_sh ? CorKind::shgrad : CorKind::grad)
+                         : A.feat_out ? CorKind::feat : A.depth_out ? CorKind::depth
                          : f.stats   ? CorKind::stats : CorKind::plain;
     const CorLaunch render = cor_kernel(kind, sc->d_sh != nullptr, (plan.mode & GSRT_FLAG_LUT) != 0);
     hipStream_t rs = st;

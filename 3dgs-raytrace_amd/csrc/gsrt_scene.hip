@@ -181,4 +181,41 @@ void launch_grad_compact(hipStream_t s, float* dst, const float* rows, uint32_t 
                        accumulate ? 1u : 0u);
 }
 
+// SH rows of a device source (gsrt_scene_set_sh): one thread per float of the device layout [gauss][rgb][coef], read from
+// the API layout [gauss][coef][rgb]; word 0 of a channel is (s_0 Y_0) + 0.5, the product rounded before the sum, as
+// upload_common computes it on the host (the library is built with -ffp-contract=off)
+__global__ __launch_bounds__(256) void k_sh_rows(float* __restrict__ rows, const float* __restrict__ src, size_t n48) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n48) return;
+    const size_t g = i / 48;
+    const uint32_t r = (uint32_t)(i - g * 48), c = r >> 4, k = r & 15u;
+    const float s = src[g * 48 + 3 * k + c];
+    rows[i] = k == 0 ? __fadd_rn(__fmul_rn(s, kShY0), 0.5f) : s;
+}
+
+void launch_sh_rows(hipStream_t s, float* rows, const float* src, uint32_t n) {
+    const size_t n48 = (size_t)n * 48;
+    if (!n48) return;
+    hipLaunchKernelGGL(k_sh_rows, dim3((uint32_t)((n48 + 255) / 256)), dim3(256), 0, s, rows, src, n48);
+}
+
+// SH gradient rows of an SH gradient frame (gsrt_render_sh_grad) to the caller's table: one thread per output float,
+// dst[g][coef][rgb] = rows[g][rgb][coef] of the 192-B rows the render kernel added to, or += when accumulate
+__global__ __launch_bounds__(256) void k_sh_grad_compact(float* __restrict__ dst, const float* __restrict__ rows, size_t n48,
+                                                         uint32_t accumulate) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n48) return;
+    const size_t g = i / 48;
+    const uint32_t r = (uint32_t)(i - g * 48), k = r / 3, c = r - 3 * k;
+    const float v = rows[g * 48 + 16 * c + k];
+    dst[i] = accumulate ? dst[i] + v : v;
+}
+
+void launch_sh_grad_compact(hipStream_t s, float* dst, const float* rows, uint32_t n, bool accumulate) {
+    const size_t n48 = (size_t)n * 48;
+    if (!n48) return;
+    hipLaunchKernelGGL(k_sh_grad_compact, dim3((uint32_t)((n48 + 255) / 256)), dim3(256), 0, s, dst, rows, n48,
+                       accumulate ? 1u : 0u);
+}
+
 }  // namespace gsrt

@@ -24,6 +24,7 @@ PAGE_GAUSSIANS = 4096  # GSRT_PAGE_GAUSSIANS
 MODE_REF, MODE_COR = 0, 1
 FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8, FLAG_DEPTH, FLAG_FEATURES = 0x100, 0x200, 0x400, 0x800, 0x1000
 FLAG_FEATURE_GRAD = 0x2000
+FLAG_SH_GRAD = 0x4000
 MAX_FEATURES = 16  # GSRT_MAX_FEATURES
 DUMP8_ESCAPE = 1 << 30  # GSRT_DUMP8_ESCAPE
 SYNTH_COR, SYNTH_REF, SYNTH_NEEDLE = 0, 1, 2
@@ -65,7 +66,7 @@ EXPORTS = [
     "gsrt_decide_bands", "gsrt_render_depth", "gsrt_render_depth_async", "gsrt_depth_buffer", "gsrt_dump_pfm",
     "gsrt_scene_set_features", "gsrt_scene_features", "gsrt_render_features", "gsrt_render_features_async",
     "gsrt_feature_buffer", "gsrt_render_feature_grad", "gsrt_render_feature_grad_async", "gsrt_group_order",
-    "gsrt_unit_order",
+    "gsrt_unit_order", "gsrt_scene_set_sh", "gsrt_render_sh_grad", "gsrt_render_sh_grad_async",
 ]
 
 
@@ -178,6 +179,9 @@ def _load():
         "gsrt_feature_buffer": ([P], P),
         "gsrt_render_feature_grad": ([P, P, u32, u32, P, u32, P, i32], i32),
         "gsrt_render_feature_grad_async": ([P, P, u32, u32, P, u32, P, i32], i32),
+        "gsrt_scene_set_sh": ([P, P], i32),
+        "gsrt_render_sh_grad": ([P, P, u32, u32, P, P, i32], i32),
+        "gsrt_render_sh_grad_async": ([P, P, u32, u32, P, P, i32], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -909,6 +913,41 @@ class Scene:
         over a pixel's samples), i.e. feature_grad of an image of ones with one channel."""
         W, H = int(ubo["width"][0]), int(ubo["height"][0])
         return self.feature_grad(ubo, np.ones((H, W), np.float32), mode, k)[:, 0]
+
+    def set_sh(self, sh):
+        """Replace the scene's SH rows: an (n, 16, 3) or (n, 48) float32 array laid out [gauss][coef][rgb], copied, or a
+        device address of n * 48 floats in that layout; None removes them (the scene then renders colour 1). Waits for
+        every queued frame first (gsrt_scene_set_sh)."""
+        if sh is None:
+            _check(lib.gsrt_scene_set_sh(self.handle, None), self.ctx)
+            return
+        if isinstance(sh, int):
+            _check(lib.gsrt_scene_set_sh(self.handle, ctypes.c_void_p(sh)), self.ctx)
+            return
+        sh = _f32(sh, (self.n, 48))
+        _check(lib.gsrt_scene_set_sh(self.handle, _p(sh)), self.ctx)
+
+    def sh_grad(self, ubo, grad_image, mode=MODE_COR, k=0):
+        """The backward of a colour frame to the SH table (gsrt_render_sh_grad): grad_image is the upstream gradient of
+        the RGBA frame, (H, W, 4) or (H, W, 3) float32 (alpha's gradient is ignored: alpha does not depend on SH); returns
+        the (n, 16, 3) gradient of the table, grad[g, q, ch] = sum of w * Y_q * G[p, ch] / ns over the hits of Gaussian g
+        whose channel ch the clamp at 0 let through. The sum's order is unspecified (float atomics)."""
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        g = np.asarray(grad_image, np.float32)
+        if g.ndim != 3 or g.shape[:2] != (H, W) or g.shape[2] not in (3, 4):
+            raise GsrtError(E_ARG, "sh_grad: an (H, W, 4) or (H, W, 3) array")
+        if g.shape[2] == 3:
+            g = np.concatenate([g, np.zeros((H, W, 1), np.float32)], axis=2)
+        g = np.ascontiguousarray(g)
+        out = np.zeros((self.n, 16, 3), np.float32)
+        _check(lib.gsrt_render_sh_grad(self.handle, _p(ubo), mode, k, _p(g), _p(out), 0), self.ctx)
+        return out
+
+    def sh_grad_async(self, ubo, d_grad_image: int, d_grad_table: int, accumulate=False, mode=MODE_COR, k=0):
+        """Enqueue one SH gradient frame on ctx.stream: d_grad_image (W*H*4 floats) and d_grad_table (n*48 floats,
+        ordinary device memory) are device addresses; accumulate adds to the table instead of writing it."""
+        _check(lib.gsrt_render_sh_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
+                                             ctypes.c_void_p(d_grad_table or None), 1 if accumulate else 0), self.ctx)
 
     def render_sharded(self, ubo, mode=MODE_COR, k=0, want_image=True):
         W, H = int(ubo["width"][0]), int(ubo["height"][0])

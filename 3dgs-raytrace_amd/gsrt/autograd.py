@@ -4,6 +4,12 @@
     rgba, feat = render_features(scene, ubo, table)   # table: (n, C) float32 tensor on the scene's device
     loss(feat).backward()                              # table.grad: Scene.feature_grad of the loss's gradient
 
+and for colour frames: fit the scene's SH table (its appearance) on frozen geometry.
+
+    from gsrt.autograd import render_colour
+    rgba = render_colour(scene, ubo, sh)               # sh: (n, 16, 3) or (n, 48) float32 tensor on the scene's device
+    loss(rgba).backward()                              # sh.grad: Scene.sh_grad of the loss's gradient
+
 torch is imported here only; `import gsrt` never needs it.
 
 Synchronisation is plain and blocking: the current torch stream is synchronised before the library reads a tensor, and
@@ -54,3 +60,40 @@ def render_features(scene, ubo, table, mode=MODE_COR, k=0):
     attached arrays, streamed pages) must stay as it was in the forward until backward has run, or the gradient is that
     of another frame. The forward leaves `table` as the scene's feature table."""
     return _RenderFeatures.apply(table, scene, ubo, mode, k)
+
+
+class _RenderColour(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sh, scene, ubo, mode, k):
+        if sh.dtype != torch.float32 or not sh.is_cuda or tuple(sh.shape) not in ((scene.n, 16, 3), (scene.n, 48)):
+            raise ValueError("render_colour: sh must be an (n, 16, 3) or (n, 48) float32 tensor on the GPU")
+        table = sh.contiguous()
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        rgba = torch.empty((H, W, 4), dtype=torch.float32, device=sh.device)
+        torch.cuda.current_stream(sh.device).synchronize()
+        scene.set_sh(table.data_ptr())  # copied into the scene's own rows
+        scene.render_async(ubo, mode, k, rgba.data_ptr())
+        scene.ctx.synchronize()
+        ctx.scene, ctx.ubo, ctx.mode, ctx.k, ctx.shape = scene, ubo.copy(), mode, k, tuple(sh.shape)  # the camera as it is now
+        return rgba
+
+    @staticmethod
+    def backward(ctx, grad_rgba):
+        g = grad_rgba.to(torch.float32).contiguous()
+        out = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        torch.cuda.current_stream(g.device).synchronize()
+        ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), out.data_ptr(), False, ctx.mode, ctx.k)
+        ctx.scene.ctx.synchronize()
+        return out, None, None, None, None
+
+
+def render_colour(scene, ubo, sh, mode=MODE_COR, k=0):
+    """One colour frame of the SH table `sh` ((n, 16, 3) or (n, 48) float32 GPU tensor, [gauss][coef][rgb]) as a torch
+    tensor rgba[H, W, 4], differentiable with respect to `sh`: the backward is Scene.sh_grad_async of the upstream
+    gradient (alpha's share is ignored: alpha does not depend on SH). The table is copied into the scene (Scene.set_sh).
+    Blocking synchronisation on both sides: torch's current stream before each library call, Context.synchronize()
+    after it.
+    The backward renders the scene again: it keeps a copy of `ubo`, but the scene's geometry (Scene.update, refits,
+    attached arrays, streamed pages) and its SH rows must stay as they were in the forward until backward has run, or
+    the gradient is that of another frame. The forward leaves `sh` as the scene's SH table."""
+    return _RenderColour.apply(sh, scene, ubo, mode, k)

@@ -78,8 +78,10 @@ enum {
     GSRT_FLAG_FEATURES = 0x1000, /* whole COR frames: blend the scene's feature table instead of colour
                                    (gsrt_render_features below); GSRT_E_ARG with REF, GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8,
                                    GSRT_FLAG_DEPTH or a sharded entry point; GSRT_E_STATE without a feature table */
-    GSRT_FLAG_FEATURE_GRAD = 0x2000 /* whole COR frames: the backward of a feature frame to the feature table; set by
+    GSRT_FLAG_FEATURE_GRAD = 0x2000, /* whole COR frames: the backward of a feature frame to the feature table; set by
                                        gsrt_render_feature_grad (below) itself, GSRT_E_ARG through every other entry point */
+    GSRT_FLAG_SH_GRAD = 0x4000 /* whole COR frames: the backward of a colour frame to the SH table; set by gsrt_render_sh_grad
+                                  (below) itself, GSRT_E_ARG through every other entry point */
 };
 /* synthetic cloud kinds */
 enum { GSRT_SYNTH_COR = 0, GSRT_SYNTH_REF = 1, GSRT_SYNTH_NEEDLE = 2 };
@@ -131,6 +133,11 @@ void gsrt_destroy_scene(gsrt_scene* scene);
 #define GSRT_MAX_FEATURES 16u
 gsrt_status gsrt_scene_set_features(gsrt_scene* scene, const float* feat, uint32_t channels);
 uint32_t gsrt_scene_features(const gsrt_scene* scene);
+/* Replace the scene's SH rows. sh: n*48 floats laid out [gauss][coef 0..15][rgb] as at creation, a host or device pointer,
+ * copied (a device source is transposed on the device, without a host round trip); sh == NULL removes the rows, and the
+ * scene then renders colour 1. The call first waits for every queued frame of the context. A frame after it is byte for
+ * byte the frame of a scene created with the same sh. */
+gsrt_status gsrt_scene_set_sh(gsrt_scene* scene, const float* sh);
 
 /* 3DGS .ply ingestion (the reference only has hard-coded CreateGauss calls,
  * SceneList.cpp:123-125). Vertex properties x y z, scale_0..2 (log), rot_0..3 (w x y z, unnormalised),
@@ -310,7 +317,7 @@ const float* gsrt_feature_buffer(gsrt_ctx* ctx);
  * GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH or GSRT_FLAG_FEATURES with it; sharded entry points; a scene with a mesh; channels
  * out of range; a NULL grad_image or grad_table; the flag passed to gsrt_render / gsrt_render_async (or the depth and
  * feature forms), which have nowhere to take the image.
- * Not provided: gradients with respect to geometry, opacity, SH or the normaliser (sum w); sharded frames; more than
+ * Not provided: gradients with respect to geometry, opacity or the normaliser (sum w); sharded frames; more than
  * GSRT_MAX_FEATURES channels.
  * gsrt_render_feature_grad blocks until the table is complete, like gsrt_render. */
 gsrt_status gsrt_render_feature_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
@@ -319,6 +326,36 @@ gsrt_status gsrt_render_feature_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uin
 gsrt_status gsrt_render_feature_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                            const float* d_grad_image, uint32_t channels, float* d_grad_table,
                                            int accumulate);
+/* SH gradient frame (GSRT_FLAG_SH_GRAD): the backward of a plain COR colour frame with respect to the scene's SH table.
+ * Apart from the clamp at 0 the colour is linear in the coefficients, so the backward is one forward-ordered pass.
+ * grad_image is the upstream gradient G of the RGBA frame, W*H*4 floats laid out as the frame is; channel 3 is ignored
+ * (alpha does not depend on SH). grad_table receives n*48 floats laid out [gauss][coef 0..15][rgb], as the sh of
+ * gsrt_scene_from_params is:
+ *     grad_table[g][q][ch] = sum over pixels p, samples s of p, hits i of ray (p, s) with id g and a_{i,ch} > 0 of
+ *                            w_i * Y_q(d_{p,s}) * (G[p][ch] / ns)
+ * with ns the samples per pixel; w_i, the hits, their order and the stop exactly those of the colour blend; a_{i,ch} the
+ * blend's own float32 channel value before its clamp at 0; Y_q the ray's float32 SH basis (Y_0 = 0.28209479: the gradient
+ * is with respect to s_0 as the API takes it). The clamp's mask is a select: a clamped channel contributes +0, and a
+ * non-finite G[p][ch] reaches only the (Gaussian, channel) pairs pixel p blends unclamped. G / ns is formed once (G * (1/ns)
+ * for a power of two, G / ns otherwise); a term is the float32 product (w_i * that) * Y_q. The terms are summed on the
+ * device with float atomic adds, so the order of the sum is unspecified and results can differ in their last bits from
+ * run to run.
+ * accumulate == 0: the table is written, entries nothing reaches get +0. accumulate != 0: this frame's gradient is added
+ * to what the table holds; that form takes a device grad_table only, a host one is GSRT_E_ARG. grad_image / grad_table are
+ * host or device pointers; a device table must be ordinary device memory.
+ * The frame's RGBA (gsrt_framebuffer) is the plain colour frame's, bit for bit. Like depth, feature and feature-gradient
+ * frames it takes the in-order path on gsrt_stream(): gsrt_slot_streams reads 0 after it, gsrt_depth_buffer and
+ * gsrt_feature_buffer read NULL; gsrt_timing records the frame like any other.
+ * GSRT_E_STATE: a scene without SH rows. GSRT_E_ARG (gsrt_last_error names GSRT_FLAG_SH_GRAD, and the context renders as
+ * before): REF mode; GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH, GSRT_FLAG_FEATURES or GSRT_FLAG_FEATURE_GRAD with
+ * it; sharded entry points; a scene with a mesh; a NULL grad_image or grad_table; the flag passed to any other entry point.
+ * Not provided: gradients with respect to geometry or opacity; sharded frames.
+ * gsrt_render_sh_grad blocks until the table is complete, like gsrt_render. */
+gsrt_status gsrt_render_sh_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const float* grad_image,
+                                float* grad_table, int accumulate);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_render_sh_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                      const float* d_grad_image, float* d_grad_table, int accumulate);
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into
