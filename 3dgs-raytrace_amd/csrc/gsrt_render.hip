@@ -755,8 +755,10 @@ struct CorVariant {
     // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
     // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
     // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
+    // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before blend_stage: left at 4 it takes 102.
     static constexpr uint32_t waves =
-        shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves : SH ? (LUT ? 4 : 6) : (LUT ? 5 : 6);
+        shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
+        : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
     // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
     // stage, and DMA instructions per stage (one piece per lane each)
     static constexpr uint32_t row_pieces = feat ? 4u : 12u;
@@ -841,6 +843,9 @@ struct CorRay {
     // wave-candidates (per wave, lane 0 adds): staged while some lane active; some lane passed g; some lane's
     // alpha > 0; some lane blended (SH evaluated); lane-candidates passing g; lane blends
     uint32_t dg_staged, dg_gpass, dg_contrib, dg_blend, dg_lanes_g, dg_lanes_blend;
+    // stages shaded while some lane active; of those, stages some lane blends in; over those, the sum of the largest
+    // number of candidates one lane blends (the SH evaluations of blend_stage; dg_blend counts blend_hit's)
+    uint32_t dg_stages, dg_stages_blend, dg_lane_max;
 #endif
 };
 
@@ -856,7 +861,10 @@ __device__ GSRT_INLINE float sh_channel(const float (&bs)[16], const float (&s)[
     for (int q = 1; q < 16; ++q) a = fmaf(bs[q], s[q], a);
     return a > 0.0f ? a : 0.0f;
 }
-struct ShFromStage {  // the stage's LDS copy of candidate c's row
+// the stage's LDS copy of candidate c's row. c is wave-uniform (broadcast reads) or the lane's own (blend_stage): the
+// stage's rows lie 192 B = 48 banks apart, so lanes reading the same 16-B piece of different rows meet four distinct
+// 4-bank groups, and a ds_read_b128 costs its 4 LDS-array cycles either way
+struct ShFromStage {
     const Stage* stg;
     uint32_t c;
     __device__ GSRT_INLINE void operator()(const float (&bs)[16], float (&col)[3]) const {
@@ -1020,6 +1028,106 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
     return term;
 }
 
+// The SH colour kinds (plain and depth frames with SH rows) shade a stage in two parts. The colour of a hit does not
+// depend on T, only the blend is ordered: weigh_hit is the ordered part of candidate c (blend_hit's tests, masks and stop
+// handling, and T), which keeps the blend's weight and reads no SH row; blend_stage then evaluates, per lane, the SH
+// colours of the candidates that lane blends. A stage so runs as many SH evaluations as its busiest lane blends
+// candidates, not one per candidate that some lane blends.
+template <class V>
+constexpr bool kShPerLane = V::sh && !V::stats && !V::shgrad;
+struct StageBlends {
+    uint64_t blend[kGroup] = {0, 0, 0, 0};  // per candidate the lanes that blend it (ballots: SGPR pairs)
+    float w[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};  // alpha T of the candidate on those lanes
+};
+template <class V>
+__device__ GSRT_INLINE uint64_t weigh_hit(uint32_t c, float alpha, uint64_t contrib, CorRay<V>& ray, StageBlends& sb) {
+    const float tn = ray.T * (1.0f - alpha);
+    const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
+    const uint64_t term = contrib & low;
+    const uint64_t blend = contrib & ~low;
+    sb.blend[c] = blend;
+    sb.w[c] = alpha * ray.T;  // the blend's own weight, read on the blending lanes only
+    ray.T = lane_of(blend) ? tn : ray.T;
+    if (term) {  // wave-uniform: a ray stops once
+        if (lane_of(term)) {
+            ray.active = false;
+            ray.pxs = __builtin_nanf("");  // see blend_hit
+        }
+    }
+    return term;
+}
+// A lane blends its candidates in ascending c, as blend_hit does, with the same weights and the same colour chain: pass
+// J blends every lane's J-th blending candidate of the stage. Which candidate that is comes from the blend ballots by
+// scalar instructions: at[J][c] = the lanes whose J-th blend is candidate c (c >= J). The lane selects its weight and
+// its row by these masks; nothing crosses lanes. Returns false when no lane has a J-th blend (so none has a later one).
+// depth: z is read again from the lane's candidate's record in the stage (one ds_read_b32 per pass); kept in registers
+// from weigh_hit, the four z spilled to scratch inside the loop, whose reloads drain the stage pipeline (vmcnt(0)).
+template <class V, uint32_t J>
+__device__ GSRT_INLINE bool blend_pass(const Stage* stg, const uint64_t (&at)[kGroup][kGroup], const float (&ws)[kGroup],
+                                       CorRay<V>& ray) {
+    uint64_t any = at[J][J];
+    if constexpr (J + 1 < kGroup) any |= at[J][J + 1];
+    if constexpr (J + 2 < kGroup) any |= at[J][J + 2];
+    if constexpr (J + 3 < kGroup) any |= at[J][J + 3];
+    if (!any) return false;  // wave-uniform
+#ifdef GSRT_DIAG
+    ray.dg_lane_max += 1u;
+#endif
+    if (lane_of(any)) {
+        uint32_t cj = J;
+        float w = ws[J];
+        if constexpr (J + 1 < kGroup) {
+            const bool here = lane_of(at[J][J + 1]);
+            cj = here ? J + 1 : cj, w = here ? ws[J + 1] : w;
+        }
+        if constexpr (J + 2 < kGroup) {
+            const bool here = lane_of(at[J][J + 2]);
+            cj = here ? J + 2 : cj, w = here ? ws[J + 2] : w;
+        }
+        if constexpr (J + 3 < kGroup) {
+            const bool here = lane_of(at[J][J + 3]);
+            cj = here ? J + 3 : cj, w = here ? ws[J + 3] : w;
+        }
+        float col[3];
+        ShFromStage{stg, cj}(ray.bs, col);
+        ray.C[0] = fmaf(col[0], w, ray.C[0]);
+        ray.C[1] = fmaf(col[1], w, ray.C[1]);
+        ray.C[2] = fmaf(col[2], w, ray.C[2]);
+        if constexpr (V::depth) ray.k.D = fmaf(stg->rec[cj].depth, w, ray.k.D);
+    }
+    return true;
+}
+template <class V>
+__device__ GSRT_INLINE void blend_stage(const Stage* stg, const StageBlends& sb, CorRay<V>& ray) {
+    static_assert(kGroup == 4, "two bit planes count a lane's earlier blends; blend_pass selects among four");
+    if (!(sb.blend[0] | sb.blend[1] | sb.blend[2] | sb.blend[3])) return;  // wave-uniform: no lane blends in this stage
+#ifdef GSRT_DIAG
+    ray.dg_stages_blend += 1u;
+#endif
+    // the lanes' counts of earlier blends as two bit planes (p1 p0), candidate by candidate
+    uint64_t at[kGroup][kGroup];
+    uint64_t p0 = 0, p1 = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < kGroup; ++c) {
+        const uint64_t b = sb.blend[c];
+        at[0][c] = b & ~p0 & ~p1;
+        at[1][c] = b & p0 & ~p1;
+        at[2][c] = b & ~p0 & p1;
+        at[3][c] = b & p0 & p1;
+        const uint64_t carry = p0 & b;
+        p0 ^= b;
+        p1 ^= carry;
+    }
+    // the weights as register values before they are selected: selects between loads of sb.w would be folded into one
+    // load at a selected address, which keeps the whole of sb in scratch memory
+    float ws[kGroup] = {sb.w[0], sb.w[1], sb.w[2], sb.w[3]};
+    asm volatile("" : "+v"(ws[0]), "+v"(ws[1]), "+v"(ws[2]), "+v"(ws[3]));
+    if (!blend_pass<V, 0>(stg, at, ws, ray)) return;
+    if (!blend_pass<V, 1>(stg, at, ws, ray)) return;
+    if (!blend_pass<V, 2>(stg, at, ws, ray)) return;
+    blend_pass<V, 3>(stg, at, ws, ray);
+}
+
 // Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
 // compile time (the steady state of shade_sorted), so no candidate is tested against m.
 // grad: the stage's terms w G go to the gradient table (go.dst) in one atomic wave-instruction, lane 16 c + ch adding
@@ -1050,8 +1158,11 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
         }
 #ifdef GSRT_DIAG
         ray.dg_staged += __ballot(ray.active) ? m : 0u;
+        ray.dg_stages += __ballot(ray.active) ? 1u : 0u;
 #endif
-        // Phase 2, front to back over the candidates some lane passed: slab test, exp, alpha, blend
+        // Phase 2, front to back over the candidates some lane passed: slab test, exp, alpha, blend (the SH colour
+        // kinds: alpha, weight and T here, the stage's blends after the loop, blend_stage)
+        [[maybe_unused]] StageBlends sb;
 #pragma unroll
         for (uint32_t c = 0; c < kGroup; ++c) {
             if (!okg[c]) continue;
@@ -1082,12 +1193,15 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
-            const uint64_t stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad...);
+            uint64_t stopped;
+            if constexpr (kShPerLane<V>) stopped = weigh_hit<V>(c, alpha, contrib, ray, sb);
+            else stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad...);
             if (stopped) {
 #pragma unroll
                 for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
             }
         }
+        if constexpr (kShPerLane<V>) blend_stage<V>(stg, sb, ray);
         if constexpr (V::grad) {
             const GradStage& go = only(grad...);
             const uint32_t gmask = go.mask;
@@ -1801,6 +1915,7 @@ __device__ GSRT_INLINE CorRay<V> cor_ray(const CorTile::Pixel& p, uint32_t S, ui
     ray.cand = ray.blended = ray.term = 0;
 #ifdef GSRT_DIAG
     ray.dg_staged = ray.dg_gpass = ray.dg_contrib = ray.dg_blend = ray.dg_lanes_g = ray.dg_lanes_blend = 0;
+    ray.dg_stages = ray.dg_stages_blend = ray.dg_lane_max = 0;
 #endif
     return ray;
 }
@@ -2015,6 +2130,8 @@ void k_render_cor(const KArgs karg) {
         if (!V::stats && lane == 0) {
             const uint32_t dg[6] = {ray.dg_staged, ray.dg_gpass, ray.dg_contrib, ray.dg_blend, ray.dg_lanes_g, ray.dg_lanes_blend};
             for (int q = 0; q < 6; ++q) atomicAdd(kargs().a.counters + 16 + q, (unsigned long long)dg[q]);
+            const uint32_t ds[3] = {ray.dg_stages, ray.dg_stages_blend, ray.dg_lane_max};
+            for (int q = 0; q < 3; ++q) atomicAdd(kargs().a.counters + 25 + q, (unsigned long long)ds[q]);
         }
 #endif
     }

@@ -42,3 +42,9 @@ st, gp, co, bl, lg, lb = (int(x) for x in cnt[16:22])
 print(f"{cfg}: per wave: staged candidates {st / waves:.1f}, some lane passes g {gp / waves:.1f}, some lane alpha > 0 "
       f"{co / waves:.1f}, some lane blends (SH) {bl / waves:.1f}; lanes per g-survivor {lg / max(gp, 1):.1f}, "
       f"lanes per blending candidate {lb / max(bl, 1):.1f}")
+# SH colour frames only (blend_stage): stages shaded, stages some lane blends in, and over those the sum of the largest
+# number of candidates one lane blends. E = candidates some lane blends, E' = SH evaluations run, per stage
+ns, nb, lm = (int(x) for x in cnt[25:28])
+if nb:
+    print(f"{cfg}: stages shaded {ns} ({ns / waves:.2f} per wave), with a blend {nb}; per shaded stage E {bl / ns:.3f} "
+          f"E' {lm / ns:.3f}; per stage with a blend E {bl / nb:.3f} E' {lm / nb:.3f}; E'/E {lm / max(bl, 1):.3f}")
