@@ -23,7 +23,11 @@
 // --sh-grad FILE --sh-grad-out FILE (COR, a scene with SH rows: an SH gradient frame, gsrt_render_sh_grad: the upstream
 // gradient of the RGBA frame, raw float32 W*H*4, in; the gradient of the SH table, raw float32 n*48 laid out
 // [gauss][coef][rgb], out; no image is dumped; usage errors: --mode ref or a REF-default scene, --stats, --depth,
-// --features, --feature-grad, one option without the other).
+// --features, --feature-grad, one option without the other),
+// --opacity-grad FILE --opacity-grad-out FILE (COR: an opacity gradient frame, gsrt_render_opacity_grad: the upstream
+// gradient of the RGBA frame, raw float32 W*H*4, in; the gradient of the opacities, raw float32 n, out; no image is dumped;
+// usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, --feature-grad, --sh-grad, one option
+// without the other).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +50,7 @@ struct Options {
     int device = 0;
     float fov = 0.0f;  // 0: scene default
     std::string camera, out, binary, text, ply, depth, features, features_out, feature_grad, feature_grad_out;
-    std::string sh_grad, sh_grad_out;
+    std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out;
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
 };
@@ -60,7 +64,8 @@ struct Options {
                  "                   [--text FILE] [--ply FILE] [--device D] [--frames F] [--stats]\n"
                  "                   [--depth PFM] [--features FILE --feature-channels C --features-out FILE]\n"
                  "                   [--feature-grad FILE --feature-channels C --feature-grad-out FILE]\n"
-                 "                   [--sh-grad FILE --sh-grad-out FILE]\n");
+                 "                   [--sh-grad FILE --sh-grad-out FILE]\n"
+                 "                   [--opacity-grad FILE --opacity-grad-out FILE]\n");
     std::exit(2);
 }
 
@@ -108,6 +113,8 @@ Options parse(int argc, char** argv) {
         else if (a == "--feature-grad-out") o.feature_grad_out = val();
         else if (a == "--sh-grad") o.sh_grad = val();
         else if (a == "--sh-grad-out") o.sh_grad_out = val();
+        else if (a == "--opacity-grad") o.opacity_grad = val();
+        else if (a == "--opacity-grad-out") o.opacity_grad_out = val();
         else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
@@ -118,6 +125,16 @@ Options parse(int argc, char** argv) {
     if (!o.width || !o.height) usage("empty frame");
     if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
     if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
+    if (!o.opacity_grad.empty() || !o.opacity_grad_out.empty()) {
+        if (o.opacity_grad.empty() || o.opacity_grad_out.empty()) usage("--opacity-grad and --opacity-grad-out go together");
+        if (o.mode != "cor") usage("--opacity-grad needs --mode cor (REF frames blend nothing)");
+        if (o.stats) usage("--opacity-grad cannot be combined with --stats");
+        if (!o.depth.empty()) usage("--opacity-grad cannot be combined with --depth");
+        if (!o.features.empty() || !o.features_out.empty()) usage("--opacity-grad cannot be combined with --features");
+        if (!o.feature_grad.empty() || !o.feature_grad_out.empty())
+            usage("--opacity-grad cannot be combined with --feature-grad");
+        if (!o.sh_grad.empty() || !o.sh_grad_out.empty()) usage("--opacity-grad cannot be combined with --sh-grad");
+    }
     if (!o.sh_grad.empty() || !o.sh_grad_out.empty()) {
         if (o.sh_grad.empty() || o.sh_grad_out.empty()) usage("--sh-grad and --sh-grad-out go together");
         if (o.mode != "cor") usage("--sh-grad needs --mode cor (REF frames blend nothing)");
@@ -285,6 +302,24 @@ int main(int argc, char** argv) {
             if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.sh_grad_out.c_str());
         }
         if (!rc) std::printf("wrote %s\n", o.sh_grad_out.c_str());
+    } else if (!rc && !o.opacity_grad.empty()) {
+        // the upstream gradient of the RGBA frame: W * H * 4 raw float32; the opacities' gradient: n raw float32
+        std::vector<float> gimg((size_t)o.width * o.height * 4), gtab((size_t)gsrt_scene_size(scene));
+        FILE* f = std::fopen(o.opacity_grad.c_str(), "rb");
+        const bool whole = f && std::fread(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size() &&
+                           std::fgetc(f) == EOF;
+        if (f) std::fclose(f);
+        if (!whole) {
+            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x 4)\n", o.opacity_grad.c_str(), gimg.size());
+            rc = 1;
+        }
+        if (!rc) rc = check(gsrt_render_opacity_grad(scene, &ubo, mode, 0, gimg.data(), gtab.data(), 0), ctx, "render");
+        if (!rc) {
+            f = std::fopen(o.opacity_grad_out.c_str(), "wb");
+            const bool ok = f && std::fwrite(gtab.data(), sizeof(float), gtab.size(), f) == gtab.size();
+            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.opacity_grad_out.c_str());
+        }
+        if (!rc) std::printf("wrote %s\n", o.opacity_grad_out.c_str());
     } else if (!rc) {
         rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
     }
@@ -307,7 +342,7 @@ int main(int argc, char** argv) {
         const double rays = (double)o.width * o.height * o.samples * frames;
         if (!rc) std::printf("%u frames %.3f ms/frame %.1f Mrays/s\n", frames, dt / frames * 1e3, rays / dt / 1e6);
     }
-    if (!rc && !o.no_dump && o.feature_grad.empty() && o.sh_grad.empty()) {  // a gradient run writes its table only
+    if (!rc && !o.no_dump && o.feature_grad.empty() && o.sh_grad.empty() && o.opacity_grad.empty()) {  // a gradient run writes its table only
         std::string path = o.out;
         if (path.empty()) {
             char name[128];

@@ -763,12 +763,27 @@ gsrt_status gsrt_bvh_download(gsrt_scene* sc, uint32_t* nodes, uint32_t* leaf_gi
 }
 
 // grad_call: the caller is gsrt_render_feature_grad(_async), the only entry point that may carry GSRT_FLAG_FEATURE_GRAD,
-// or gsrt_render_sh_grad(_async), the only one that may carry GSRT_FLAG_SH_GRAD
-enum class GradCall { none, feature, sh };
+// or gsrt_render_sh_grad(_async), the only one that may carry GSRT_FLAG_SH_GRAD, or gsrt_render_opacity_grad(_async), the
+// only one that may carry GSRT_FLAG_OPACITY_GRAD
+enum class GradCall { none, feature, sh, opacity };
 static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, GradCall grad_call = GradCall::none) {
     if (!sc || !ubo) return GSRT_E_ARG;
     if (ubo->width == 0 || ubo->height == 0 || ubo->width > 32768 || ubo->height > 32768)
         return fail(sc->ctx, GSRT_E_ARG, "bad frame size");
+    if (mode & GSRT_FLAG_OPACITY_GRAD) {  // a whole COR colour frame that scatters its gradient to the opacities it blends
+        const char* why = nullptr;
+        if (grad_call != GradCall::opacity)
+            why = "GSRT_FLAG_OPACITY_GRAD: only through gsrt_render_opacity_grad (the gradient image goes there)";
+        else if ((mode & 0xffu) != GSRT_MODE_COR) why = "GSRT_FLAG_OPACITY_GRAD: COR frames only";
+        else if (mode & GSRT_FLAG_STATS) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_STATS";
+        else if (mode & GSRT_FLAG_OUT_DUMP8) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_OUT_DUMP8";
+        else if (mode & GSRT_FLAG_DEPTH) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_DEPTH";
+        else if (mode & GSRT_FLAG_FEATURES) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_FEATURES";
+        else if (mode & GSRT_FLAG_FEATURE_GRAD) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_FEATURE_GRAD";
+        else if (mode & GSRT_FLAG_SH_GRAD) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_SH_GRAD";
+        else if (sc->ntri) why = "GSRT_FLAG_OPACITY_GRAD: not for a scene with a triangle mesh";
+        if (why) return fail(sc->ctx, GSRT_E_ARG, why);
+    }
     if (mode & GSRT_FLAG_SH_GRAD) {  // a whole COR colour frame that scatters its gradient to the SH rows it blends
         const char* why = nullptr;
         if (grad_call != GradCall::sh) why = "GSRT_FLAG_SH_GRAD: only through gsrt_render_sh_grad (the gradient image goes there)";
@@ -805,7 +820,7 @@ static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32
     }
     if ((mode & 0xffu) > GSRT_MODE_COR ||
         (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH | GSRT_FLAG_FEATURES | GSRT_FLAG_FEATURE_GRAD |
-                  GSRT_FLAG_SH_GRAD)))
+                  GSRT_FLAG_SH_GRAD | GSRT_FLAG_OPACITY_GRAD)))
         return fail(sc->ctx, GSRT_E_ARG, "bad mode");
     if ((mode & 0xffu) == GSRT_MODE_COR && ubo->samples == 0) return fail(sc->ctx, GSRT_E_ARG, "samples == 0");
     if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
@@ -849,6 +864,7 @@ struct GradFrame {
     float* d_rows;       // the zeroed gradient table, n rows of 16 floats
     uint32_t channels;
     bool sh = false;     // a GSRT_FLAG_SH_GRAD frame's: the RGBA frame's gradient (channels = 4), n rows of 48 floats
+    bool opacity = false;  // a GSRT_FLAG_OPACITY_GRAD frame's: the RGBA frame's gradient (channels = 4), the table itself, n floats
 };
 
 // a frame's device outputs: a caller fills the ones its frame has, the others stay nullptr
@@ -865,7 +881,10 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
     float* const d_rgba = out.rgba;
     gsrt_raystate* const d_rs = out.rs;
     gsrt_status s = check_render_args(sc, ubo, mode,
-                                      !out.grad ? GradCall::none : out.grad->sh ? GradCall::sh : GradCall::feature);
+                                      !out.grad            ? GradCall::none
+                                      : out.grad->opacity ? GradCall::opacity
+                                      : out.grad->sh      ? GradCall::sh
+                                                          : GradCall::feature);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
@@ -878,7 +897,7 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
     // ray states are one buffer, so frames that write them stay in order; so are the depth image (GSRT_FLAG_DEPTH) and
     // the feature image (GSRT_FLAG_FEATURES) and a gradient frame's table (GSRT_FLAG_FEATURE_GRAD)
     const bool depth = (mode & GSRT_FLAG_DEPTH) != 0, feat = (mode & GSRT_FLAG_FEATURES) != 0;
-    const bool grad = (mode & (GSRT_FLAG_FEATURE_GRAD | GSRT_FLAG_SH_GRAD)) != 0;
+    const bool grad = (mode & (GSRT_FLAG_FEATURE_GRAD | GSRT_FLAG_SH_GRAD | GSRT_FLAG_OPACITY_GRAD)) != 0;
     const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth && !feat && !grad &&
                       gsrt::use_slot_streams(ctx, false);
     if (slot) {
@@ -923,6 +942,7 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
             rsy.grad_rows = out.grad->d_rows;
             rsy.grad_channels = out.grad->channels;
             rsy.grad_sh = out.grad->sh;
+            rsy.grad_opacity = out.grad->opacity;
         }
         s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat && !grad ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
@@ -1151,6 +1171,58 @@ gsrt_status gsrt_render_sh_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
         GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
     s = gsrt_render_sh_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in,
                                   out_dev ? grad_table : ctx->d_grad_out, accumulate);
+    return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
+                                     sizeof(float) * out_floats, "gradient table download failed"}});
+}
+
+// An opacity gradient frame: the table is n floats in API order, so the render kernel adds to the caller's device table
+// itself (zeroed first on the render stream unless it accumulates) and nothing is compacted; a host image and a host table
+// go through the gradient frames' buffers of the ctx, in order with the other gradient frames on the render stream.
+static gsrt_status check_opacity_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const float* grad_image,
+                                           const float* grad_table) {
+    if (!sc || !ubo) return GSRT_E_ARG;
+    if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: grad_image is NULL");
+    if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: grad_table is NULL");
+    return check_render_args(sc, ubo, mode, GradCall::opacity);
+}
+
+gsrt_status gsrt_render_opacity_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                           const float* d_grad_image, float* d_grad_table, int accumulate) {
+    mode |= GSRT_FLAG_OPACITY_GRAD;
+    gsrt_status s = check_opacity_grad_args(sc, ubo, mode, d_grad_image, d_grad_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (!accumulate && sc->n) GSRT_HIP(ctx, hipMemsetAsync(d_grad_table, 0, sizeof(float) * sc->n, ctx->stream));
+    GradFrame gf{d_grad_image, d_grad_table, 4u};
+    gf.opacity = true;
+    FrameOut out;
+    out.grad = &gf;
+    return render_async(sc, ubo, mode, k, out);
+}
+
+gsrt_status gsrt_render_opacity_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                     const float* grad_image, float* grad_table, int accumulate) {
+    mode |= GSRT_FLAG_OPACITY_GRAD;
+    gsrt_status s = check_opacity_grad_args(sc, ubo, mode, grad_image, grad_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
+    if (accumulate && !out_dev) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: accumulate needs a device grad_table");
+    const size_t in_floats = (size_t)ubo->width * ubo->height * 4, out_floats = sc->n;
+    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
+    }
+    if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_out, &ctx->grad_out_floats, out_floats ? out_floats : 1)) != GSRT_OK) return s;
+    }
+    if (!in_dev)
+        GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
+    s = gsrt_render_opacity_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in,
+                                       out_dev ? grad_table : ctx->d_grad_out, accumulate);
     return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
                                      sizeof(float) * out_floats, "gradient table download failed"}});
 }

@@ -358,6 +358,8 @@ gsrt_status gsrt_render_sharded_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint3
     if (mode & GSRT_FLAG_FEATURE_GRAD)
         return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: whole frames only, not sharded ones");
     if (mode & GSRT_FLAG_SH_GRAD) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: whole frames only, not sharded ones");
+    if (mode & GSRT_FLAG_OPACITY_GRAD)
+        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: whole frames only, not sharded ones");
     if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     (void)hipSetDevice(ctx->device);
@@ -806,6 +808,8 @@ static gsrt_status render_emulated(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t
     if (mode & GSRT_FLAG_FEATURE_GRAD)
         return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: whole frames only, not sharded ones");
     if (mode & GSRT_FLAG_SH_GRAD) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: whole frames only, not sharded ones");
+    if (mode & GSRT_FLAG_OPACITY_GRAD)
+        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: whole frames only, not sharded ones");
     const bool d8 = (mode & GSRT_FLAG_OUT_DUMP8) != 0;
     if (d8 && ((mode & 0xffu) != GSRT_MODE_COR || (mode & GSRT_FLAG_STATS)))
         return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OUT_DUMP8: COR frames without GSRT_FLAG_STATS only");

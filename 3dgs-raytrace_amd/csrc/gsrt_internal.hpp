@@ -159,6 +159,7 @@ struct gsrt_ctx {
     // GSRT_FLAG_FEATURE_GRAD frames (one set of buffers: such frames stay in order): the gradient table the render
     // kernel adds to, n rows of 16 floats; a host gradient image's device copy; a host table's compact device copy.
     // GSRT_FLAG_SH_GRAD frames use the same three, in order with them: n rows of 48 floats, W x H x 4, n x 48
+    // GSRT_FLAG_OPACITY_GRAD frames use the last two (W x H x 4, n): the render kernel adds to the device table itself
     float* d_grad_rows = nullptr;
     size_t grad_rows_floats = 0;
     float* d_grad_in = nullptr;
@@ -366,7 +367,10 @@ struct RenderSync {
     const float* grad_in = nullptr;
     float* grad_rows = nullptr;
     uint32_t grad_channels = 0;
+    // GSRT_FLAG_OPACITY_GRAD (grad_opacity): the upstream gradient of the RGBA frame (grad_channels = 4) and the caller's
+    // own device table, n floats, which the frame adds to
     bool grad_sh = false;
+    bool grad_opacity = false;
 };
 gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_rgba,
                           gsrt_raystate* d_rs, RenderSync* sync = nullptr);

@@ -67,6 +67,9 @@ constexpr bool kGroupRegSort = GSRT_GROUP_REGSORT != 0;
 #ifndef GSRT_SHGRAD_WAVES
 #define GSRT_SHGRAD_WAVES 4
 #endif
+#ifndef GSRT_OPGRAD_WAVES
+#define GSRT_OPGRAD_WAVES 4
+#endif
 constexpr uint32_t kFront = 128;   // frontier entries per super-group
 
 
@@ -126,6 +129,8 @@ struct RenderArgs {
     // An SH gradient frame (GSRT_FLAG_SH_GRAD, k_render_cor shgrad) uses the same three: grad_in is the upstream gradient of
     // the RGBA frame (grad_channels = 4, the image's stride; alpha's is not read), grad_rows one 192-B row of 48 floats
     // per Gaussian id, [rgb][coef] as the SH rows are (compacted by launch_sh_grad_compact)
+    // An opacity gradient frame (GSRT_FLAG_OPACITY_GRAD, k_render_cor opgrad) likewise: grad_in is the upstream gradient of
+    // the RGBA frame, all four channels read, and grad_rows the caller's own table, one float per Gaussian id
     const float* grad_in;
     float* grad_rows;
     uint32_t grad_channels;
@@ -725,12 +730,15 @@ static_assert(sizeof(Stage) == kGroup * 256 && sizeof(Stage) % 1024 == 0, "whole
 // ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
 // with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
 // or a gradient frame, the backward of a feature frame to the feature table (GSRT_FLAG_FEATURE_GRAD, grad_rows). SH: the
-// scene's SH-3 rows are blended; LUT: the ExpLUT instead of the exact exponential. Eighteen kernels: {plain, stats,
-// depth} x SH x LUT and {feat, grad, shgrad} x LUT, named by cor_kernel and nowhere else. What a kind adds (blend_hit)
+// scene's SH-3 rows are blended; LUT: the ExpLUT instead of the exact exponential. Twenty-two kernels: {plain, stats,
+// depth, opgrad} x SH x LUT and {feat, grad, shgrad} x LUT, named by cor_kernel and nowhere else. What a kind adds (blend_hit)
 // sits under if constexpr on these members: the other kinds' code does not change. The RGBA of feat and grad is the
 // no-SH frame's. shgrad (GSRT_FLAG_SH_GRAD, grad_rows with RenderSync::grad_sh) is the backward of a plain colour frame
-// to the SH table: SH rows always, and the plain frame's RGBA.
-enum class CorKind { plain, stats, depth, feat, grad, shgrad };
+// to the SH table: SH rows always, and the plain frame's RGBA. opgrad (GSRT_FLAG_OPACITY_GRAD, grad_rows with
+// RenderSync::grad_opacity) is the backward of a plain colour frame to the opacities, with or without SH rows: every pass
+// shades its rays twice (k_render_cor), the plain blend for the ray's finals and then the same blend again with the
+// gradient terms; the plain frame's RGBA.
+enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad };
 // waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
 // spill to scratch)
 constexpr uint32_t kFeatWaves = 4;
@@ -741,15 +749,22 @@ constexpr uint32_t kFeatWaves = 4;
 constexpr uint32_t kGradWaves = GSRT_GRAD_WAVES;
 // and for the two shgrad kernels, likewise (GSRT_SHGRAD_WAVES)
 constexpr uint32_t kShGradWaves = GSRT_SHGRAD_WAVES;
+// and for the four opgrad kernels, likewise (GSRT_OPGRAD_WAVES): 127 VGPRs with SH rows and 94 / 95
+// without, no scratch at 4; at 5 both SH kernels spill (63 and 66 VGPRs to scratch), at 6 two kernels do
+constexpr uint32_t kOpGradWaves = GSRT_OPGRAD_WAVES;
 struct NoPayload {};
 struct DepthPayload { float D; };      // sum of z w over the blended hits (expected view depth, premultiplied)
 struct ChannelPayload { float F[16]; };  // feat: sum of f_k w over the blended hits per channel; grad: the lane's G_k / ns
 struct RgbGradPayload { float G[3]; };   // shgrad: the lane's upstream colour gradient G_ch / ns
+// opgrad: the lane's upstream gradient G_ch / ns of all four channels, and in the second sweep the ray's finals of the
+// first: the colour C_ch and the transmittance T_end
+struct OpGradPayload { float G[4], fin[4]; };
 template <CorKind K, bool SH, bool LUT>
 struct CorVariant {
     static constexpr bool sh = SH, lut = LUT;
     static constexpr bool stats = K == CorKind::stats, depth = K == CorKind::depth;
     static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad, shgrad = K == CorKind::shgrad;
+    static constexpr bool opgrad = K == CorKind::opgrad;
     static_assert(!(feat || grad) || !SH, "feature and gradient frames evaluate no SH");
     static_assert(!shgrad || SH, "an SH gradient frame blends the SH rows");
     // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
@@ -757,7 +772,7 @@ struct CorVariant {
     // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
     // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before blend_stage: left at 4 it takes 102.
     static constexpr uint32_t waves =
-        shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
+        opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
         : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
     // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
     // stage, and DMA instructions per stage (one piece per lane each)
@@ -766,7 +781,8 @@ struct CorVariant {
     static constexpr uint32_t stage_ops = (stage_pieces + 63) / 64;
     // what the kind adds to a ray's state (CorRay) and to a pixel's sums (PixelSums); empty where it adds nothing
     using RayPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat || grad, ChannelPayload,
-                                          std::conditional_t<shgrad, RgbGradPayload, NoPayload>>>;
+                                          std::conditional_t<shgrad, RgbGradPayload,
+                                          std::conditional_t<opgrad, OpGradPayload, NoPayload>>>>;
     using SumPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat, ChannelPayload, NoPayload>>;
 };
 
@@ -940,9 +956,43 @@ struct ShGradStage {
     float sums[3][kGroup] = {};
     uint32_t mask = 0;  // bit c: some lane blended candidate c
 };
+// opgrad only, second sweep, likewise: the opacity gradient table (one float per Gaussian id), and a stage's share: per
+// candidate the lane's own term d e (+0 where the lane does not blend it or its alpha was clamped), summed over the wave
+// once per stage (opgrad_stage_sums). e, open: the hit shade_stage hands to blend_hit, its exponential and whether
+// fl(|o| e) < 0.99f, i.e. whether alpha is |o| e and not the clamp's constant
+struct OpGradDst { float* rows; };
+struct OpGradStage {
+    const uint32_t* ids;
+    OpGradDst dst;
+    float t[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t mask = 0;  // bit c: some lane blended candidate c
+    float e = 0.0f;
+    bool open = false;
+};
 // a stage's share of a round's destination
 __device__ GSRT_INLINE GradStage stage_of(const uint32_t* ids, const GradDst& dst) { return GradStage{ids, dst}; }
 __device__ GSRT_INLINE ShGradStage stage_of(const uint32_t* ids, const ShGradDst& dst) { return ShGradStage{ids, dst}; }
+__device__ GSRT_INLINE OpGradStage stage_of(const uint32_t* ids, const OpGradDst& dst) { return OpGradStage{ids, dst}; }
+// opgrad: a stage's four terms per lane (t[c]: candidate c) to the wave's sums, transposed: every lane l returns the wave's
+// sum of candidate l & 3. Inside a quad the butterfly of grad_row_sums' last two steps (partners i ^ 2 and i ^ 1: a lane
+// keeps the half its own lane bit names and sends the other), then the four quads of a row by two row rotations, which
+// keep l & 3, and the four rows by the two permlane swaps of a value with itself (grad_stage_sums): first + second
+// is then the sum of both halves on every lane.
+__device__ GSRT_INLINE float opgrad_stage_sums(const float (&t)[kGroup]) {
+    static_assert(kGroup == 4, "one candidate per lane of a quad");
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const bool b1 = lane_of(0xCCCCCCCCCCCCCCCCull), b0 = lane_of(0xAAAAAAAAAAAAAAAAull);
+    float c[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) c[k] = (b1 ? t[2 + k] : t[k]) + dpp_from<0x4E>(b1 ? t[k] : t[2 + k]);
+    float v = (b0 ? c[1] : c[0]) + dpp_from<0xB1>(b0 ? c[0] : c[1]);  // the quad's sum of candidate l & 3
+    v = v + dpp_from<0x128>(v);  // row_ror:8
+    v = v + dpp_from<0x124>(v);  // row_ror:4: the row's sum
+    const u32x2 p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    const float u = __uint_as_float(p.x) + __uint_as_float(p.y);  // rows 0 + 1 below lane 32, rows 2 + 3 above
+    const u32x2 q = __builtin_amdgcn_permlane32_swap(__float_as_uint(u), __float_as_uint(u), false, false);
+    return __uint_as_float(q.x) + __uint_as_float(q.y);
+}
 template <class T>
 __device__ GSRT_INLINE T& only(T& t) { return t; }  // the one element of a pack that holds one
 // z: the candidate's view depth (SplatRec::depth), already in a register from shade_stage's read of the record (a read
@@ -957,7 +1007,8 @@ __device__ GSRT_INLINE T& only(T& t) { return t; }  // the one element of a pack
 template <class V, class... G>
 __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z, float alpha, uint64_t contrib,
                                           CorRay<V>& ray, G&... grad) {
-    static_assert(sizeof...(G) == (V::grad || V::shgrad ? 1 : 0), "a gradient frame's stage, and only that");
+    static_assert(sizeof...(G) == (V::grad || V::shgrad ? 1 : 0) || (V::opgrad && sizeof...(G) == 1),
+                  "a gradient frame's stage, and only that (opgrad: none in its first sweep)");
     const float tn = ray.T * (1.0f - alpha);
     const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
     const uint64_t term = contrib & low;
@@ -993,6 +1044,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
             }
             gs.mask |= 1u << c;
         }
+        if constexpr (V::opgrad && sizeof...(G) == 1) only(grad...).mask |= 1u << c;  // the terms: below, with the blend
         if (lane_of(blend)) {
             const float w = alpha * ray.T;
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
@@ -1014,6 +1066,18 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
                     ray.k.F[4 * q + 3] = fmaf(f.w, w, ray.k.F[4 * q + 3]);
                 }
             }
+            if constexpr (V::opgrad && sizeof...(G) == 1) {
+                // second sweep: d(frame . G) / d(alpha) of this hit from the ray's finals (ray.k.fin, the first sweep's)
+                // and the running colour after this hit, times d(alpha) / d|o| = e where the clamp let |o| e through;
+                // ray.T is still T_i. A select: the lanes that do not blend c keep the stage's +0 in t[c]
+                OpGradStage& gs = only(grad...);
+                const float r = 1.0f / (1.0f - alpha);  // alpha <= 0.99
+                float d = (ray.k.G[3] * ray.k.fin[3]) * r;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch)
+                    d = d + ray.k.G[ch] * (ray.T * col[ch] - (ray.k.fin[ch] - ray.C[ch]) * r);
+                gs.t[c] = gs.open ? d * gs.e : 0.0f;
+            }
             ray.T = tn;
             if (V::stats) ++ray.blended;
         }
@@ -1034,7 +1098,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
 // colours of the candidates that lane blends. A stage so runs as many SH evaluations as its busiest lane blends
 // candidates, not one per candidate that some lane blends.
 template <class V>
-constexpr bool kShPerLane = V::sh && !V::stats && !V::shgrad;
+constexpr bool kShPerLane = V::sh && !V::stats && !V::shgrad && !V::opgrad;
 struct StageBlends {
     uint64_t blend[kGroup] = {0, 0, 0, 0};  // per candidate the lanes that blend it (ballots: SGPR pairs)
     float w[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};  // alpha T of the candidate on those lanes
@@ -1133,6 +1197,7 @@ __device__ GSRT_INLINE void blend_stage(const Stage* stg, const StageBlends& sb,
 // grad: the stage's terms w G go to the gradient table (go.dst) in one atomic wave-instruction, lane 16 c + ch adding
 // the wave's sum for candidate c and channel ch, masked to the candidates some lane blended and to the channels in use.
 // shgrad: likewise three wave-instructions, one per colour channel, lane 16 c + q adding coefficient q.
+// opgrad, second sweep (the one with a stage in G): one wave-instruction, lane c adding candidate c's sum.
 template <class V, bool FULL, class... G>
 __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay<V>& ray, G... grad) {
     constexpr bool LUT = V::lut;
@@ -1193,6 +1258,10 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
+            if constexpr (V::opgrad && sizeof...(G) == 1) {  // what the hit's term needs besides the blend's own values
+                only(grad...).e = e;
+                only(grad...).open = fabsf(q1.w) * e < 0.99f;
+            }
             uint64_t stopped;
             if constexpr (kShPerLane<V>) stopped = weigh_hit<V>(c, alpha, contrib, ray, sb);
             else stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad...);
@@ -1241,6 +1310,22 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
                     float* row = go.dst.rows + (size_t)id * 48u + q;
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) atomicAdd(row + 16 * ch, sum[ch]);  // no-return global_atomic_add_f32
+                }
+            }
+        }
+        if constexpr (V::opgrad && sizeof...(G) == 1) {
+            // one atomic wave-instruction per stage: lane c < kGroup adds the wave's sum of candidate c's terms to the
+            // table's entry of its id, masked to the candidates some lane blended
+            const OpGradStage& go = only(grad...);
+            const uint32_t gmask = go.mask;
+            if (gmask) {  // wave-uniform: a stage no lane blended adds nothing
+                const float sum = opgrad_stage_sums(go.t);
+                const uint32_t l = lane_here();
+                // a blended candidate c is below m, so ids[c] is an entry of the round's list: its id is below n and its
+                // float inside the table
+                if (l < kGroup && ((gmask >> l) & 1u)) {
+                    const uint32_t id = lds_read_settled(go.ids + l);
+                    atomicAdd(go.dst.rows + id, sum);  // no-return global_atomic_add_f32
                 }
             }
         }
@@ -1910,6 +1995,18 @@ __device__ GSRT_INLINE CorRay<V> cor_ray(const CorTile::Pixel& p, uint32_t S, ui
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) ray.k.G[ch] = p.valid ? over_samples(gi[ch], ns) : 0.0f;
     }
+    if constexpr (V::opgrad) {
+        // the pixel's upstream gradient of all four channels (alpha depends on opacity), scaled once by 1 / ns; invalid
+        // lanes hold +0. The finals are the first sweep's results (k_render_cor sets them before the second)
+        const KArgs& K = kargs();
+        const uint32_t ns = S * passes;
+        const float* gi = K.a.grad_in + ((size_t)p.y * K.a.width + p.x) * 4;
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) {
+            ray.k.G[ch] = p.valid ? over_samples(gi[ch], ns) : 0.0f;
+            ray.k.fin[ch] = 0.0f;
+        }
+    }
     ray.active = p.valid;
     if (!p.valid) ray.pxs = __builtin_nanf("");  // see blend_hit
     ray.cand = ray.blended = ray.term = 0;
@@ -2074,46 +2171,67 @@ void k_render_cor(const KArgs karg) {
 #endif
     for (uint32_t pass = 0; pass < passes; ++pass) {
         CorRay<V> ray = cor_ray<V>(tile.pixel(), S, pass, passes);
-        uint64_t lo = 0;
-        bool has_lo = false;
-        uint32_t gpos = 0;  // with group lists: where this tile resumes in its group's sorted list
-        for (;;) {
+        // opgrad: two sweeps over the same rounds. The first is the plain blend and gives the pass its results and the
+        // ray its finals; the second sets the ray up again, restarts the rounds from the tile's first list
+        // (round_from_list issues it again: prefetched is false by then) and blends the same hits in the same order with
+        // the same arithmetic, so that every test falls as it fell, now with the gradient terms (blend_hit)
+        // (a do-while whose condition is constant false for every other kind: their loop nest is what it was)
+        [[maybe_unused]] uint32_t sweep = 0;
+        do {
+            uint64_t lo = 0;
+            bool has_lo = false;
+            uint32_t gpos = 0;  // with group lists: where this tile resumes in its group's sorted list
+            for (;;) {
 #ifdef GSRT_DIAG
-            const unsigned long long d0 = __builtin_amdgcn_s_memtime();
-            if (!has_lo) diag_setup += d0 - (pass == 0 ? diag_entry : diag_last);
+                const unsigned long long d0 = __builtin_amdgcn_s_memtime();
+                if (!has_lo) diag_setup += d0 - (pass == 0 ? diag_entry : diag_last);
 #endif
-            Collected cl;
-            bool listed = true;
-            if (kargs().a.prelisted && !has_lo) {
-                cl = round_from_list(tile, prefetched, ids, lhdr, lo, gpos);
-            } else {
-                listed = false;
-                if (kargs().a.use_groups) cl = round_from_group(tile, ids, lo, gpos, listed);
+                Collected cl;
+                bool listed = true;
+                if (kargs().a.prelisted && !has_lo) {
+                    cl = round_from_list(tile, prefetched, ids, lhdr, lo, gpos);
+                } else {
+                    listed = false;
+                    if (kargs().a.use_groups) cl = round_from_group(tile, ids, lo, gpos, listed);
+                }
+                if (!listed) cl = round_from_traversal<V>(tile, keys, stack, ids, lo, has_lo, restarts);
+#ifdef GSRT_DIAG
+                const unsigned long long d1 = __builtin_amdgcn_s_memtime();
+                diag_collect += d1 - d0;
+#endif
+                ++st_rounds;
+                if (cl.total > maxc) maxc = cl.total;
+                bool live;
+                if constexpr (V::grad)
+                    live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
+                                           GradDst{kargs().a.grad_rows, kargs().a.grad_channels});
+                else if constexpr (V::shgrad)
+                    live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, ShGradDst{kargs().a.grad_rows});
+                else if constexpr (V::opgrad)
+                    live = sweep == 0 ? shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp)
+                                      : shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
+                                                        OpGradDst{kargs().a.grad_rows});
+                else
+                    live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
+#ifdef GSRT_DIAG
+                diag_last = __builtin_amdgcn_s_memtime();
+                diag_shade += diag_last - d1;
+#endif
+                if (!cl.more || !live) break;
+                has_lo = true;  // lo = the last (largest) key of this round
+                __syncthreads();
             }
-            if (!listed) cl = round_from_traversal<V>(tile, keys, stack, ids, lo, has_lo, restarts);
-#ifdef GSRT_DIAG
-            const unsigned long long d1 = __builtin_amdgcn_s_memtime();
-            diag_collect += d1 - d0;
-#endif
-            ++st_rounds;
-            if (cl.total > maxc) maxc = cl.total;
-            bool live;
-            if constexpr (V::grad)
-                live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
-                                       GradDst{kargs().a.grad_rows, kargs().a.grad_channels});
-            else if constexpr (V::shgrad)
-                live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, ShGradDst{kargs().a.grad_rows});
-            else
-                live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
-#ifdef GSRT_DIAG
-            diag_last = __builtin_amdgcn_s_memtime();
-            diag_shade += diag_last - d1;
-#endif
-            if (!cl.more || !live) break;
-            has_lo = true;  // lo = the last (largest) key of this round
-            __syncthreads();
-        }
-        sums.take(ray);
+            if constexpr (V::opgrad) {
+                if (sweep == 0) {
+                    sums.take(ray);  // once per pass, from the first sweep's values
+                    const float fin[4] = {ray.C[0], ray.C[1], ray.C[2], ray.T};
+                    ray = cor_ray<V>(tile.pixel(), S, pass, passes);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) ray.k.fin[q] = fin[q];
+                }
+            }
+        } while (V::opgrad && ++sweep < 2);
+        if constexpr (!V::opgrad) sums.take(ray);
         if (passes > 1) {  // then S == 1 (make_plan): the lane's pixel accumulates its passes in order, prev + pass
             const CorTile::Pixel p = tile.pixel();
             if (p.valid) {
@@ -2970,6 +3088,7 @@ static CorLaunch cor_kernel(CorKind kind, bool sh, bool lut) {
         case CorKind::feat: return cor_kernel_of<CorKind::feat>(sh, lut);
         case CorKind::grad: return cor_kernel_of<CorKind::grad>(sh, lut);
         case CorKind::shgrad: return cor_kernel_of<CorKind::shgrad>(sh, lut);
+        case CorKind::opgrad: return cor_kernel_of<CorKind::opgrad>(sh, lut);
     }
     return nullptr;
 }
@@ -3024,7 +3143,7 @@ static gsrt_status launch_cor(gsrt_scene* sc, const RenderPlan& plan, const Fram
     const hipStream_t st = ctx->stream;
     FrameSlot& S = ctx->slot[f.b];
     const RenderArgs& A = k.a;
-    const CorKind kind = A.grad_rows ? (sync->grad_sh ? CorKind::shgrad : CorKind::grad)
+    const CorKind kind = A.grad_rows ? (sync->grad_opacity ? CorKind::opgrad : sync->grad_sh ? CorKind::shgrad : CorKind::grad)
                          : A.feat_out ? CorKind::feat : A.depth_out ? CorKind::depth
                          : f.stats   ? CorKind::stats : CorKind::plain;
     const CorLaunch render = cor_kernel(kind, sc->d_sh != nullptr, (plan.mode & GSRT_FLAG_LUT) != 0);

@@ -25,6 +25,7 @@ MODE_REF, MODE_COR = 0, 1
 FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8, FLAG_DEPTH, FLAG_FEATURES = 0x100, 0x200, 0x400, 0x800, 0x1000
 FLAG_FEATURE_GRAD = 0x2000
 FLAG_SH_GRAD = 0x4000
+FLAG_OPACITY_GRAD = 0x8000
 MAX_FEATURES = 16  # GSRT_MAX_FEATURES
 DUMP8_ESCAPE = 1 << 30  # GSRT_DUMP8_ESCAPE
 SYNTH_COR, SYNTH_REF, SYNTH_NEEDLE = 0, 1, 2
@@ -67,6 +68,7 @@ EXPORTS = [
     "gsrt_scene_set_features", "gsrt_scene_features", "gsrt_render_features", "gsrt_render_features_async",
     "gsrt_feature_buffer", "gsrt_render_feature_grad", "gsrt_render_feature_grad_async", "gsrt_group_order",
     "gsrt_unit_order", "gsrt_scene_set_sh", "gsrt_render_sh_grad", "gsrt_render_sh_grad_async",
+    "gsrt_render_opacity_grad", "gsrt_render_opacity_grad_async",
 ]
 
 
@@ -182,6 +184,8 @@ def _load():
         "gsrt_scene_set_sh": ([P, P], i32),
         "gsrt_render_sh_grad": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_render_sh_grad_async": ([P, P, u32, u32, P, P, i32], i32),
+        "gsrt_render_opacity_grad": ([P, P, u32, u32, P, P, i32], i32),
+        "gsrt_render_opacity_grad_async": ([P, P, u32, u32, P, P, i32], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -948,6 +952,28 @@ class Scene:
         ordinary device memory) are device addresses; accumulate adds to the table instead of writing it."""
         _check(lib.gsrt_render_sh_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
                                              ctypes.c_void_p(d_grad_table or None), 1 if accumulate else 0), self.ctx)
+
+    def opacity_grad(self, ubo, grad_image, mode=MODE_COR, k=0):
+        """The backward of a colour frame to the opacities (gsrt_render_opacity_grad): grad_image is the upstream
+        gradient of the RGBA frame, (H, W, 4) float32, or (H, W, 3), padded with a zero alpha gradient; returns the (n,)
+        gradient with respect to each Gaussian's opacity (the definition is in gsrt.h). A hit whose alpha the clamp at
+        0.99 cut contributes +0. The sum's order is unspecified (float atomics)."""
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        g = np.asarray(grad_image, np.float32)
+        if g.ndim != 3 or g.shape[:2] != (H, W) or g.shape[2] not in (3, 4):
+            raise GsrtError(E_ARG, "opacity_grad: an (H, W, 4) or (H, W, 3) array")
+        if g.shape[2] == 3:
+            g = np.concatenate([g, np.zeros((H, W, 1), np.float32)], axis=2)
+        g = np.ascontiguousarray(g)
+        out = np.zeros(self.n, np.float32)
+        _check(lib.gsrt_render_opacity_grad(self.handle, _p(ubo), mode, k, _p(g), _p(out), 0), self.ctx)
+        return out
+
+    def opacity_grad_async(self, ubo, d_grad_image: int, d_grad_table: int, accumulate=False, mode=MODE_COR, k=0):
+        """Enqueue one opacity gradient frame on ctx.stream: d_grad_image (W*H*4 floats) and d_grad_table (n floats,
+        ordinary device memory) are device addresses; accumulate adds to the table instead of writing it."""
+        _check(lib.gsrt_render_opacity_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
+                                                  ctypes.c_void_p(d_grad_table or None), 1 if accumulate else 0), self.ctx)
 
     def render_sharded(self, ubo, mode=MODE_COR, k=0, want_image=True):
         W, H = int(ubo["width"][0]), int(ubo["height"][0])

@@ -97,3 +97,70 @@ def render_colour(scene, ubo, sh, mode=MODE_COR, k=0):
     attached arrays, streamed pages) and its SH rows must stay as they were in the forward until backward has run, or
     the gradient is that of another frame. The forward leaves `sh` as the scene's SH table."""
     return _RenderColour.apply(sh, scene, ubo, mode, k)
+
+
+def _device_params(scene, device):
+    """The scene's GaussParam array as an (n, 12) torch tensor on `device`, made once per scene from Scene.download and
+    kept on the scene: render_rgba writes the opacities into its column 3 and hands it to Scene.update by address."""
+    t = getattr(scene, "_autograd_params", None)
+    if t is None or t.device != device:
+        params, _ = scene.download()
+        t = torch.from_numpy(params).to(device)
+        scene._autograd_params = t
+    return t
+
+
+class _RenderRgba(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, opacity, sh, scene, ubo, mode, k):
+        if opacity.dtype != torch.float32 or not opacity.is_cuda or tuple(opacity.shape) != (scene.n,):
+            raise ValueError("render_rgba: opacity must be an (n,) float32 tensor on the GPU")
+        if sh is not None and (sh.dtype != torch.float32 or not sh.is_cuda or
+                               tuple(sh.shape) not in ((scene.n, 16, 3), (scene.n, 48))):
+            raise ValueError("render_rgba: sh must be an (n, 16, 3) or (n, 48) float32 tensor on the GPU")
+        params = _device_params(scene, opacity.device)
+        params[:, 3] = opacity.detach()
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        rgba = torch.empty((H, W, 4), dtype=torch.float32, device=opacity.device)
+        table = None if sh is None else sh.contiguous()
+        torch.cuda.current_stream(opacity.device).synchronize()
+        if table is not None:
+            scene.set_sh(table.data_ptr())  # copied into the scene's own rows
+        scene.update(params=params.data_ptr())  # copied; the AABBs do not depend on opacity, so nothing is refitted
+        scene.render_async(ubo, mode, k, rgba.data_ptr())
+        scene.ctx.synchronize()
+        ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
+        ctx.sh_shape = None if sh is None else tuple(sh.shape)
+        return rgba
+
+    @staticmethod
+    def backward(ctx, grad_rgba):
+        g = grad_rgba.to(torch.float32).contiguous()
+        d_op = torch.empty((ctx.scene.n,), dtype=torch.float32, device=g.device)
+        d_sh = None
+        if ctx.sh_shape is not None and ctx.needs_input_grad[1]:
+            d_sh = torch.empty(ctx.sh_shape, dtype=torch.float32, device=g.device)
+        torch.cuda.current_stream(g.device).synchronize()
+        ctx.scene.opacity_grad_async(ctx.ubo, g.data_ptr(), d_op.data_ptr(), False, ctx.mode, ctx.k)
+        if d_sh is not None:
+            ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
+        ctx.scene.ctx.synchronize()
+        return d_op, d_sh, None, None, None, None
+
+
+def render_rgba(scene, ubo, opacity, sh=None, mode=MODE_COR, k=0):
+    """One colour frame of the opacities `opacity` ((n,) float32 GPU tensor) and, when given, the SH table `sh` ((n, 16, 3)
+    or (n, 48) float32 GPU tensor, [gauss][coef][rgb]) as a torch tensor rgba[H, W, 4], differentiable with respect to
+    both: the backward is Scene.opacity_grad_async of the upstream gradient, all four channels, and Scene.sh_grad_async
+    of the same gradient when `sh` requires one. The forward writes `opacity` into column 3 of a device copy of the
+    scene's GaussParam array (made once per scene from Scene.download and kept on the scene) and passes it to
+    Scene.update; with `sh` it also calls Scene.set_sh. sh=None leaves the scene's SH rows as they are, and only the
+    opacity gradient is produced. The gradient is that of gsrt.h: hits whose alpha the clamp at 0.99 cut contribute 0,
+    and the set of hits, their order and the stop are not differentiated.
+    Blocking synchronisation on both sides: torch's current stream before each library call, Context.synchronize()
+    after it.
+    The backward renders the scene again: it keeps a copy of `ubo`, but the scene's geometry (Scene.update, refits,
+    attached arrays, streamed pages), its opacities and its SH rows must stay as they were in the forward until backward
+    has run, or the gradient is that of another frame. The forward leaves `opacity` as the scene's opacities and `sh`
+    as its SH table; a geometry change made through Scene.update by the caller is not seen by the kept copy."""
+    return _RenderRgba.apply(opacity, sh, scene, ubo, mode, k)

@@ -80,8 +80,10 @@ enum {
                                    GSRT_FLAG_DEPTH or a sharded entry point; GSRT_E_STATE without a feature table */
     GSRT_FLAG_FEATURE_GRAD = 0x2000, /* whole COR frames: the backward of a feature frame to the feature table; set by
                                        gsrt_render_feature_grad (below) itself, GSRT_E_ARG through every other entry point */
-    GSRT_FLAG_SH_GRAD = 0x4000 /* whole COR frames: the backward of a colour frame to the SH table; set by gsrt_render_sh_grad
-                                  (below) itself, GSRT_E_ARG through every other entry point */
+    GSRT_FLAG_SH_GRAD = 0x4000, /* whole COR frames: the backward of a colour frame to the SH table; set by gsrt_render_sh_grad
+                                   (below) itself, GSRT_E_ARG through every other entry point */
+    GSRT_FLAG_OPACITY_GRAD = 0x8000 /* whole COR frames: the backward of a colour frame to the opacities; set by
+                                       gsrt_render_opacity_grad (below) itself, GSRT_E_ARG through every other entry point */
 };
 /* synthetic cloud kinds */
 enum { GSRT_SYNTH_COR = 0, GSRT_SYNTH_REF = 1, GSRT_SYNTH_NEEDLE = 2 };
@@ -317,7 +319,7 @@ const float* gsrt_feature_buffer(gsrt_ctx* ctx);
  * GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH or GSRT_FLAG_FEATURES with it; sharded entry points; a scene with a mesh; channels
  * out of range; a NULL grad_image or grad_table; the flag passed to gsrt_render / gsrt_render_async (or the depth and
  * feature forms), which have nowhere to take the image.
- * Not provided: gradients with respect to geometry, opacity or the normaliser (sum w); sharded frames; more than
+ * Not provided: gradients with respect to geometry or the normaliser (sum w); sharded frames; more than
  * GSRT_MAX_FEATURES channels.
  * gsrt_render_feature_grad blocks until the table is complete, like gsrt_render. */
 gsrt_status gsrt_render_feature_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
@@ -349,13 +351,47 @@ gsrt_status gsrt_render_feature_grad_async(gsrt_scene* scene, const gsrt_ubo* ub
  * GSRT_E_STATE: a scene without SH rows. GSRT_E_ARG (gsrt_last_error names GSRT_FLAG_SH_GRAD, and the context renders as
  * before): REF mode; GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH, GSRT_FLAG_FEATURES or GSRT_FLAG_FEATURE_GRAD with
  * it; sharded entry points; a scene with a mesh; a NULL grad_image or grad_table; the flag passed to any other entry point.
- * Not provided: gradients with respect to geometry or opacity; sharded frames.
+ * Not provided: gradients with respect to geometry (opacity: gsrt_render_opacity_grad below); sharded frames.
  * gsrt_render_sh_grad blocks until the table is complete, like gsrt_render. */
 gsrt_status gsrt_render_sh_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const float* grad_image,
                                 float* grad_table, int accumulate);
 /* the same, enqueued on gsrt_stream(); device pointers only */
 gsrt_status gsrt_render_sh_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                       const float* d_grad_image, float* d_grad_table, int accumulate);
+/* Opacity gradient frame (GSRT_FLAG_OPACITY_GRAD): the backward of a plain COR colour frame (RGBA) with respect to each
+ * Gaussian's opacity, gsrt_gauss_param::center_opacity[3], i.e. the opacity of gsrt_scene_from_model. The blend is ordered
+ * front to back, so every ray is shaded twice in the same order: once for its final colour and transmittance, then again,
+ * where the colour behind a hit is the final colour minus the running colour.
+ * grad_image is the upstream gradient G of the RGBA frame, W*H*4 floats laid out as the frame is; all four channels are
+ * used (alpha depends on opacity). grad_table receives n floats, [gauss].
+ * For sample ray (p, s) with blended hits i = 1..N in the blend's order, with the blend's own alpha_i, T_i (the
+ * transmittance before hit i) and w_i = alpha_i T_i, col_{i,ch} the clamped SH colour the blend used (1 without SH rows),
+ * the ray's finals C_ch = sum_i col_{i,ch} w_i and T_end = T_{N+1}:
+ *     Cafter_{i,ch} = the blend's running colour after hit i (fma(col, w, C))
+ *     d_i  = sum_ch Gs[ch] * (T_i col_{i,ch} - (C_ch - Cafter_{i,ch}) / (1 - alpha_i))  +  Gs[3] * T_end / (1 - alpha_i)
+ *     grad_table[g] = sum over p, s, hits i with id g and fl(|o_g| e_i) < 0.99f of   d_i * e_i
+ * Gs = G[p] / ns, formed once (G * (1/ns) for a power of two, G / ns otherwise); e_i is the blend's own float32
+ * exponential, or the LUT's value under GSRT_FLAG_LUT; the division is one float32 reciprocal of 1 - alpha_i per hit. A hit
+ * whose alpha was clamped to 0.99 contributes +0; that is a select, so a non-finite G[p] reaches only the Gaussians pixel p
+ * blends unclamped. Sets fixed by the forward frame and not differentiated: the hits taken and their order, the
+ * alpha > 1/255 cut and gcut, and the stop before a hit that would take T below 1e-4. The terms are summed on the device
+ * with float atomic adds, so the order of the sum is unspecified and results can differ in their last bits from run to run.
+ * accumulate == 0: the table is written, entries nothing reaches get +0. accumulate != 0: this frame's gradient is added
+ * to what the table holds; that form takes a device grad_table only, a host one is GSRT_E_ARG. grad_image / grad_table are
+ * host or device pointers; a device table must be ordinary device memory.
+ * The frame's RGBA (gsrt_framebuffer) is the plain colour frame's, bit for bit. Like the other gradient frames it takes the
+ * in-order path on gsrt_stream(): gsrt_slot_streams reads 0 after it, gsrt_depth_buffer and gsrt_feature_buffer read NULL;
+ * gsrt_timing records the frame like any other. Scenes with and without SH rows are both served.
+ * GSRT_E_ARG (gsrt_last_error names GSRT_FLAG_OPACITY_GRAD, and the context renders as before): REF mode; GSRT_FLAG_STATS,
+ * GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH, GSRT_FLAG_FEATURES, GSRT_FLAG_FEATURE_GRAD or GSRT_FLAG_SH_GRAD with it; sharded entry
+ * points; a scene with a mesh; a NULL grad_image or grad_table; the flag passed to any other entry point.
+ * Not provided: gradients with respect to means, covariances or SH (SH: gsrt_render_sh_grad); sharded frames.
+ * gsrt_render_opacity_grad blocks until the table is complete, like gsrt_render. */
+gsrt_status gsrt_render_opacity_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                     const float* grad_image, float* grad_table, int accumulate);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_render_opacity_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                           const float* d_grad_image, float* d_grad_table, int accumulate);
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into
