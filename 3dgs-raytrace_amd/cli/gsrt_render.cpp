@@ -16,22 +16,18 @@
 // GSRT_FLAG_DEPTH, as a one-channel PFM; a usage error with --mode ref or --stats), --features FILE --feature-channels C
 // (raw little-endian float32, n*C values: the scene's feature table) with --features-out FILE (COR: the feature frame,
 // GSRT_FLAG_FEATURES, as raw float32 H*W*C, and FILE.pfm when C is 1 or 3; usage errors: --mode ref, --stats, --depth,
-// C outside 1..16, one option of the pair without the other), --feature-grad FILE --feature-channels C
-// --feature-grad-out FILE (COR: a gradient frame, gsrt_render_feature_grad: the upstream gradient of a feature image, raw
-// float32 W*H*C, in; the gradient of the feature table, raw float32 n*C, out; no image is dumped; usage errors: --mode ref
-// or a REF-default scene, --stats, --depth, --features, C outside 1..16, one option without the others),
-// --sh-grad FILE --sh-grad-out FILE (COR, a scene with SH rows: an SH gradient frame, gsrt_render_sh_grad: the upstream
-// gradient of the RGBA frame, raw float32 W*H*4, in; the gradient of the SH table, raw float32 n*48 laid out
-// [gauss][coef][rgb], out; no image is dumped; usage errors: --mode ref or a REF-default scene, --stats, --depth,
-// --features, --feature-grad, one option without the other),
-// --opacity-grad FILE --opacity-grad-out FILE (COR: an opacity gradient frame, gsrt_render_opacity_grad: the upstream
-// gradient of the RGBA frame, raw float32 W*H*4, in; the gradient of the opacities, raw float32 n, out; no image is dumped;
-// usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, --feature-grad, --sh-grad, one option
-// without the other).
+// C outside 1..16, one option of the pair without the other), and the gradient runs (COR: one gradient frame, an upstream
+// gradient image in as raw float32, a table's gradient out as raw float32, no image dumped; kGradOptions):
+// --feature-grad FILE --feature-channels C --feature-grad-out FILE (gsrt_render_feature_grad: W*H*C in, n*C out),
+// --sh-grad FILE --sh-grad-out FILE (gsrt_render_sh_grad, a scene with SH rows: the RGBA frame's gradient W*H*4 in, n*48
+// laid out [gauss][coef][rgb] out), --opacity-grad FILE --opacity-grad-out FILE (gsrt_render_opacity_grad: W*H*4 in, n
+// out). Their usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, a gradient run listed before
+// it, one option without the others, C outside 1..16.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -54,6 +50,31 @@ struct Options {
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
 };
+
+// A gradient run, --NAME FILE with --NAME-out FILE: the upstream gradient image (raw float32, W*H*image_channels) in, the
+// table's gradient (raw float32, n*table_floats) out; 0 for either: --feature-channels, which the pair then needs. Oldest
+// first: a pair cannot be combined with one before it.
+struct GradOption {
+    const char* name;
+    std::string Options::*in, Options::*out;
+    uint32_t image_channels, table_floats;
+    gsrt_status (*call)(gsrt_scene*, const gsrt_ubo*, uint32_t mode, const float* gimg, uint32_t channels, float* gtab);
+};
+const GradOption kGradOptions[] = {
+    {"--feature-grad", &Options::feature_grad, &Options::feature_grad_out, 0, 0,
+     [](gsrt_scene* s, const gsrt_ubo* u, uint32_t m, const float* g, uint32_t c, float* t) {
+         return gsrt_render_feature_grad(s, u, m, 0, g, c, t, 0);
+     }},
+    {"--sh-grad", &Options::sh_grad, &Options::sh_grad_out, 4, 48,
+     [](gsrt_scene* s, const gsrt_ubo* u, uint32_t m, const float* g, uint32_t, float* t) {
+         return gsrt_render_sh_grad(s, u, m, 0, g, t, 0);
+     }},
+    {"--opacity-grad", &Options::opacity_grad, &Options::opacity_grad_out, 4, 1,
+     [](gsrt_scene* s, const gsrt_ubo* u, uint32_t m, const float* g, uint32_t, float* t) {
+         return gsrt_render_opacity_grad(s, u, m, 0, g, t, 0);
+     }},
+};
+bool given(const Options& o, const GradOption& g) { return !(o.*g.in).empty() || !(o.*g.out).empty(); }
 
 [[noreturn]] void usage(const char* msg) {
     if (msg) std::fprintf(stderr, "gsrt_render: %s\n", msg);
@@ -125,33 +146,24 @@ Options parse(int argc, char** argv) {
     if (!o.width || !o.height) usage("empty frame");
     if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
     if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
-    if (!o.opacity_grad.empty() || !o.opacity_grad_out.empty()) {
-        if (o.opacity_grad.empty() || o.opacity_grad_out.empty()) usage("--opacity-grad and --opacity-grad-out go together");
-        if (o.mode != "cor") usage("--opacity-grad needs --mode cor (REF frames blend nothing)");
-        if (o.stats) usage("--opacity-grad cannot be combined with --stats");
-        if (!o.depth.empty()) usage("--opacity-grad cannot be combined with --depth");
-        if (!o.features.empty() || !o.features_out.empty()) usage("--opacity-grad cannot be combined with --features");
-        if (!o.feature_grad.empty() || !o.feature_grad_out.empty())
-            usage("--opacity-grad cannot be combined with --feature-grad");
-        if (!o.sh_grad.empty() || !o.sh_grad_out.empty()) usage("--opacity-grad cannot be combined with --sh-grad");
+    for (const GradOption* g = std::end(kGradOptions); g-- != kGradOptions;) {  // newest first
+        if (!given(o, *g)) continue;
+        const std::string n = g->name;
+        auto clash = [&](bool with, const char* other) {
+            if (with) usage((n + " cannot be combined with " + other).c_str());
+        };
+        const bool channels = !g->image_channels;
+        if ((o.*g->in).empty() || (o.*g->out).empty() || (channels && !o.feature_channels_given))
+            usage((n + (channels ? ", --feature-channels and " : " and ") + n + "-out go together").c_str());
+        if (channels && (o.feature_channels < 1 || o.feature_channels > GSRT_MAX_FEATURES)) usage("--feature-channels must be 1..16");
+        if (o.mode != "cor") usage((n + " needs --mode cor (REF frames blend nothing)").c_str());
+        clash(o.stats, "--stats");
+        clash(!o.depth.empty(), "--depth");
+        clash(!o.features.empty() || !o.features_out.empty(), "--features");
+        for (const GradOption* older = kGradOptions; older != g; ++older) clash(given(o, *older), older->name);
     }
-    if (!o.sh_grad.empty() || !o.sh_grad_out.empty()) {
-        if (o.sh_grad.empty() || o.sh_grad_out.empty()) usage("--sh-grad and --sh-grad-out go together");
-        if (o.mode != "cor") usage("--sh-grad needs --mode cor (REF frames blend nothing)");
-        if (o.stats) usage("--sh-grad cannot be combined with --stats");
-        if (!o.depth.empty()) usage("--sh-grad cannot be combined with --depth");
-        if (!o.features.empty() || !o.features_out.empty()) usage("--sh-grad cannot be combined with --features");
-        if (!o.feature_grad.empty() || !o.feature_grad_out.empty()) usage("--sh-grad cannot be combined with --feature-grad");
-    }
-    if (!o.feature_grad.empty() || !o.feature_grad_out.empty()) {
-        if (o.feature_grad.empty() || o.feature_grad_out.empty() || !o.feature_channels_given)
-            usage("--feature-grad, --feature-channels and --feature-grad-out go together");
-        if (o.feature_channels < 1 || o.feature_channels > GSRT_MAX_FEATURES) usage("--feature-channels must be 1..16");
-        if (o.mode != "cor") usage("--feature-grad needs --mode cor (REF frames blend nothing)");
-        if (o.stats) usage("--feature-grad cannot be combined with --stats");
-        if (!o.depth.empty()) usage("--feature-grad cannot be combined with --depth");
-        if (!o.features.empty() || !o.features_out.empty()) usage("--feature-grad cannot be combined with --features");
-    } else if (!o.features.empty() || !o.features_out.empty() || o.feature_channels_given) {
+    // (with --feature-grad, --feature-channels is that pair's)
+    if (!given(o, kGradOptions[0]) && (!o.features.empty() || !o.features_out.empty() || o.feature_channels_given)) {
         if (o.features.empty() || o.features_out.empty() || !o.feature_channels_given)
             usage("--features, --feature-channels and --features-out go together");
         if (o.feature_channels < 1 || o.feature_channels > GSRT_MAX_FEATURES) usage("--feature-channels must be 1..16");
@@ -233,6 +245,9 @@ int main(int argc, char** argv) {
     if (o.stats) mode |= GSRT_FLAG_STATS;
     std::vector<float> rgba((size_t)o.width * o.height * 4);
     std::vector<float> depth(o.depth.empty() ? 0 : (size_t)o.width * o.height);
+    const GradOption* grad = nullptr;  // the gradient run asked for (parse: at most one)
+    for (const GradOption& g : kGradOptions)
+        if (given(o, g)) grad = &g;
     if (!rc && !o.depth.empty()) {
         mode |= GSRT_FLAG_DEPTH;
         rc = check(gsrt_render_depth(scene, &ubo, mode, 0, rgba.data(), depth.data()), ctx, "render");
@@ -264,62 +279,27 @@ int main(int argc, char** argv) {
             rc = check(gsrt_dump_pfm(pfm.c_str(), feat.data(), o.width, o.height, C), ctx, "dump_pfm");
             if (!rc) std::printf("wrote %s\n", pfm.c_str());
         }
-    } else if (!rc && !o.feature_grad.empty()) {
-        // the upstream gradient: W * H * C raw float32; the table's gradient: n * C raw float32
-        const uint32_t C = o.feature_channels;
-        std::vector<float> gimg((size_t)o.width * o.height * C), gtab((size_t)gsrt_scene_size(scene) * C);
-        FILE* f = std::fopen(o.feature_grad.c_str(), "rb");
+    } else if (!rc && grad) {
+        const uint32_t C = grad->image_channels ? grad->image_channels : o.feature_channels;
+        const uint32_t T = grad->table_floats ? grad->table_floats : o.feature_channels;
+        const std::string &in = o.*grad->in, &out = o.*grad->out;
+        std::vector<float> gimg((size_t)o.width * o.height * C), gtab((size_t)gsrt_scene_size(scene) * T);
+        FILE* f = std::fopen(in.c_str(), "rb");
         const bool whole = f && std::fread(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size() &&
                            std::fgetc(f) == EOF;
         if (f) std::fclose(f);
         if (!whole) {
-            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x channels)\n", o.feature_grad.c_str(),
-                         gimg.size());
+            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x %s)\n", in.c_str(), gimg.size(),
+                         grad->image_channels ? "4" : "channels");
             rc = 1;
         }
-        if (!rc) rc = check(gsrt_render_feature_grad(scene, &ubo, mode, 0, gimg.data(), C, gtab.data(), 0), ctx, "render");
+        if (!rc) rc = check(grad->call(scene, &ubo, mode, gimg.data(), C, gtab.data()), ctx, "render");
         if (!rc) {
-            f = std::fopen(o.feature_grad_out.c_str(), "wb");
+            f = std::fopen(out.c_str(), "wb");
             const bool ok = f && std::fwrite(gtab.data(), sizeof(float), gtab.size(), f) == gtab.size();
-            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.feature_grad_out.c_str());
+            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, out.c_str());
         }
-        if (!rc) std::printf("wrote %s\n", o.feature_grad_out.c_str());
-    } else if (!rc && !o.sh_grad.empty()) {
-        // the upstream gradient of the RGBA frame: W * H * 4 raw float32; the SH table's gradient: n * 48 raw float32
-        std::vector<float> gimg((size_t)o.width * o.height * 4), gtab((size_t)gsrt_scene_size(scene) * 48);
-        FILE* f = std::fopen(o.sh_grad.c_str(), "rb");
-        const bool whole = f && std::fread(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size() &&
-                           std::fgetc(f) == EOF;
-        if (f) std::fclose(f);
-        if (!whole) {
-            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x 4)\n", o.sh_grad.c_str(), gimg.size());
-            rc = 1;
-        }
-        if (!rc) rc = check(gsrt_render_sh_grad(scene, &ubo, mode, 0, gimg.data(), gtab.data(), 0), ctx, "render");
-        if (!rc) {
-            f = std::fopen(o.sh_grad_out.c_str(), "wb");
-            const bool ok = f && std::fwrite(gtab.data(), sizeof(float), gtab.size(), f) == gtab.size();
-            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.sh_grad_out.c_str());
-        }
-        if (!rc) std::printf("wrote %s\n", o.sh_grad_out.c_str());
-    } else if (!rc && !o.opacity_grad.empty()) {
-        // the upstream gradient of the RGBA frame: W * H * 4 raw float32; the opacities' gradient: n raw float32
-        std::vector<float> gimg((size_t)o.width * o.height * 4), gtab((size_t)gsrt_scene_size(scene));
-        FILE* f = std::fopen(o.opacity_grad.c_str(), "rb");
-        const bool whole = f && std::fread(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size() &&
-                           std::fgetc(f) == EOF;
-        if (f) std::fclose(f);
-        if (!whole) {
-            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x 4)\n", o.opacity_grad.c_str(), gimg.size());
-            rc = 1;
-        }
-        if (!rc) rc = check(gsrt_render_opacity_grad(scene, &ubo, mode, 0, gimg.data(), gtab.data(), 0), ctx, "render");
-        if (!rc) {
-            f = std::fopen(o.opacity_grad_out.c_str(), "wb");
-            const bool ok = f && std::fwrite(gtab.data(), sizeof(float), gtab.size(), f) == gtab.size();
-            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.opacity_grad_out.c_str());
-        }
-        if (!rc) std::printf("wrote %s\n", o.opacity_grad_out.c_str());
+        if (!rc) std::printf("wrote %s\n", out.c_str());
     } else if (!rc) {
         rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
     }
@@ -342,7 +322,7 @@ int main(int argc, char** argv) {
         const double rays = (double)o.width * o.height * o.samples * frames;
         if (!rc) std::printf("%u frames %.3f ms/frame %.1f Mrays/s\n", frames, dt / frames * 1e3, rays / dt / 1e6);
     }
-    if (!rc && !o.no_dump && o.feature_grad.empty() && o.sh_grad.empty() && o.opacity_grad.empty()) {  // a gradient run writes its table only
+    if (!rc && !o.no_dump && !grad) {  // a gradient run writes its table only
         std::string path = o.out;
         if (path.empty()) {
             char name[128];

@@ -11,6 +11,7 @@
 #include "gsrt_internal.hpp"
 
 using gsrt::fail;
+using gsrt::GradKind;
 
 namespace {
 
@@ -762,75 +763,14 @@ gsrt_status gsrt_bvh_download(gsrt_scene* sc, uint32_t* nodes, uint32_t* leaf_gi
     return GSRT_OK;
 }
 
-// grad_call: the caller is gsrt_render_feature_grad(_async), the only entry point that may carry GSRT_FLAG_FEATURE_GRAD,
-// or gsrt_render_sh_grad(_async), the only one that may carry GSRT_FLAG_SH_GRAD, or gsrt_render_opacity_grad(_async), the
-// only one that may carry GSRT_FLAG_OPACITY_GRAD
-enum class GradCall { none, feature, sh, opacity };
-static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, GradCall grad_call = GradCall::none) {
+// caller: the gradient entry point the frame came through (the only one that may carry its flag), none for every other
+static gsrt_status check_render_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, GradKind caller = GradKind::none) {
     if (!sc || !ubo) return GSRT_E_ARG;
     if (ubo->width == 0 || ubo->height == 0 || ubo->width > 32768 || ubo->height > 32768)
         return fail(sc->ctx, GSRT_E_ARG, "bad frame size");
-    if (mode & GSRT_FLAG_OPACITY_GRAD) {  // a whole COR colour frame that scatters its gradient to the opacities it blends
-        const char* why = nullptr;
-        if (grad_call != GradCall::opacity)
-            why = "GSRT_FLAG_OPACITY_GRAD: only through gsrt_render_opacity_grad (the gradient image goes there)";
-        else if ((mode & 0xffu) != GSRT_MODE_COR) why = "GSRT_FLAG_OPACITY_GRAD: COR frames only";
-        else if (mode & GSRT_FLAG_STATS) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_STATS";
-        else if (mode & GSRT_FLAG_OUT_DUMP8) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_OUT_DUMP8";
-        else if (mode & GSRT_FLAG_DEPTH) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_DEPTH";
-        else if (mode & GSRT_FLAG_FEATURES) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_FEATURES";
-        else if (mode & GSRT_FLAG_FEATURE_GRAD) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_FEATURE_GRAD";
-        else if (mode & GSRT_FLAG_SH_GRAD) why = "GSRT_FLAG_OPACITY_GRAD: not with GSRT_FLAG_SH_GRAD";
-        else if (sc->ntri) why = "GSRT_FLAG_OPACITY_GRAD: not for a scene with a triangle mesh";
-        if (why) return fail(sc->ctx, GSRT_E_ARG, why);
-    }
-    if (mode & GSRT_FLAG_SH_GRAD) {  // a whole COR colour frame that scatters its gradient to the SH rows it blends
-        const char* why = nullptr;
-        if (grad_call != GradCall::sh) why = "GSRT_FLAG_SH_GRAD: only through gsrt_render_sh_grad (the gradient image goes there)";
-        else if ((mode & 0xffu) != GSRT_MODE_COR) why = "GSRT_FLAG_SH_GRAD: COR frames only";
-        else if (mode & GSRT_FLAG_STATS) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_STATS";
-        else if (mode & GSRT_FLAG_OUT_DUMP8) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_OUT_DUMP8";
-        else if (mode & GSRT_FLAG_DEPTH) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_DEPTH";
-        else if (mode & GSRT_FLAG_FEATURES) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_FEATURES";
-        else if (mode & GSRT_FLAG_FEATURE_GRAD) why = "GSRT_FLAG_SH_GRAD: not with GSRT_FLAG_FEATURE_GRAD";
-        else if (sc->ntri) why = "GSRT_FLAG_SH_GRAD: not for a scene with a triangle mesh";
-        if (why) return fail(sc->ctx, GSRT_E_ARG, why);
-    }
-    if (mode & GSRT_FLAG_FEATURE_GRAD) {  // a whole COR frame that scatters a gradient image to the Gaussians it blends
-        const char* why = nullptr;
-        if (grad_call != GradCall::feature) why = "GSRT_FLAG_FEATURE_GRAD: only through gsrt_render_feature_grad (the gradient image goes there)";
-        else if ((mode & 0xffu) != GSRT_MODE_COR) why = "GSRT_FLAG_FEATURE_GRAD: COR frames only";
-        else if (mode & GSRT_FLAG_STATS) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_STATS";
-        else if (mode & GSRT_FLAG_OUT_DUMP8) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_OUT_DUMP8";
-        else if (mode & GSRT_FLAG_DEPTH) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_DEPTH";
-        else if (mode & GSRT_FLAG_FEATURES) why = "GSRT_FLAG_FEATURE_GRAD: not with GSRT_FLAG_FEATURES";
-        else if (sc->ntri) why = "GSRT_FLAG_FEATURE_GRAD: not for a scene with a triangle mesh";
-        if (why) return fail(sc->ctx, GSRT_E_ARG, why);
-    }
-    if (mode & GSRT_FLAG_DEPTH) {  // a whole COR frame's second output; the counting pass and dump codes carry none
-        if ((mode & 0xffu) != GSRT_MODE_COR) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: COR frames only");
-        if (mode & GSRT_FLAG_STATS) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: not with GSRT_FLAG_STATS");
-        if (mode & GSRT_FLAG_OUT_DUMP8) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: not with GSRT_FLAG_OUT_DUMP8");
-    }
-    if (mode & GSRT_FLAG_FEATURES) {  // a whole COR frame that blends the feature table instead of colour
-        if ((mode & 0xffu) != GSRT_MODE_COR) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: COR frames only");
-        if (mode & GSRT_FLAG_STATS) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_STATS");
-        if (mode & GSRT_FLAG_OUT_DUMP8) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_OUT_DUMP8");
-        if (mode & GSRT_FLAG_DEPTH) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: not with GSRT_FLAG_DEPTH");
-    }
-    if ((mode & 0xffu) > GSRT_MODE_COR ||
-        (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | GSRT_FLAG_DEPTH | GSRT_FLAG_FEATURES | GSRT_FLAG_FEATURE_GRAD |
-                  GSRT_FLAG_SH_GRAD | GSRT_FLAG_OPACITY_GRAD)))
-        return fail(sc->ctx, GSRT_E_ARG, "bad mode");
-    if ((mode & 0xffu) == GSRT_MODE_COR && ubo->samples == 0) return fail(sc->ctx, GSRT_E_ARG, "samples == 0");
-    if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
-    if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
-        return fail(sc->ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
-    if ((mode & GSRT_FLAG_FEATURES) && !gsrt_scene_features(sc))
-        return fail(sc->ctx, GSRT_E_STATE, "GSRT_FLAG_FEATURES: the scene has no feature table (gsrt_scene_set_features)");
-    if ((mode & GSRT_FLAG_SH_GRAD) && !sc->d_sh)
-        return fail(sc->ctx, GSRT_E_STATE, "GSRT_FLAG_SH_GRAD: the scene has no SH rows (gsrt_scene_set_sh)");
-    return GSRT_OK;
+    const gsrt::Refusal r = gsrt::frame_refusal(mode, caller, ubo->samples,
+                                                {sc->bvh_built, sc->ntri, gsrt_scene_features(sc) != 0, sc->d_sh != nullptr});
+    return r.status == GSRT_OK ? GSRT_OK : fail(sc->ctx, r.status, r.msg);
 }
 
 static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mode, uint32_t feat_channels = 0) {
@@ -858,13 +798,12 @@ static gsrt_status prepare_frame(gsrt_ctx* ctx, const gsrt_ubo* ubo, uint32_t mo
     return GSRT_OK;
 }
 
-// a GSRT_FLAG_FEATURE_GRAD frame's device buffers (gsrt_render_feature_grad_async)
+// a gradient frame's device buffers (grad_frame_async)
 struct GradFrame {
     const float* d_in;   // the upstream gradient image, W x H x channels floats
-    float* d_rows;       // the zeroed gradient table, n rows of 16 floats
+    float* d_rows;       // the table the render kernel adds to: the zeroed ctx rows, or the caller's table (kFrameFlags)
     uint32_t channels;
-    bool sh = false;     // a GSRT_FLAG_SH_GRAD frame's: the RGBA frame's gradient (channels = 4), n rows of 48 floats
-    bool opacity = false;  // a GSRT_FLAG_OPACITY_GRAD frame's: the RGBA frame's gradient (channels = 4), the table itself, n floats
+    GradKind kind;
 };
 
 // a frame's device outputs: a caller fills the ones its frame has, the others stay nullptr
@@ -873,18 +812,14 @@ struct FrameOut {
     gsrt_raystate* rs = nullptr;      // the per-ray states
     float* depth = nullptr;           // a GSRT_FLAG_DEPTH frame: a copy of ctx->d_depth
     float* feat = nullptr;            // a GSRT_FLAG_FEATURES frame: a copy of ctx->d_feat
-    const GradFrame* grad = nullptr;  // a GSRT_FLAG_FEATURE_GRAD frame's buffers
+    const GradFrame* grad = nullptr;  // a gradient frame's buffers
 };
 
 // one frame on the render stream
 static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const FrameOut& out) {
     float* const d_rgba = out.rgba;
     gsrt_raystate* const d_rs = out.rs;
-    gsrt_status s = check_render_args(sc, ubo, mode,
-                                      !out.grad            ? GradCall::none
-                                      : out.grad->opacity ? GradCall::opacity
-                                      : out.grad->sh      ? GradCall::sh
-                                                          : GradCall::feature);
+    gsrt_status s = check_render_args(sc, ubo, mode, out.grad ? out.grad->kind : GradKind::none);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
@@ -895,9 +830,9 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
     gsrt::timing_mark(ctx, 0);
     // pipelined COR frames render into their own buffer while slot streams are chosen (their frames overlap); the
     // ray states are one buffer, so frames that write them stay in order; so are the depth image (GSRT_FLAG_DEPTH) and
-    // the feature image (GSRT_FLAG_FEATURES) and a gradient frame's table (GSRT_FLAG_FEATURE_GRAD)
+    // the feature image (GSRT_FLAG_FEATURES) and a gradient frame's table (a gradient flag got here only with its buffers)
     const bool depth = (mode & GSRT_FLAG_DEPTH) != 0, feat = (mode & GSRT_FLAG_FEATURES) != 0;
-    const bool grad = (mode & (GSRT_FLAG_FEATURE_GRAD | GSRT_FLAG_SH_GRAD | GSRT_FLAG_OPACITY_GRAD)) != 0;
+    const bool grad = out.grad != nullptr;
     const bool slot = (mode & 0xffu) == GSRT_MODE_COR && !(mode & GSRT_FLAG_STATS) && !d_rs && !depth && !feat && !grad &&
                       gsrt::use_slot_streams(ctx, false);
     if (slot) {
@@ -941,8 +876,7 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
             rsy.grad_in = out.grad->d_in;
             rsy.grad_rows = out.grad->d_rows;
             rsy.grad_channels = out.grad->channels;
-            rsy.grad_sh = out.grad->sh;
-            rsy.grad_opacity = out.grad->opacity;
+            rsy.grad_kind = out.grad->kind;
         }
         s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat && !grad ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
@@ -1051,180 +985,106 @@ gsrt_status gsrt_render_features(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t m
 
 const float* gsrt_feature_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_feat ? ctx->d_feat : nullptr; }
 
-// The frame zeroes the ctx's gradient rows (n x 16 floats, 64-B rows: the shape the render kernel's atomics take), the
-// render kernel adds every blended hit's terms to them, and a small kernel compacts them into the caller's n x channels
-// table, all in order on the render stream.
-static gsrt_status check_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const float* grad_image,
-                                   uint32_t channels, const float* grad_table) {
+// Gradient frames, each kind by its row F of kFrameFlags. With ctx rows (feature: n x 16 floats, 64-B rows; sh: n x 48,
+// 192-B rows in the SH rows' own [rgb][coef] layout: the shapes the render kernel's atomics take) the frame zeroes them, the
+// render kernel adds every blended hit's terms to them and a small kernel compacts them into the caller's table (sh:
+// transposed into [gauss][coef][rgb]). Without (opacity: n floats in API order) the render kernel adds to the caller's
+// device table itself, zeroed first unless it accumulates, and nothing is compacted. All in order on the render stream: the
+// kinds share the ctx's buffers.
+static gsrt_status check_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const gsrt::FrameFlag& F,
+                                   const float* grad_image, uint32_t channels, const float* grad_table) {
     if (!sc || !ubo) return GSRT_E_ARG;
-    if (channels < 1 || channels > GSRT_MAX_FEATURES)
-        return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: channels must be 1..GSRT_MAX_FEATURES");
-    if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: grad_image is NULL");
-    if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: grad_table is NULL");
-    return check_render_args(sc, ubo, mode, GradCall::feature);
+    const std::string name = std::string(F.name) + ": ";
+    if (!F.image_channels && (channels < 1 || channels > GSRT_MAX_FEATURES))
+        return fail(sc->ctx, GSRT_E_ARG, name + "channels must be 1..GSRT_MAX_FEATURES");
+    if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, name + "grad_image is NULL");
+    if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, name + "grad_table is NULL");
+    return check_render_args(sc, ubo, mode, F.kind);
+}
+
+static gsrt_status grad_frame_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, GradKind kind,
+                                    const float* d_image, uint32_t channels, float* d_table, int accumulate) {
+    const gsrt::FrameFlag& F = gsrt::grad_flag(kind);
+    mode |= F.bit;
+    gsrt_status s = check_grad_args(sc, ubo, mode, F, d_image, channels, d_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (F.image_channels) channels = F.image_channels;
+    if (F.row_floats) {
+        const size_t rows = (size_t)F.row_floats * (sc->n ? sc->n : 1);
+        if (ctx->grad_rows_floats < rows || !ctx->d_grad_rows) {  // a queued frame may still use the old rows
+            if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+            if ((s = grow(ctx, &ctx->d_grad_rows, &ctx->grad_rows_floats, rows)) != GSRT_OK) return s;
+        }
+        GSRT_HIP(ctx, hipMemsetAsync(ctx->d_grad_rows, 0, sizeof(float) * rows, ctx->stream));
+    } else if (!accumulate && sc->n) {
+        GSRT_HIP(ctx, hipMemsetAsync(d_table, 0, sizeof(float) * F.table_floats * sc->n, ctx->stream));
+    }
+    const GradFrame gf{d_image, F.row_floats ? ctx->d_grad_rows : d_table, channels, kind};
+    FrameOut out;
+    out.grad = &gf;
+    s = render_async(sc, ubo, mode, k, out);
+    if (s != GSRT_OK || !F.row_floats) return s;
+    if (kind == GradKind::sh) gsrt::launch_sh_grad_compact(ctx->stream, d_table, ctx->d_grad_rows, sc->n, accumulate != 0);
+    else gsrt::launch_grad_compact(ctx->stream, d_table, ctx->d_grad_rows, sc->n, channels, accumulate != 0);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+// a host image and a host table go through the gradient frames' buffers of the ctx (d_grad_in, d_grad_out)
+static gsrt_status grad_frame_blocking(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, GradKind kind,
+                                       const float* grad_image, uint32_t channels, float* grad_table, int accumulate) {
+    const gsrt::FrameFlag& F = gsrt::grad_flag(kind);
+    mode |= F.bit;
+    gsrt_status s = check_grad_args(sc, ubo, mode, F, grad_image, channels, grad_table);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
+    if (accumulate && !out_dev) return fail(ctx, GSRT_E_ARG, std::string(F.name) + ": accumulate needs a device grad_table");
+    const size_t in_floats = (size_t)ubo->width * ubo->height * (F.image_channels ? F.image_channels : channels);
+    const size_t out_floats = (size_t)sc->n * (F.table_floats ? F.table_floats : channels);
+    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
+    }
+    if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
+        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_out, &ctx->grad_out_floats, out_floats ? out_floats : 1)) != GSRT_OK) return s;
+    }
+    if (!in_dev)
+        GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
+    s = grad_frame_async(sc, ubo, mode, k, kind, in_dev ? grad_image : ctx->d_grad_in, channels,
+                         out_dev ? grad_table : ctx->d_grad_out, accumulate);
+    return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
+                                     sizeof(float) * out_floats, "gradient table download failed"}});
 }
 
 gsrt_status gsrt_render_feature_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                            const float* d_grad_image, uint32_t channels, float* d_grad_table,
                                            int accumulate) {
-    mode |= GSRT_FLAG_FEATURE_GRAD;
-    gsrt_status s = check_grad_args(sc, ubo, mode, d_grad_image, channels, d_grad_table);
-    if (s != GSRT_OK) return s;
-    gsrt_ctx* ctx = sc->ctx;
-    (void)hipSetDevice(ctx->device);
-    const size_t rows = (size_t)16 * (sc->n ? sc->n : 1);
-    if (ctx->grad_rows_floats < rows || !ctx->d_grad_rows) {  // a queued frame may still use the old rows
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_rows, &ctx->grad_rows_floats, rows)) != GSRT_OK) return s;
-    }
-    GSRT_HIP(ctx, hipMemsetAsync(ctx->d_grad_rows, 0, sizeof(float) * rows, ctx->stream));
-    const GradFrame gf{d_grad_image, ctx->d_grad_rows, channels};
-    FrameOut out;
-    out.grad = &gf;
-    s = render_async(sc, ubo, mode, k, out);
-    if (s != GSRT_OK) return s;
-    gsrt::launch_grad_compact(ctx->stream, d_grad_table, ctx->d_grad_rows, sc->n, channels, accumulate != 0);
-    GSRT_HIP(ctx, hipGetLastError());
-    return GSRT_OK;
+    return grad_frame_async(sc, ubo, mode, k, GradKind::feature, d_grad_image, channels, d_grad_table, accumulate);
 }
-
 gsrt_status gsrt_render_feature_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                      const float* grad_image, uint32_t channels, float* grad_table, int accumulate) {
-    mode |= GSRT_FLAG_FEATURE_GRAD;
-    gsrt_status s = check_grad_args(sc, ubo, mode, grad_image, channels, grad_table);
-    if (s != GSRT_OK) return s;
-    gsrt_ctx* ctx = sc->ctx;
-    (void)hipSetDevice(ctx->device);
-    const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
-    if (accumulate && !out_dev)
-        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: accumulate needs a device grad_table");
-    const size_t in_floats = (size_t)ubo->width * ubo->height * channels, out_floats = (size_t)sc->n * channels;
-    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
-    }
-    if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_out, &ctx->grad_out_floats, out_floats ? out_floats : 1)) != GSRT_OK) return s;
-    }
-    if (!in_dev)
-        GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
-    s = gsrt_render_feature_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in, channels,
-                                       out_dev ? grad_table : ctx->d_grad_out, accumulate);
-    return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
-                                     sizeof(float) * out_floats, "gradient table download failed"}});
+    return grad_frame_blocking(sc, ubo, mode, k, GradKind::feature, grad_image, channels, grad_table, accumulate);
 }
-
-// An SH gradient frame goes the same way through the same buffers of the ctx (such frames and feature-gradient frames stay
-// in order on the render stream): the rows are n x 48 floats, 192-B rows in the SH rows' own [rgb][coef] layout, and
-// launch_sh_grad_compact transposes them into the caller's [gauss][coef][rgb] table.
-static gsrt_status check_sh_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const float* grad_image,
-                                      const float* grad_table) {
-    if (!sc || !ubo) return GSRT_E_ARG;
-    if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: grad_image is NULL");
-    if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: grad_table is NULL");
-    return check_render_args(sc, ubo, mode, GradCall::sh);
-}
-
 gsrt_status gsrt_render_sh_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                       const float* d_grad_image, float* d_grad_table, int accumulate) {
-    mode |= GSRT_FLAG_SH_GRAD;
-    gsrt_status s = check_sh_grad_args(sc, ubo, mode, d_grad_image, d_grad_table);
-    if (s != GSRT_OK) return s;
-    gsrt_ctx* ctx = sc->ctx;
-    (void)hipSetDevice(ctx->device);
-    const size_t rows = (size_t)48 * (sc->n ? sc->n : 1);
-    if (ctx->grad_rows_floats < rows || !ctx->d_grad_rows) {  // a queued frame may still use the old rows
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_rows, &ctx->grad_rows_floats, rows)) != GSRT_OK) return s;
-    }
-    GSRT_HIP(ctx, hipMemsetAsync(ctx->d_grad_rows, 0, sizeof(float) * rows, ctx->stream));
-    const GradFrame gf{d_grad_image, ctx->d_grad_rows, 4u, true};
-    FrameOut out;
-    out.grad = &gf;
-    s = render_async(sc, ubo, mode, k, out);
-    if (s != GSRT_OK) return s;
-    gsrt::launch_sh_grad_compact(ctx->stream, d_grad_table, ctx->d_grad_rows, sc->n, accumulate != 0);
-    GSRT_HIP(ctx, hipGetLastError());
-    return GSRT_OK;
+    return grad_frame_async(sc, ubo, mode, k, GradKind::sh, d_grad_image, 0, d_grad_table, accumulate);
 }
-
 gsrt_status gsrt_render_sh_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const float* grad_image,
                                 float* grad_table, int accumulate) {
-    mode |= GSRT_FLAG_SH_GRAD;
-    gsrt_status s = check_sh_grad_args(sc, ubo, mode, grad_image, grad_table);
-    if (s != GSRT_OK) return s;
-    gsrt_ctx* ctx = sc->ctx;
-    (void)hipSetDevice(ctx->device);
-    const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
-    if (accumulate && !out_dev) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: accumulate needs a device grad_table");
-    const size_t in_floats = (size_t)ubo->width * ubo->height * 4, out_floats = (size_t)sc->n * 48;
-    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
-    }
-    if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_out, &ctx->grad_out_floats, out_floats ? out_floats : 1)) != GSRT_OK) return s;
-    }
-    if (!in_dev)
-        GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
-    s = gsrt_render_sh_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in,
-                                  out_dev ? grad_table : ctx->d_grad_out, accumulate);
-    return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
-                                     sizeof(float) * out_floats, "gradient table download failed"}});
+    return grad_frame_blocking(sc, ubo, mode, k, GradKind::sh, grad_image, 0, grad_table, accumulate);
 }
-
-// An opacity gradient frame: the table is n floats in API order, so the render kernel adds to the caller's device table
-// itself (zeroed first on the render stream unless it accumulates) and nothing is compacted; a host image and a host table
-// go through the gradient frames' buffers of the ctx, in order with the other gradient frames on the render stream.
-static gsrt_status check_opacity_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const float* grad_image,
-                                           const float* grad_table) {
-    if (!sc || !ubo) return GSRT_E_ARG;
-    if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: grad_image is NULL");
-    if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: grad_table is NULL");
-    return check_render_args(sc, ubo, mode, GradCall::opacity);
-}
-
 gsrt_status gsrt_render_opacity_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                            const float* d_grad_image, float* d_grad_table, int accumulate) {
-    mode |= GSRT_FLAG_OPACITY_GRAD;
-    gsrt_status s = check_opacity_grad_args(sc, ubo, mode, d_grad_image, d_grad_table);
-    if (s != GSRT_OK) return s;
-    gsrt_ctx* ctx = sc->ctx;
-    (void)hipSetDevice(ctx->device);
-    if (!accumulate && sc->n) GSRT_HIP(ctx, hipMemsetAsync(d_grad_table, 0, sizeof(float) * sc->n, ctx->stream));
-    GradFrame gf{d_grad_image, d_grad_table, 4u};
-    gf.opacity = true;
-    FrameOut out;
-    out.grad = &gf;
-    return render_async(sc, ubo, mode, k, out);
+    return grad_frame_async(sc, ubo, mode, k, GradKind::opacity, d_grad_image, 0, d_grad_table, accumulate);
 }
-
 gsrt_status gsrt_render_opacity_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                      const float* grad_image, float* grad_table, int accumulate) {
-    mode |= GSRT_FLAG_OPACITY_GRAD;
-    gsrt_status s = check_opacity_grad_args(sc, ubo, mode, grad_image, grad_table);
-    if (s != GSRT_OK) return s;
-    gsrt_ctx* ctx = sc->ctx;
-    (void)hipSetDevice(ctx->device);
-    const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
-    if (accumulate && !out_dev) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: accumulate needs a device grad_table");
-    const size_t in_floats = (size_t)ubo->width * ubo->height * 4, out_floats = sc->n;
-    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
-    }
-    if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
-        if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_out, &ctx->grad_out_floats, out_floats ? out_floats : 1)) != GSRT_OK) return s;
-    }
-    if (!in_dev)
-        GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
-    s = gsrt_render_opacity_grad_async(sc, ubo, mode, k, in_dev ? grad_image : ctx->d_grad_in,
-                                       out_dev ? grad_table : ctx->d_grad_out, accumulate);
-    return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
-                                     sizeof(float) * out_floats, "gradient table download failed"}});
+    return grad_frame_blocking(sc, ubo, mode, k, GradKind::opacity, grad_image, 0, grad_table, accumulate);
 }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,

@@ -276,6 +276,13 @@ gsrt_status gsrt_comm_init(gsrt_ctx* ctx, const uint8_t id[128], int nranks, int
 }  // extern "C"
 
 namespace {
+// a second output or a gradient (kFrameFlags) belongs to a whole frame: a sharded one refuses the first such flag it carries
+gsrt_status refuse_frame_flags(gsrt_ctx* ctx, uint32_t mode) {
+    for (const gsrt::FrameFlag& F : gsrt::kFrameFlags)
+        if (mode & F.bit) return fail(ctx, GSRT_E_ARG, std::string(F.name) + ": whole frames only, not sharded ones");
+    return GSRT_OK;
+}
+
 // FNV-1a over a sharded frame's partition and packed layout, and whether the bands are pinned: every rank must render
 // the same one, and pin or balance alike (a pinned rank would not follow the others' next cut)
 uint32_t plan_hash(uint32_t tiles_x, uint32_t tiles_y, uint32_t tw, uint32_t th, uint32_t nranks, const uint32_t* bands,
@@ -353,13 +360,7 @@ gsrt_status gsrt_render_sharded_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint3
     if (!ctx->comm) return fail(ctx, GSRT_E_STATE, "gsrt_comm_init not called");
     if (!sc->bvh_built) return fail(ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
     if (ubo->width == 0 || ubo->height == 0 || (mode & 0xffu) > GSRT_MODE_COR) return GSRT_E_ARG;
-    if (mode & GSRT_FLAG_DEPTH) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_FEATURES) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_FEATURE_GRAD)
-        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_SH_GRAD) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_OPACITY_GRAD)
-        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: whole frames only, not sharded ones");
+    if (gsrt_status s = refuse_frame_flags(ctx, mode); s != GSRT_OK) return s;
     if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     (void)hipSetDevice(ctx->device);
@@ -803,13 +804,7 @@ static gsrt_status render_emulated(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t
     if (!sc->bvh_built) return fail(ctx, GSRT_E_STATE, "render before gsrt_build_bvh");
     if (sc->ntri && (mode & 0xffu) != GSRT_MODE_REF)
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
-    if (mode & GSRT_FLAG_DEPTH) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_DEPTH: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_FEATURES) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURES: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_FEATURE_GRAD)
-        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_FEATURE_GRAD: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_SH_GRAD) return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_SH_GRAD: whole frames only, not sharded ones");
-    if (mode & GSRT_FLAG_OPACITY_GRAD)
-        return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OPACITY_GRAD: whole frames only, not sharded ones");
+    if (gsrt_status s = refuse_frame_flags(ctx, mode); s != GSRT_OK) return s;
     const bool d8 = (mode & GSRT_FLAG_OUT_DUMP8) != 0;
     if (d8 && ((mode & 0xffu) != GSRT_MODE_COR || (mode & GSRT_FLAG_STATS)))
         return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OUT_DUMP8: COR frames without GSRT_FLAG_STATS only");

@@ -303,6 +303,50 @@ gsrt_status lbvh_fit_if_stale(gsrt_scene* sc, uint32_t slot, hipStream_t st, boo
 // ---- meshes (gsrt_mesh_trace.hip): the closest triangle hit t per pixel of a REF frame (kTMax: none) into tri_t
 void launch_mesh_thit(hipStream_t s, const gsrt_ubo& ubo, const gsrt_scene* sc, float* tri_t);
 
+// ---- frame kinds on the host. A whole COR frame may carry one second output or be one gradient frame; each is a flag of
+// the mode word and one row here, in the order they were introduced. Everything the host does per kind reads the row: the
+// refusals (frame_refusal, gsrt_plan.cpp; gsrt_comm.cpp), the allowed mode bits, the gradient entry points (gsrt_api.cpp).
+enum class GradKind : uint32_t { none, feature, sh, opacity };  // which gradient frame (none: the caller is no gradient call)
+struct FrameFlag {
+    uint32_t bit;
+    const char* name;         // as the messages spell it
+    GradKind kind;            // a gradient flag's kind; the fields below are its own
+    const char* entry;        // the blocking entry point, the only one (with its _async) that may carry the flag
+    uint32_t row_floats;      // floats per Gaussian of the ctx rows the render kernel adds to; 0: the caller's table is the rows
+    uint32_t image_channels;  // the gradient image's channels; 0: the caller's `channels`
+    uint32_t table_floats;    // the caller's table, floats per Gaussian; 0: the caller's `channels`
+    bool needs_sh;            // the scene must have SH rows
+};
+constexpr FrameFlag kFrameFlags[] = {
+    {GSRT_FLAG_DEPTH, "GSRT_FLAG_DEPTH", GradKind::none, nullptr, 0, 0, 0, false},
+    {GSRT_FLAG_FEATURES, "GSRT_FLAG_FEATURES", GradKind::none, nullptr, 0, 0, 0, false},
+    {GSRT_FLAG_FEATURE_GRAD, "GSRT_FLAG_FEATURE_GRAD", GradKind::feature, "gsrt_render_feature_grad", 16, 0, 0, false},
+    {GSRT_FLAG_SH_GRAD, "GSRT_FLAG_SH_GRAD", GradKind::sh, "gsrt_render_sh_grad", 48, 4, 48, true},
+    {GSRT_FLAG_OPACITY_GRAD, "GSRT_FLAG_OPACITY_GRAD", GradKind::opacity, "gsrt_render_opacity_grad", 0, 4, 1, false},
+};
+constexpr uint32_t frame_flag_bits() {  // every row's bit (the allowed mode bits beside the low byte, LUT and STATS)
+    uint32_t m = 0;
+    for (const FrameFlag& f : kFrameFlags) m |= f.bit;
+    return m;
+}
+constexpr const FrameFlag& grad_flag(GradKind kind) {  // a gradient kind's row
+    for (const FrameFlag& f : kFrameFlags)
+        if (f.kind == kind) return f;
+    return kFrameFlags[0];
+}
+// Why a whole frame of `mode` is refused, or GSRT_OK and no message (gsrt_plan.cpp: host logic, the test hook
+// gsrt_debug_frame_refusal exposes it). caller: the gradient entry point the frame came through, none for every other.
+struct SceneFacts {
+    bool bvh_built;
+    uint32_t ntri;
+    bool features, sh;  // the scene has a feature table, SH rows
+};
+struct Refusal {
+    gsrt_status status;
+    std::string msg;
+};
+Refusal frame_refusal(uint32_t mode, GradKind caller, uint32_t samples, const SceneFacts& sc);
+
 // ---- frame plan and dispatch orders (gsrt_plan.cpp: host arithmetic, no HIP calls), render (gsrt_render.hip) ----
 struct RenderPlan {
     uint32_t mode = GSRT_MODE_COR;  // GSRT_MODE_* | flags
@@ -361,16 +405,13 @@ struct RenderSync {
     float* depth = nullptr;
     // GSRT_FLAG_FEATURES (likewise): the frame's feature image, W x H x feat_channels floats, or nullptr
     float* feat = nullptr;
-    // GSRT_FLAG_FEATURE_GRAD (likewise): the upstream gradient image, W x H x grad_channels floats, and the zeroed
-    // gradient table the frame adds to, n rows of 16 floats; or nullptr
-    // GSRT_FLAG_SH_GRAD (grad_sh): the upstream gradient of the RGBA frame (grad_channels = 4) and n rows of 48 floats
+    // a gradient frame (likewise; grad_kind says which, kFrameFlags): the upstream gradient image, W x H x grad_channels
+    // floats, and the table the frame adds to, n rows of the kind's row width (feature 16, sh 48 floats, zeroed ctx rows;
+    // opacity: the caller's own device table, n floats); or nullptr
     const float* grad_in = nullptr;
     float* grad_rows = nullptr;
     uint32_t grad_channels = 0;
-    // GSRT_FLAG_OPACITY_GRAD (grad_opacity): the upstream gradient of the RGBA frame (grad_channels = 4) and the caller's
-    // own device table, n floats, which the frame adds to
-    bool grad_sh = false;
-    bool grad_opacity = false;
+    GradKind grad_kind = GradKind::none;
 };
 gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_rgba,
                           gsrt_raystate* d_rs, RenderSync* sync = nullptr);

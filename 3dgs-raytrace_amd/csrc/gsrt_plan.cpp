@@ -220,7 +220,55 @@ void deal_units(const double* cost, const uint32_t* centre, uint32_t R, uint32_t
     }
 }
 
+// The refusals of a whole frame. Each flag of kFrameFlags in the mode is checked on its own, the gradient flags first and
+// newest first, then the two second outputs oldest first: its entry point, COR, not the counting pass, not dump codes, none
+// of the flags before it in the table, and for a gradient frame no mesh. The first refusal wins; then the checks every frame
+// gets.
+Refusal frame_refusal(uint32_t mode, GradKind caller, uint32_t samples, const SceneFacts& sc) {
+    constexpr int N = (int)(sizeof kFrameFlags / sizeof kFrameFlags[0]);
+    const uint32_t low = mode & 0xffu;
+    auto why_not = [&](int i, bool grad) -> std::string {  // flag i of the table, if the mode has it and it is of that sort
+        const FrameFlag& F = kFrameFlags[i];
+        if (!(mode & F.bit) || (F.kind != GradKind::none) != grad) return "";
+        const std::string name = std::string(F.name) + ": ";
+        if (grad && caller != F.kind) return name + "only through " + F.entry + " (the gradient image goes there)";
+        if (low != GSRT_MODE_COR) return name + "COR frames only";
+        if (mode & GSRT_FLAG_STATS) return name + "not with GSRT_FLAG_STATS";
+        if (mode & GSRT_FLAG_OUT_DUMP8) return name + "not with GSRT_FLAG_OUT_DUMP8";
+        for (int j = 0; j < i; ++j)
+            if (mode & kFrameFlags[j].bit) return name + "not with " + kFrameFlags[j].name;
+        return grad && sc.ntri ? name + "not for a scene with a triangle mesh" : "";
+    };
+    std::string why;
+    for (int i = N - 1; i >= 0 && why.empty(); --i) why = why_not(i, true);
+    for (int i = 0; i < N && why.empty(); ++i) why = why_not(i, false);
+    if (!why.empty()) return {GSRT_E_ARG, why};
+    if (low > GSRT_MODE_COR || (mode & ~(0xffu | GSRT_FLAG_LUT | GSRT_FLAG_STATS | frame_flag_bits()))) return {GSRT_E_ARG, "bad mode"};
+    if (low == GSRT_MODE_COR && samples == 0) return {GSRT_E_ARG, "samples == 0"};
+    if (!sc.bvh_built) return {GSRT_E_STATE, "render before gsrt_build_bvh"};
+    if (sc.ntri && low != GSRT_MODE_REF) return {GSRT_E_ARG, "triangle meshes are co-traced in REF mode only"};
+    if ((mode & GSRT_FLAG_FEATURES) && !sc.features)
+        return {GSRT_E_STATE, "GSRT_FLAG_FEATURES: the scene has no feature table (gsrt_scene_set_features)"};
+    for (const FrameFlag& F : kFrameFlags)
+        if ((mode & F.bit) && F.needs_sh && !sc.sh)
+            return {GSRT_E_STATE, std::string(F.name) + ": the scene has no SH rows (gsrt_scene_set_sh)"};
+    return {GSRT_OK, ""};
+}
+
 }  // namespace gsrt
+
+extern "C" gsrt_status gsrt_debug_frame_refusal(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
+                                                int has_features, int has_sh, char* msg, size_t cap) {
+    if (caller > (uint32_t)gsrt::GradKind::opacity) return GSRT_E_ARG;
+    const gsrt::Refusal r = gsrt::frame_refusal(mode, (gsrt::GradKind)caller, samples,
+                                                {bvh_built != 0, ntri, has_features != 0, has_sh != 0});
+    if (msg && cap) {
+        const size_t len = std::min(r.msg.size(), cap - 1);
+        std::memcpy(msg, r.msg.data(), len);
+        msg[len] = '\0';
+    }
+    return r.status;
+}
 
 extern "C" gsrt_status gsrt_deal_units(const double* cost, const uint32_t* centre, uint32_t units, uint32_t* perm) {
     if (!cost || !centre || !perm || units % gsrt::kXcds) return GSRT_E_ARG;

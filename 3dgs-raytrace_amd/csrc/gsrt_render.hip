@@ -733,9 +733,9 @@ static_assert(sizeof(Stage) == kGroup * 256 && sizeof(Stage) % 1024 == 0, "whole
 // scene's SH-3 rows are blended; LUT: the ExpLUT instead of the exact exponential. Twenty-two kernels: {plain, stats,
 // depth, opgrad} x SH x LUT and {feat, grad, shgrad} x LUT, named by cor_kernel and nowhere else. What a kind adds (blend_hit)
 // sits under if constexpr on these members: the other kinds' code does not change. The RGBA of feat and grad is the
-// no-SH frame's. shgrad (GSRT_FLAG_SH_GRAD, grad_rows with RenderSync::grad_sh) is the backward of a plain colour frame
-// to the SH table: SH rows always, and the plain frame's RGBA. opgrad (GSRT_FLAG_OPACITY_GRAD, grad_rows with
-// RenderSync::grad_opacity) is the backward of a plain colour frame to the opacities, with or without SH rows: every pass
+// no-SH frame's. shgrad (GSRT_FLAG_SH_GRAD, grad_rows of GradKind::sh) is the backward of a plain colour frame
+// to the SH table: SH rows always, and the plain frame's RGBA. opgrad (GSRT_FLAG_OPACITY_GRAD, grad_rows of
+// GradKind::opacity, RenderSync::grad_kind) is the backward of a plain colour frame to the opacities, with or without SH rows: every pass
 // shades its rays twice (k_render_cor), the plain blend for the ray's finals and then the same blend again with the
 // gradient terms; the plain frame's RGBA.
 enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad };
@@ -2751,8 +2751,9 @@ static void fill_args(KArgs& k, const gsrt_scene* sc, const gsrt_ubo& ubo, const
     A.feat_out = outputs ? sync->feat : nullptr;
     A.feat_rows = A.feat_out ? sc->d_feat_rows : nullptr;
     A.feat_channels = A.feat_out ? sc->feat_channels : 0u;
-    // (an SH gradient frame of a scene without SH rows is refused before it gets here, gsrt_api.cpp check_render_args)
-    const bool grad = outputs && sync->grad_rows && !A.depth_out && !A.feat_out && (!sync->grad_sh || sc->d_sh);
+    // (an SH gradient frame of a scene without SH rows is refused before it gets here, frame_refusal)
+    const bool grad = outputs && sync->grad_rows && !A.depth_out && !A.feat_out &&
+                      (!grad_flag(sync->grad_kind).needs_sh || sc->d_sh);
     A.grad_in = grad ? sync->grad_in : nullptr;
     A.grad_rows = grad ? sync->grad_rows : nullptr;
     A.grad_channels = grad ? sync->grad_channels : 0u;
@@ -3068,7 +3069,7 @@ static gsrt_status launch_ref(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderP
 }
 
 // The k_render_cor instantiation of a frame: every one the library holds is named here and nowhere else. Feature and
-// gradient frames blend no SH whatever the scene holds (never with stats or depth, gsrt_api.cpp check_render_args).
+// gradient frames blend no SH whatever the scene holds (never with stats or depth, frame_refusal).
 using CorLaunch = void (*)(hipStream_t, const KArgs&);
 template <CorKind K>
 static CorLaunch cor_kernel_of(bool sh, bool lut) {
@@ -3143,9 +3144,13 @@ static gsrt_status launch_cor(gsrt_scene* sc, const RenderPlan& plan, const Fram
     const hipStream_t st = ctx->stream;
     FrameSlot& S = ctx->slot[f.b];
     const RenderArgs& A = k.a;
-    const CorKind kind = A.grad_rows ? (sync->grad_opacity ? CorKind::opgrad : sync->grad_sh ? CorKind::shgrad : CorKind::grad)
-                         : A.feat_out ? CorKind::feat : A.depth_out ? CorKind::depth
-                         : f.stats   ? CorKind::stats : CorKind::plain;
+    CorKind kind = A.feat_out ? CorKind::feat : A.depth_out ? CorKind::depth : f.stats ? CorKind::stats : CorKind::plain;
+    if (A.grad_rows)
+        switch (sync->grad_kind) {
+            case GradKind::opacity: kind = CorKind::opgrad; break;
+            case GradKind::sh: kind = CorKind::shgrad; break;
+            default: kind = CorKind::grad; break;
+        }
     const CorLaunch render = cor_kernel(kind, sc->d_sh != nullptr, (plan.mode & GSRT_FLAG_LUT) != 0);
     hipStream_t rs = st;
     if (f.slot_streams) {

@@ -68,7 +68,7 @@ EXPORTS = [
     "gsrt_scene_set_features", "gsrt_scene_features", "gsrt_render_features", "gsrt_render_features_async",
     "gsrt_feature_buffer", "gsrt_render_feature_grad", "gsrt_render_feature_grad_async", "gsrt_group_order",
     "gsrt_unit_order", "gsrt_scene_set_sh", "gsrt_render_sh_grad", "gsrt_render_sh_grad_async",
-    "gsrt_render_opacity_grad", "gsrt_render_opacity_grad_async",
+    "gsrt_render_opacity_grad", "gsrt_render_opacity_grad_async", "gsrt_debug_frame_refusal",
 ]
 
 
@@ -186,6 +186,7 @@ def _load():
         "gsrt_render_sh_grad_async": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_render_opacity_grad": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_render_opacity_grad_async": ([P, P, u32, u32, P, P, i32], i32),
+        "gsrt_debug_frame_refusal": ([u32, u32, u32, i32, u32, i32, i32, ctypes.c_char_p, ctypes.c_size_t], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -218,6 +219,16 @@ def _check(status: int, ctx=None):
 def _f32(a, shape):
     a = np.ascontiguousarray(a, dtype=np.float32)
     return a.reshape(shape)
+
+
+def _rgba_grad(what, ubo, grad_image):
+    """an RGBA frame's upstream gradient as (H, W, 4) float32, contiguous: an (H, W, 3) one gets a zero alpha gradient"""
+    g = np.asarray(grad_image, np.float32)
+    if g.ndim != 3 or g.shape[:2] != (int(ubo["height"][0]), int(ubo["width"][0])) or g.shape[2] not in (3, 4):
+        raise GsrtError(E_ARG, f"{what}: an (H, W, 4) or (H, W, 3) array")
+    if g.shape[2] == 3:
+        g = np.concatenate([g, np.zeros(g.shape[:2] + (1,), np.float32)], axis=2)
+    return np.ascontiguousarray(g)
 
 
 # ---------------------------------------------------------------- camera (RayTracer.cpp:38-65)
@@ -936,13 +947,7 @@ class Scene:
         the RGBA frame, (H, W, 4) or (H, W, 3) float32 (alpha's gradient is ignored: alpha does not depend on SH); returns
         the (n, 16, 3) gradient of the table, grad[g, q, ch] = sum of w * Y_q * G[p, ch] / ns over the hits of Gaussian g
         whose channel ch the clamp at 0 let through. The sum's order is unspecified (float atomics)."""
-        W, H = int(ubo["width"][0]), int(ubo["height"][0])
-        g = np.asarray(grad_image, np.float32)
-        if g.ndim != 3 or g.shape[:2] != (H, W) or g.shape[2] not in (3, 4):
-            raise GsrtError(E_ARG, "sh_grad: an (H, W, 4) or (H, W, 3) array")
-        if g.shape[2] == 3:
-            g = np.concatenate([g, np.zeros((H, W, 1), np.float32)], axis=2)
-        g = np.ascontiguousarray(g)
+        g = _rgba_grad("sh_grad", ubo, grad_image)
         out = np.zeros((self.n, 16, 3), np.float32)
         _check(lib.gsrt_render_sh_grad(self.handle, _p(ubo), mode, k, _p(g), _p(out), 0), self.ctx)
         return out
@@ -958,13 +963,7 @@ class Scene:
         gradient of the RGBA frame, (H, W, 4) float32, or (H, W, 3), padded with a zero alpha gradient; returns the (n,)
         gradient with respect to each Gaussian's opacity (the definition is in gsrt.h). A hit whose alpha the clamp at
         0.99 cut contributes +0. The sum's order is unspecified (float atomics)."""
-        W, H = int(ubo["width"][0]), int(ubo["height"][0])
-        g = np.asarray(grad_image, np.float32)
-        if g.ndim != 3 or g.shape[:2] != (H, W) or g.shape[2] not in (3, 4):
-            raise GsrtError(E_ARG, "opacity_grad: an (H, W, 4) or (H, W, 3) array")
-        if g.shape[2] == 3:
-            g = np.concatenate([g, np.zeros((H, W, 1), np.float32)], axis=2)
-        g = np.ascontiguousarray(g)
+        g = _rgba_grad("opacity_grad", ubo, grad_image)
         out = np.zeros(self.n, np.float32)
         _check(lib.gsrt_render_opacity_grad(self.handle, _p(ubo), mode, k, _p(g), _p(out), 0), self.ctx)
         return out

@@ -4,7 +4,7 @@
  * Nothing here is part of the reference boundary: a reference-side caller links gsrt.h alone. These
  * entry points serve the test suite, the bench and multi-process transports other than RCCL: diagnostic counters,
  * host mirrors of the sharded layout and of the partition rule, the host's dispatch orders (gsrt_deal_units,
- * gsrt_group_order, gsrt_unit_order), emulated gathers on one device, and the synthetic clouds of SURVEY.md §8d. They are exported by the same library.
+ * gsrt_group_order, gsrt_unit_order) and frame refusals (gsrt_debug_frame_refusal), emulated gathers on one device, and the synthetic clouds of SURVEY.md §8d. They are exported by the same library.
  */
 #ifndef GSRT_TEST_H
 #define GSRT_TEST_H
@@ -44,6 +44,14 @@ gsrt_status gsrt_deal_units(const double* cost, const uint32_t* centre, uint32_t
 gsrt_status gsrt_group_order(uint32_t groups_x, uint32_t groups_y, uint32_t fg, uint32_t row0, uint32_t row1,
                              uint32_t nranks, uint32_t* ord, uint32_t* own);
 gsrt_status gsrt_unit_order(uint32_t units, uint32_t row0, uint32_t row1, uint32_t tiles_x, uint32_t* perm);
+/* whether a whole frame is refused, and why (gsrt_plan.cpp, host logic; no device): the status and gsrt_last_error text
+ * that gsrt_render, gsrt_render_depth, gsrt_render_features, the three gradient calls and their _async forms give a frame
+ * of `mode` (the flag an entry point sets itself included) with ubo.samples = samples, for a scene with or without a built
+ * BVH, ntri mesh triangles, a feature table, SH rows. caller: 0 for an entry point that is no gradient call, 1
+ * gsrt_render_feature_grad, 2 gsrt_render_sh_grad, 3 gsrt_render_opacity_grad. msg (cap bytes, may be NULL) takes the
+ * text, cut to fit and terminated; empty with GSRT_OK. The frame-size and NULL checks of the entry points come before. */
+gsrt_status gsrt_debug_frame_refusal(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
+                                     int has_features, int has_sh, char* msg, size_t cap);
 /* the context's streams (hipStream_t) in creation order: render, prep H 0, prep L 0, prep H 1, prep L 1, update, comm
  * (NULL before gsrt_comm_init); *n = 7. For the hardware-queue map (profiles/probes/gsrt_queue_map.py) */
 gsrt_status gsrt_debug_streams(gsrt_ctx* ctx, void* out[8], uint32_t* n);
