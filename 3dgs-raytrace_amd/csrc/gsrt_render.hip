@@ -727,65 +727,6 @@ struct Stage {
 };
 static_assert(sizeof(Stage) == kGroup * 256 && sizeof(Stage) % 1024 == 0, "whole wave-instructions of 16-B pieces");
 
-// ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
-// with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
-// or a gradient frame, the backward of a feature frame to the feature table (GSRT_FLAG_FEATURE_GRAD, grad_rows). SH: the
-// scene's SH-3 rows are blended; LUT: the ExpLUT instead of the exact exponential. Twenty-two kernels: {plain, stats,
-// depth, opgrad} x SH x LUT and {feat, grad, shgrad} x LUT, named by cor_kernel and nowhere else. What a kind adds (blend_hit)
-// sits under if constexpr on these members: the other kinds' code does not change. The RGBA of feat and grad is the
-// no-SH frame's. shgrad (GSRT_FLAG_SH_GRAD, grad_rows of GradKind::sh) is the backward of a plain colour frame
-// to the SH table: SH rows always, and the plain frame's RGBA. opgrad (GSRT_FLAG_OPACITY_GRAD, grad_rows of
-// GradKind::opacity, RenderSync::grad_kind) is the backward of a plain colour frame to the opacities, with or without SH rows: every pass
-// shades its rays twice (k_render_cor), the plain blend for the ray's finals and then the same blend again with the
-// gradient terms; the plain frame's RGBA.
-enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad };
-// waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
-// spill to scratch, DESIGN.md section 3)
-constexpr uint32_t kFeatWaves = 4;
-// and for the two grad kernels, likewise (96 VGPRs, no spill at 5 waves; at 6 the no-LUT kernel spills 12 VGPRs to scratch
-// and the LUT kernel stays at 96; 5 measured 4-5 % faster than 4: DESIGN.md section 3). A/B builds (make ab AB_FLAGS=...,
-// never the product library) set GSRT_GRAD_WAVES, or GSRT_GRAD_AB: 1 leaves the stage's atomic out (timing only), 2
-// makes it count adds per row and wave-instructions instead of summing (profiles/feature_grad_cost.py); defaults at the top
-constexpr uint32_t kGradWaves = GSRT_GRAD_WAVES;
-// and for the two shgrad kernels, likewise (GSRT_SHGRAD_WAVES, DESIGN.md section 3)
-constexpr uint32_t kShGradWaves = GSRT_SHGRAD_WAVES;
-// and for the four opgrad kernels, likewise (GSRT_OPGRAD_WAVES, DESIGN.md section 3): 127 VGPRs with SH rows and 94 / 95
-// without, no scratch at 4; at 5 both SH kernels spill (63 and 66 VGPRs to scratch), at 6 two kernels do
-constexpr uint32_t kOpGradWaves = GSRT_OPGRAD_WAVES;
-struct NoPayload {};
-struct DepthPayload { float D; };      // sum of z w over the blended hits (expected view depth, premultiplied)
-struct ChannelPayload { float F[16]; };  // feat: sum of f_k w over the blended hits per channel; grad: the lane's G_k / ns
-struct RgbGradPayload { float G[3]; };   // shgrad: the lane's upstream colour gradient G_ch / ns
-// opgrad: the lane's upstream gradient G_ch / ns of all four channels, and in the second sweep the ray's finals of the
-// first: the colour C_ch and the transmittance T_end
-struct OpGradPayload { float G[4], fin[4]; };
-template <CorKind K, bool SH, bool LUT>
-struct CorVariant {
-    static constexpr bool sh = SH, lut = LUT;
-    static constexpr bool stats = K == CorKind::stats, depth = K == CorKind::depth;
-    static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad, shgrad = K == CorKind::shgrad;
-    static constexpr bool opgrad = K == CorKind::opgrad;
-    static_assert(!(feat || grad) || !SH, "feature and gradient frames evaluate no SH");
-    static_assert(!shgrad || SH, "an SH gradient frame blends the SH rows");
-    // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
-    // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
-    // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
-    // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before blend_stage: left at 4 it takes 102.
-    static constexpr uint32_t waves =
-        opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
-        : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
-    // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
-    // stage, and DMA instructions per stage (one piece per lane each)
-    static constexpr uint32_t row_pieces = feat ? 4u : 12u;
-    static constexpr uint32_t stage_pieces = SH ? 16 * kGroup : (feat ? 8 * kGroup : 4 * kGroup);
-    static constexpr uint32_t stage_ops = (stage_pieces + 63) / 64;
-    // what the kind adds to a ray's state (CorRay) and to a pixel's sums (PixelSums); empty where it adds nothing
-    using RayPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat || grad, ChannelPayload,
-                                          std::conditional_t<shgrad, RgbGradPayload,
-                                          std::conditional_t<opgrad, OpGradPayload, NoPayload>>>>;
-    using SumPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat, ChannelPayload, NoPayload>>;
-};
-
 // The wait for the stage issued `younger` stages before the most recent one: vmcnt counts VMEM operations in issue
 // order, so vmcnt(younger * stage_ops) leaves the younger stages' DMAs in flight (any other younger VMEM operation only
 // makes the wait stricter)
@@ -852,7 +793,7 @@ struct CorRay {
     float pxs, pys;
     float bs[16];
     float T, C[3];
-    typename V::RayPayload k;  // the kind's own: depth D, feat / grad F[16] (no bs there)
+    typename V::RayPayload k;  // the kind's own: depth D, feat F[16] (no bs there), a gradient kind's upstream gradient
     bool active;
     uint32_t cand, blended, term;
 #ifdef GSRT_DIAG
@@ -937,42 +878,6 @@ __device__ GSRT_INLINE float grad_stage_sums(const float (&gs)[kGroup]) {
     const u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(u), __float_as_uint(v), false, false);
     return __uint_as_float(r.x) + __uint_as_float(r.y);
 }
-// grad only: where a round's gradient goes (the gradient table's rows and the channel count), and one stage's share of
-// it: the stage's candidate ids (ids + g0 of the round's list in LDS), the candidates' row sums (blend_hit) and the mask
-// of the candidates some lane blended. The other kinds pass neither.
-struct GradDst { float* rows; uint32_t channels; };
-struct GradStage {
-    const uint32_t* ids;
-    GradDst dst;
-    float sums[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
-    uint32_t mask = 0;  // bit c: some lane blended candidate c
-};
-// shgrad only, likewise: the SH gradient table's rows (192 B per Gaussian id, [rgb][coef] as the SH rows are), and a
-// stage's share: per colour channel the candidates' row sums over the coefficients
-struct ShGradDst { float* rows; };
-struct ShGradStage {
-    const uint32_t* ids;
-    ShGradDst dst;
-    float sums[3][kGroup] = {};
-    uint32_t mask = 0;  // bit c: some lane blended candidate c
-};
-// opgrad only, second sweep, likewise: the opacity gradient table (one float per Gaussian id), and a stage's share: per
-// candidate the lane's own term d e (+0 where the lane does not blend it or its alpha was clamped), summed over the wave
-// once per stage (opgrad_stage_sums). e, open: the hit shade_stage hands to blend_hit, its exponential and whether
-// fl(|o| e) < 0.99f, i.e. whether alpha is |o| e and not the clamp's constant
-struct OpGradDst { float* rows; };
-struct OpGradStage {
-    const uint32_t* ids;
-    OpGradDst dst;
-    float t[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
-    uint32_t mask = 0;  // bit c: some lane blended candidate c
-    float e = 0.0f;
-    bool open = false;
-};
-// a stage's share of a round's destination
-__device__ GSRT_INLINE GradStage stage_of(const uint32_t* ids, const GradDst& dst) { return GradStage{ids, dst}; }
-__device__ GSRT_INLINE ShGradStage stage_of(const uint32_t* ids, const ShGradDst& dst) { return ShGradStage{ids, dst}; }
-__device__ GSRT_INLINE OpGradStage stage_of(const uint32_t* ids, const OpGradDst& dst) { return OpGradStage{ids, dst}; }
 // opgrad: a stage's four terms per lane (t[c]: candidate c) to the wave's sums, transposed: every lane l returns the wave's
 // sum of candidate l & 3. Inside a quad the butterfly of grad_row_sums' last two steps (partners i ^ 2 and i ^ 1: a lane
 // keeps the half its own lane bit names and sends the other), then the four quads of a row by two row rotations, which
@@ -993,46 +898,131 @@ __device__ GSRT_INLINE float opgrad_stage_sums(const float (&t)[kGroup]) {
     const u32x2 q = __builtin_amdgcn_permlane32_swap(__float_as_uint(u), __float_as_uint(u), false, false);
     return __uint_as_float(q.x) + __uint_as_float(q.y);
 }
-template <class T>
-__device__ GSRT_INLINE T& only(T& t) { return t; }  // the one element of a pack that holds one
-// z: the candidate's view depth (SplatRec::depth), already in a register from shade_stage's read of the record (a read
-// of its own from the stage here measured 1.5 % on the depth kernel). depth: the blend's own w also weighs it into ray.k.D
-// feat: w weighs the 16 floats of the candidate's staged feature row (feat_row) into ray.k.F, and the colour (1, as
-// without SH) into C[0] alone: r = g = b, replicated once the ray is done (PixelSums::take)
-// grad: ray.k.F holds the lane's upstream gradient G_c / ns (k_render_cor); the candidate's terms t_c = w G_c of the
-// blending lanes (+0, selected, on every other lane) are summed over each 16-lane row into the stage's sums
-// (grad_row_sums), and the colour is the feature frame's. G: the stage's GradStage there, nothing elsewhere.
-// shgrad: ray.k.G holds the lane's upstream colour gradient G_ch / ns; per colour channel the terms (w G_ch) Y_q of the
-// blending lanes whose channel is not clamped go the same way into the stage's ShGradStage; the colour is the plain frame's
-template <class V, class... G>
-__device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z, float alpha, uint64_t contrib,
-                                          CorRay<V>& ray, G&... grad) {
-    static_assert(sizeof...(G) == (V::grad || V::shgrad ? 1 : 0) || (V::opgrad && sizeof...(G) == 1),
-                  "a gradient frame's stage, and only that (opgrad: none in its first sweep)");
-    const float tn = ray.T * (1.0f - alpha);
-    const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
-    const uint64_t term = contrib & low;
-    const uint64_t blend = contrib & ~low;  // the wave-uniform branch and the mask of the accumulate
-    if (blend) {
-        float col[3] = {1.0f, 1.0f, 1.0f};
-        if (V::sh) ShFromStage{stg, c}(ray.bs, col);
-        if constexpr (V::grad) {
-            const float w = alpha * ray.T;  // the blend's own weight (T is updated below)
+// x summed over ns samples to their mean: x * (1 / ns) for a power of two (x / 2^k == x * 2^-k exactly), else x / ns
+__device__ GSRT_INLINE float over_samples(float x, uint32_t ns) {
+    const float nsf = (float)ns;
+    return (ns & (ns - 1)) == 0 ? x * (1.0f / nsf) : x / nsf;
+}
+
+// ---- gradient sinks. A gradient frame is the backward of a forward frame to one per-Gaussian table (RenderArgs::grad_in,
+// grad_rows). What its kind adds to the shading loop is one type, its sink; the loop (shade_sorted, shade_stage,
+// blend_hit) names no kind and calls the sink it is given. A sink holds where a round's terms go (of_frame) and supplies
+//   Payload, load: the lane's upstream gradient in the ray (CorRay::k) and how it is read;
+//   share(ids + g0): one stage's share of the round, a Share: the stage's candidate ids (in the round's list in LDS), the
+//     mask of the candidates some lane blended (bit c, wave-uniform) and the kind's sums. shade_stage tells it each
+//     candidate's exponential and |opacity| before the hit (candidate), blend_hit calls hit for the wave where some lane
+//     blends candidate c (T still the hit's T_i, col its colour) and hit_lane on the blending lanes once the colour is
+//     accumulated, and shade_stage ends with flush where mask is set: the stage's terms, summed over the wave, to the table.
+// The lane's upstream gradient of a colour frame: the first N floats of pixel (x, y) of grad_in, an RGBA image, scaled
+// once by 1 / ns as the forward store scales the sums; invalid lanes hold +0
+template <int N>
+__device__ GSRT_INLINE void load_upstream(float (&G)[N], uint32_t x, uint32_t y, bool valid, uint32_t ns) {
+    const KArgs& K = kargs();
+    const float* gi = K.a.grad_in + ((size_t)y * K.a.width + x) * 4;
+#pragma unroll
+    for (int q = 0; q < N; ++q) G[q] = valid ? over_samples(gi[q], ns) : 0.0f;
+}
+// The frame of a flush (shade_stage calls it only where some lane blended in the stage), PER lanes a candidate: the
+// wave's sums (sums(), every lane), and lane PER c + off adds (add) for candidate c if some lane blended it. A blended
+// candidate c is below the stage's m, so ids[c] is an entry of the round's list: its id is below n, its row in the table.
+template <uint32_t PER, class Sums, class Add>
+__device__ GSRT_INLINE void flush_share(const uint32_t* ids, uint32_t mask, Sums sums, Add add) {
+    const auto sum = sums();
+    const uint32_t l = lane_here(), c = l / PER, off = l % PER;
+    if ((PER * kGroup == 64 || c < kGroup) && ((mask >> c) & 1u)) add(lds_read_settled(ids + c), off, sum);
+}
+// No gradient: plain, stats, depth and feat frames, and the first sweep of an opgrad kernel
+struct NoGrad {
+    __device__ GSRT_INLINE static NoGrad of_frame() { return {}; }
+    struct Payload {};
+    template <class P> __device__ GSRT_INLINE static void load(P&, uint32_t, uint32_t, bool, uint32_t) {}
+    struct Share {
+        static constexpr uint32_t mask = 0;  // never a flush
+        __device__ GSRT_INLINE void candidate(float, float) {}
+        template <class Ray> __device__ GSRT_INLINE void hit(uint32_t, uint64_t, float, const float (&)[3], const Ray&) {}
+        template <class Ray> __device__ GSRT_INLINE void hit_lane(uint32_t, float, const float (&)[3], const Ray&) {}
+        __device__ GSRT_INLINE void flush() const {}
+    };
+    __device__ GSRT_INLINE Share share(const uint32_t*) const { return {}; }
+};
+// grad (GSRT_FLAG_FEATURE_GRAD): the backward of a feature frame to the feature table, rows of 16 floats of which
+// `channels` are in use; the RGBA is the feature frame's. G_c / ns per channel in the ray. A hit's terms t_c = w G_c of
+// the blending lanes (+0, selected, on every other lane) are summed over each 16-lane row into the share's sums
+// (grad_row_sums); the flush is one atomic wave-instruction, lane 16 c + ch adding the wave's sum for candidate c and
+// channel ch. A/B builds (make ab AB_FLAGS=..., never the product library) set GSRT_GRAD_AB: 1 leaves the atomic out
+// (timing only), 2 makes it count adds per row and wave-instructions instead of summing (profiles/feature_grad_cost.py)
+struct FeatureGrad {
+    float* rows;
+    uint32_t channels;  // of a row's 16 floats, the ones in use
+    __device__ GSRT_INLINE static FeatureGrad of_frame() { return {kargs().a.grad_rows, kargs().a.grad_channels}; }
+    struct Payload { float G[16]; };
+    __device__ GSRT_INLINE static void load(Payload& g, uint32_t x, uint32_t y, bool valid, uint32_t ns) {
+        const KArgs& K = kargs();  // load_upstream written out, as is the flush below: through the shared helpers the two
+        const uint32_t C = K.a.grad_channels;  // kernels' code differed and the 16-channel frame measured 0.3 % slower
+        const float* gi = K.a.grad_in + ((size_t)y * K.a.width + x) * C;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) g.G[q] = valid && (uint32_t)q < C ? over_samples(gi[q], ns) : 0.0f;
+    }
+    struct Share {
+        const uint32_t* ids;
+        float* rows;
+        uint32_t channels;  // channels from here on (G holds +0 there) are left out
+        float sums[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t mask = 0;
+        __device__ GSRT_INLINE void candidate(float, float) {}
+        template <class Ray>
+        __device__ GSRT_INLINE void hit(uint32_t c, uint64_t blend, float alpha, const float (&)[3], const Ray& ray) {
+            const float w = alpha * ray.T;  // the blend's own weight
             const bool mine = lane_of(blend);
             float t[16];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) t[q] = mine ? w * ray.k.F[q] : 0.0f;  // a select: another lane's G never enters
-            GradStage& gs = only(grad...);
-            gs.sums[c] = grad_row_sums(t);
-            gs.mask |= 1u << c;  // wave-uniform: some lane blended this candidate
+            for (int q = 0; q < 16; ++q) t[q] = mine ? w * ray.k.G[q] : 0.0f;  // a select: another lane's G never enters
+            sums[c] = grad_row_sums(t);
+            mask |= 1u << c;
         }
-        if constexpr (V::shgrad) {
-            // per channel the terms t_q = (w G_ch) Y_q of the blending lanes whose channel the clamp let through
-            // (col[ch] > 0 exactly when sh_channel's chain ended above 0), +0, selected, on every other lane; Y_q is the
-            // ray's own basis, bs[0] = kShY0: the gradient is with respect to the API's s_0, not the folded word
-            const float w = alpha * ray.T;  // the blend's own weight (T is updated below)
+        template <class Ray> __device__ GSRT_INLINE void hit_lane(uint32_t, float, const float (&)[3], const Ray&) {}
+        __device__ GSRT_INLINE void flush() const {
+            const float sum = grad_stage_sums(sums);
+            const uint32_t l = lane_here(), c = l >> 4, ch = l & 15u;
+            if (((mask >> c) & 1u) && ch < channels) {  // flush_share<16> written out
+                const uint32_t id = lds_read_settled(ids + c);
+#if GSRT_GRAD_AB == 1  // timing only: the reduction without its atomic
+                asm volatile("" ::"v"(sum), "v"(id));
+#elif GSRT_GRAD_AB == 2  // counting: channel 0 counts the adds a row receives, channel 1 the wave-instructions
+                const float one = ch == 0 || c == (uint32_t)__builtin_ctz(mask) ? 1.0f : 0.0f;
+                asm volatile("" ::"v"(sum));
+                atomicAdd(rows + (size_t)id * 16u + ch, one);
+#else
+                atomicAdd(rows + (size_t)id * 16u + ch, sum);  // no-return global_atomic_add_f32
+#endif
+            }
+        }
+    };
+    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows, channels}; }
+};
+// shgrad (GSRT_FLAG_SH_GRAD): the backward of a plain colour frame to the SH table, rows of 192 B per Gaussian id,
+// [rgb][coef] as the SH rows are; SH rows always, and the plain frame's RGBA. The upstream colour gradient G_ch / ns in
+// the ray (an RGBA image's first three floats: alpha does not depend on SH). Per colour channel a hit's terms
+// t_q = (w G_ch) Y_q of the blending lanes whose channel the clamp let through (col[ch] > 0 exactly when sh_channel's
+// chain ended above 0), +0, selected, on every other lane, are summed as grad's are; Y_q is the ray's own basis,
+// bs[0] = kShY0: the gradient is with respect to the API's s_0, not the folded word. The flush is three atomic
+// wave-instructions, one per colour channel, lane 16 c + q adding coefficient q.
+struct ShGrad {
+    float* rows;
+    __device__ GSRT_INLINE static ShGrad of_frame() { return {kargs().a.grad_rows}; }
+    struct Payload { float G[3]; };
+    __device__ GSRT_INLINE static void load(Payload& g, uint32_t x, uint32_t y, bool v, uint32_t ns) { load_upstream(g.G, x, y, v, ns); }
+    struct Share {
+        const uint32_t* ids;
+        float* rows;
+        float sums[3][kGroup] = {};
+        uint32_t mask = 0;
+        struct Rgb { float v[3]; };
+        __device__ GSRT_INLINE void candidate(float, float) {}
+        template <class Ray>
+        __device__ GSRT_INLINE void hit(uint32_t c, uint64_t blend, float alpha, const float (&col)[3], const Ray& ray) {
+            const float w = alpha * ray.T;  // the blend's own weight
             const bool mine = lane_of(blend);
-            ShGradStage& gs = only(grad...);
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const bool on = mine && col[ch] > 0.0f;
@@ -1040,11 +1030,135 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
                 float t[16];
 #pragma unroll
                 for (int q = 0; q < 16; ++q) t[q] = on ? wg * ray.bs[q] : 0.0f;
-                gs.sums[ch][c] = grad_row_sums(t);
+                sums[ch][c] = grad_row_sums(t);
             }
-            gs.mask |= 1u << c;
+            mask |= 1u << c;
         }
-        if constexpr (V::opgrad && sizeof...(G) == 1) only(grad...).mask |= 1u << c;  // the terms: below, with the blend
+        template <class Ray> __device__ GSRT_INLINE void hit_lane(uint32_t, float, const float (&)[3], const Ray&) {}
+        __device__ GSRT_INLINE void flush() const {
+            flush_share<16>(ids, mask, [&] {
+                Rgb sum;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) sum.v[ch] = grad_stage_sums(sums[ch]);
+                return sum;
+            }, [&](uint32_t id, uint32_t q, const Rgb& sum) {
+                float* row = rows + (size_t)id * 48u + q;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) atomicAdd(row + 16 * ch, sum.v[ch]);  // no-return global_atomic_add_f32
+            });
+        }
+    };
+    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows}; }
+};
+// opgrad (GSRT_FLAG_OPACITY_GRAD): the backward of a plain colour frame to the opacities (one float per Gaussian id),
+// with or without SH rows; the plain frame's RGBA. Every pass shades its rays twice (k_render_cor): the plain blend with
+// NoGrad for the ray's finals, then the same blend again with this sink. In the ray the upstream gradient G_ch / ns of
+// all four channels (alpha depends on opacity) and the first sweep's finals: the colour C_ch and the transmittance
+// T_end. candidate: the hit's exponential e and whether fl(|o| e) < 0.99f, i.e. whether alpha is |o| e and not the
+// clamp's constant. hit_lane: d(frame . G) / d(alpha) of this hit from the finals and the running colour after this
+// hit, times d(alpha) / d|o| = e where the clamp let |o| e through; a select: the lanes that do not blend c keep the
+// share's +0 in t[c]. The flush sums the lanes' terms over the wave (opgrad_stage_sums) and is one atomic
+// wave-instruction, lane c < kGroup adding candidate c's sum.
+struct OpacityGrad {
+    float* rows;
+    __device__ GSRT_INLINE static OpacityGrad of_frame() { return {kargs().a.grad_rows}; }
+    struct Payload { float G[4], fin[4]; };
+    __device__ GSRT_INLINE static void load(Payload& g, uint32_t x, uint32_t y, bool valid, uint32_t ns) {
+        load_upstream(g.G, x, y, valid, ns);
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) g.fin[ch] = 0.0f;  // k_render_cor sets them before the second sweep
+    }
+    struct Share {
+        const uint32_t* ids;
+        float* rows;
+        float t[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t mask = 0;
+        float e = 0.0f; bool open = false;
+        __device__ GSRT_INLINE void candidate(float e_, float o) { e = e_, open = o * e_ < 0.99f; }
+        template <class Ray>
+        __device__ GSRT_INLINE void hit(uint32_t c, uint64_t, float, const float (&)[3], const Ray&) { mask |= 1u << c; }
+        template <class Ray>
+        __device__ GSRT_INLINE void hit_lane(uint32_t c, float alpha, const float (&col)[3], const Ray& ray) {
+            const float r = 1.0f / (1.0f - alpha);  // alpha <= 0.99
+            float d = (ray.k.G[3] * ray.k.fin[3]) * r;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) d = d + ray.k.G[ch] * (ray.T * col[ch] - (ray.k.fin[ch] - ray.C[ch]) * r);
+            t[c] = open ? d * e : 0.0f;
+        }
+        __device__ GSRT_INLINE void flush() const {
+            flush_share<1>(ids, mask, [&] { return opgrad_stage_sums(t); },
+                           [&](uint32_t id, uint32_t, float sum) { atomicAdd(rows + id, sum); });
+        }
+    };
+    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows}; }
+};
+
+// ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
+// with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
+// or a gradient frame of the kind RenderSync::grad_kind names (the sinks above). SH: the scene's SH-3 rows are blended;
+// LUT: the ExpLUT instead of the exact exponential. Twenty-two kernels: {plain, stats, depth, opgrad} x SH x LUT and
+// {feat, grad, shgrad} x LUT, named by cor_kernel and nowhere else. What a forward kind adds sits under if constexpr on
+// these members, what a gradient kind adds in its sink: the other kinds' code does not change. The RGBA of feat and
+// grad is the no-SH frame's.
+// A new gradient kind supplies: a CorKind, its sink and line in Grad, a line in `waves`, a case in cor_kernel, launch_cor.
+enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad };
+// waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
+// spill to scratch, DESIGN.md section 3)
+constexpr uint32_t kFeatWaves = 4;
+// and for the two grad kernels, likewise (96 VGPRs, no spill at 5 waves; at 6 the no-LUT kernel spills 12 VGPRs to scratch
+// and the LUT kernel stays at 96; 5 measured 4-5 % faster than 4: DESIGN.md section 3); A/B builds: GSRT_GRAD_WAVES
+constexpr uint32_t kGradWaves = GSRT_GRAD_WAVES;
+// and for the two shgrad kernels, likewise (GSRT_SHGRAD_WAVES, DESIGN.md section 3)
+constexpr uint32_t kShGradWaves = GSRT_SHGRAD_WAVES;
+// and for the four opgrad kernels, likewise (GSRT_OPGRAD_WAVES, DESIGN.md section 3): 127 VGPRs with SH rows and 94 / 95
+// without, no scratch at 4; at 5 both SH kernels spill (63 and 66 VGPRs to scratch), at 6 two kernels do
+constexpr uint32_t kOpGradWaves = GSRT_OPGRAD_WAVES;
+struct NoPayload {};
+struct DepthPayload { float D; };      // sum of z w over the blended hits (expected view depth, premultiplied)
+struct ChannelPayload { float F[16]; };  // feat: sum of f_k w over the blended hits per channel
+template <CorKind K, bool SH, bool LUT>
+struct CorVariant {
+    static constexpr bool sh = SH, lut = LUT;
+    static constexpr bool stats = K == CorKind::stats, depth = K == CorKind::depth;
+    static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad, shgrad = K == CorKind::shgrad;
+    static constexpr bool opgrad = K == CorKind::opgrad;
+    static_assert(!(feat || grad) || !SH, "feature and gradient frames evaluate no SH");
+    static_assert(!shgrad || SH, "an SH gradient frame blends the SH rows");
+    // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
+    // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
+    // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
+    // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before blend_stage: left at 4 it takes 102.
+    static constexpr uint32_t waves =
+        opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
+        : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
+    // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
+    // stage, and DMA instructions per stage (one piece per lane each)
+    static constexpr uint32_t row_pieces = feat ? 4u : 12u;
+    static constexpr uint32_t stage_pieces = SH ? 16 * kGroup : (feat ? 8 * kGroup : 4 * kGroup);
+    static constexpr uint32_t stage_ops = (stage_pieces + 63) / 64;
+    // a gradient kind's sink; what a forward kind adds to a pixel's sums (PixelSums), empty where it adds nothing; and
+    // what the kind adds to a ray's state (CorRay): those sums, or its sink's payload
+    using Grad = std::conditional_t<grad, FeatureGrad, std::conditional_t<shgrad, ShGrad,
+                                    std::conditional_t<opgrad, OpacityGrad, NoGrad>>>;
+    using SumPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat, ChannelPayload, NoPayload>>;
+    using RayPayload = std::conditional_t<std::is_same_v<Grad, NoGrad>, SumPayload, typename Grad::Payload>;
+};
+// z: the candidate's view depth (SplatRec::depth), already in a register from shade_stage's read of the record (a read
+// of its own from the stage here measured 1.5 % on the depth kernel). depth: the blend's own w also weighs it into ray.k.D
+// feat: w weighs the 16 floats of the candidate's staged feature row (feat_row) into ray.k.F, and the colour (1, as
+// without SH) into C[0] alone: r = g = b, replicated once the ray is done (PixelSums::take); grad's colour is feat's.
+// grad: the stage's share of the frame's sink (Share of V::Grad, or of NoGrad), told of the hit where some lane blends
+template <class V, class Sh>
+__device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z, float alpha, uint64_t contrib,
+                                          CorRay<V>& ray, Sh& grad) {
+    const float tn = ray.T * (1.0f - alpha);
+    const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
+    const uint64_t term = contrib & low;
+    const uint64_t blend = contrib & ~low;  // the wave-uniform branch and the mask of the accumulate
+    if (blend) {
+        float col[3] = {1.0f, 1.0f, 1.0f};
+        if (V::sh) ShFromStage{stg, c}(ray.bs, col);
+        grad.hit(c, blend, alpha, col, ray);  // T is updated below
         if (lane_of(blend)) {
             const float w = alpha * ray.T;
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
@@ -1066,18 +1180,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
                     ray.k.F[4 * q + 3] = fmaf(f.w, w, ray.k.F[4 * q + 3]);
                 }
             }
-            if constexpr (V::opgrad && sizeof...(G) == 1) {
-                // second sweep: d(frame . G) / d(alpha) of this hit from the ray's finals (ray.k.fin, the first sweep's)
-                // and the running colour after this hit, times d(alpha) / d|o| = e where the clamp let |o| e through;
-                // ray.T is still T_i. A select: the lanes that do not blend c keep the stage's +0 in t[c]
-                OpGradStage& gs = only(grad...);
-                const float r = 1.0f / (1.0f - alpha);  // alpha <= 0.99
-                float d = (ray.k.G[3] * ray.k.fin[3]) * r;
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch)
-                    d = d + ray.k.G[ch] * (ray.T * col[ch] - (ray.k.fin[ch] - ray.C[ch]) * r);
-                gs.t[c] = gs.open ? d * gs.e : 0.0f;
-            }
+            grad.hit_lane(c, alpha, col, ray);  // the colour after this hit, ray.T still T_i
             ray.T = tn;
             if (V::stats) ++ray.blended;
         }
@@ -1194,12 +1297,9 @@ __device__ GSRT_INLINE void blend_stage(const Stage* stg, const StageBlends& sb,
 
 // Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
 // compile time (the steady state of shade_sorted), so no candidate is tested against m.
-// grad: the stage's terms w G go to the gradient table (go.dst) in one atomic wave-instruction, lane 16 c + ch adding
-// the wave's sum for candidate c and channel ch, masked to the candidates some lane blended and to the channels in use.
-// shgrad: likewise three wave-instructions, one per colour channel, lane 16 c + q adding coefficient q.
-// opgrad, second sweep (the one with a stage in G): one wave-instruction, lane c adding candidate c's sum.
-template <class V, bool FULL, class... G>
-__device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay<V>& ray, G... grad) {
+// grad: the stage's share of the frame's sink; its terms go to the sink's table once the stage is shaded (flush).
+template <class V, bool FULL, class Sh>
+__device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const float* lut_s, CorRay<V>& ray, Sh grad) {
     constexpr bool LUT = V::lut;
     if constexpr (!V::stats) {
         // Phase 1, g of all kGroup candidates at once (independent chains, one LDS wait): g first because lanes
@@ -1257,78 +1357,18 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_blend += __ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f) ? 1u : 0u;
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
+            grad.candidate(e, fabsf(q1.w));  // what a hit's term may need besides the blend's own values
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
-            if constexpr (V::opgrad && sizeof...(G) == 1) {  // what the hit's term needs besides the blend's own values
-                only(grad...).e = e;
-                only(grad...).open = fabsf(q1.w) * e < 0.99f;
-            }
             uint64_t stopped;
             if constexpr (kShPerLane<V>) stopped = weigh_hit<V>(c, alpha, contrib, ray, sb);
-            else stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad...);
+            else stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad);
             if (stopped) {
 #pragma unroll
                 for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
             }
         }
         if constexpr (kShPerLane<V>) blend_stage<V>(stg, sb, ray);
-        if constexpr (V::grad) {
-            const GradStage& go = only(grad...);
-            const uint32_t gmask = go.mask;
-            if (gmask) {  // wave-uniform: a stage no lane blended adds nothing
-                const float sum = grad_stage_sums(go.sums);
-                const uint32_t l = lane_here(), c = l >> 4, ch = l & 15u;
-                // a blended candidate c is below m, so ids[c] is an entry of the round's list: its id is below n and its
-                // row inside the table; channels from `channels` on (G holds +0 there) are left out
-                if (((gmask >> c) & 1u) && ch < go.dst.channels) {
-                    const uint32_t id = lds_read_settled(go.ids + c);
-#if GSRT_GRAD_AB == 1  // timing only: the reduction without its atomic
-                    asm volatile("" ::"v"(sum), "v"(id));
-#elif GSRT_GRAD_AB == 2  // counting: channel 0 counts the adds a row receives, channel 1 the wave-instructions
-                    const float one = ch == 0 || c == (uint32_t)__builtin_ctz(gmask) ? 1.0f : 0.0f;
-                    asm volatile("" ::"v"(sum));
-                    atomicAdd(go.dst.rows + (size_t)id * 16u + ch, one);
-#else
-                    atomicAdd(go.dst.rows + (size_t)id * 16u + ch, sum);  // no-return global_atomic_add_f32
-#endif
-                }
-            }
-        }
-        if constexpr (V::shgrad) {
-            // three atomic wave-instructions per stage, one per colour channel: lane 16 c + q adds the wave's sum for
-            // candidate c and coefficient q to the row's channel, masked to the candidates some lane blended
-            const ShGradStage& go = only(grad...);
-            const uint32_t gmask = go.mask;
-            if (gmask) {  // wave-uniform: a stage no lane blended adds nothing
-                float sum[3];
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) sum[ch] = grad_stage_sums(go.sums[ch]);
-                const uint32_t l = lane_here(), c = l >> 4, q = l & 15u;
-                // a blended candidate c is below m, so ids[c] is an entry of the round's list: its id is below n and its
-                // 48-float row inside the table
-                if ((gmask >> c) & 1u) {
-                    const uint32_t id = lds_read_settled(go.ids + c);
-                    float* row = go.dst.rows + (size_t)id * 48u + q;
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) atomicAdd(row + 16 * ch, sum[ch]);  // no-return global_atomic_add_f32
-                }
-            }
-        }
-        if constexpr (V::opgrad && sizeof...(G) == 1) {
-            // one atomic wave-instruction per stage: lane c < kGroup adds the wave's sum of candidate c's terms to the
-            // table's entry of its id, masked to the candidates some lane blended
-            const OpGradStage& go = only(grad...);
-            const uint32_t gmask = go.mask;
-            if (gmask) {  // wave-uniform: a stage no lane blended adds nothing
-                const float sum = opgrad_stage_sums(go.t);
-                const uint32_t l = lane_here();
-                // a blended candidate c is below m, so ids[c] is an entry of the round's list: its id is below n and its
-                // float inside the table
-                if (l < kGroup && ((gmask >> l) & 1u)) {
-                    const uint32_t id = lds_read_settled(go.ids + l);
-                    atomicAdd(go.dst.rows + id, sum);  // no-return global_atomic_add_f32
-                }
-            }
-        }
+        if (grad.mask) grad.flush();  // wave-uniform: a stage no lane blended adds nothing
     } else {
         for (uint32_t c = 0; c < m; ++c) {
             // counting pass: every AABB candidate of every active ray is counted (no g-first skip)
@@ -1351,7 +1391,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
                     }
                 }
             }
-            blend_hit<V>(stg, c, q0.w, alpha, __ballot(alpha > 0.0f), ray);
+            blend_hit<V>(stg, c, q0.w, alpha, __ballot(alpha > 0.0f), ray, grad);
         }
     }
 }
@@ -1361,21 +1401,22 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
 // Three stage buffers: while stage k is shaded, the DMAs of stages k+1 and k+2 are in flight; wait_stage waits
 // for stage k's own DMA only. No DMA stays in flight past a return (the LDS is reused by the next round or by
 // the next workgroup).
-// grad: every shaded stage also adds its terms to the gradient table gdst (shade_stage); its atomics are younger than
-// the DMAs the counted waits wait for, so those waits only become stricter, and the last wait covers them too.
-template <class V, class... G>
+// sink: where a gradient frame's terms go (V::Grad, or NoGrad). Every shaded stage then also adds its share to the
+// sink's table (shade_stage); its atomics are younger than the DMAs the counted waits wait for, so those waits only
+// become stricter, and the last wait covers them too.
+template <class V, class S>
 __device__ GSRT_INLINE bool shade_sorted(const uint32_t* ids, uint32_t count, Stage* stA, Stage* stB, Stage* stC,
-                             const float* lut_s, CorRay<V>& ray, const SplatRec* recs, const float* sh, G... gdst) {
+                             const float* lut_s, CorRay<V>& ray, const SplatRec* recs, const float* sh, S sink) {
     const uint32_t lane = lane_id();
     count = __builtin_amdgcn_readfirstlane(count);  // wave-uniform: stage bounds as scalar compares
     if (count == 0) return __ballot(ray.active) != 0;
     auto issue = [&](uint32_t g, Stage* dst) { stage_issue<V>(ids, count, g, lane, dst, recs, sh); };
     auto shade = [&](Stage* stg, uint32_t g) {
         const uint32_t m = count - g < kGroup ? count - g : kGroup;
-        shade_stage<V, false>(stg, m, lut_s, ray, stage_of(ids + g, gdst)...);
+        shade_stage<V, false>(stg, m, lut_s, ray, sink.share(ids + g));
     };
     auto shade_full = [&](Stage* stg, uint32_t g) {
-        shade_stage<V, true>(stg, kGroup, lut_s, ray, stage_of(ids + g, gdst)...);
+        shade_stage<V, true>(stg, kGroup, lut_s, ray, sink.share(ids + g));
     };
     constexpr uint32_t kWaitTwo = 2 * V::stage_ops;  // the two younger stages' DMAs stay in flight
     // stages issued after stage g's DMA when it is read: those of g + kGroup and g + 2 kGroup that exist
@@ -1895,12 +1936,6 @@ struct CorTile {
     }
 };
 
-// x summed over ns samples to their mean: x * (1 / ns) for a power of two (x / 2^k == x * 2^-k exactly), else x / ns
-__device__ GSRT_INLINE float over_samples(float x, uint32_t ns) {
-    const float nsf = (float)ns;
-    return (ns & (ns - 1)) == 0 ? x * (1.0f / nsf) : x / nsf;
-}
-
 // What a pixel outputs, summed over its samples: the colour and what the kind adds (depth: D, feat: 16 channels).
 // each visits every float in a fixed order (rgba, depth, channels 0..15), unrolled: nothing is indexed dynamically.
 template <class V>
@@ -1977,36 +2012,7 @@ __device__ GSRT_INLINE CorRay<V> cor_ray(const CorTile::Pixel& p, uint32_t S, ui
 #pragma unroll
         for (int q = 0; q < 16; ++q) ray.k.F[q] = 0.0f;
     }
-    if constexpr (V::grad) {
-        // the pixel's upstream gradient, scaled once by 1 / ns as the forward store scales the sums; channels from
-        // grad_channels on and invalid lanes hold +0 (unrolled, a uniform guard: F is never indexed dynamically)
-        const KArgs& K = kargs();
-        const uint32_t C = K.a.grad_channels, ns = S * passes;
-        const float* gi = K.a.grad_in + ((size_t)p.y * K.a.width + p.x) * C;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) ray.k.F[q] = p.valid && (uint32_t)q < C ? over_samples(gi[q], ns) : 0.0f;
-    }
-    if constexpr (V::shgrad) {
-        // the pixel's upstream colour gradient (an RGBA image's first three floats: alpha does not depend on SH), scaled
-        // once by 1 / ns; invalid lanes hold +0
-        const KArgs& K = kargs();
-        const uint32_t ns = S * passes;
-        const float* gi = K.a.grad_in + ((size_t)p.y * K.a.width + p.x) * 4;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) ray.k.G[ch] = p.valid ? over_samples(gi[ch], ns) : 0.0f;
-    }
-    if constexpr (V::opgrad) {
-        // the pixel's upstream gradient of all four channels (alpha depends on opacity), scaled once by 1 / ns; invalid
-        // lanes hold +0. The finals are the first sweep's results (k_render_cor sets them before the second)
-        const KArgs& K = kargs();
-        const uint32_t ns = S * passes;
-        const float* gi = K.a.grad_in + ((size_t)p.y * K.a.width + p.x) * 4;
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) {
-            ray.k.G[ch] = p.valid ? over_samples(gi[ch], ns) : 0.0f;
-            ray.k.fin[ch] = 0.0f;
-        }
-    }
+    V::Grad::load(ray.k, p.x, p.y, p.valid, S * passes);  // a gradient kind: the pixel's upstream gradient
     ray.active = p.valid;
     if (!p.valid) ray.pxs = __builtin_nanf("");  // see blend_hit
     ray.cand = ray.blended = ray.term = 0;
@@ -2201,18 +2207,11 @@ void k_render_cor(const KArgs karg) {
 #endif
                 ++st_rounds;
                 if (cl.total > maxc) maxc = cl.total;
-                bool live;
-                if constexpr (V::grad)
-                    live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
-                                           GradDst{kargs().a.grad_rows, kargs().a.grad_channels});
-                else if constexpr (V::shgrad)
-                    live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, ShGradDst{kargs().a.grad_rows});
-                else if constexpr (V::opgrad)
-                    live = sweep == 0 ? shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp)
-                                      : shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp,
-                                                        OpGradDst{kargs().a.grad_rows});
-                else
-                    live = shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp);
+                // a gradient kind's terms go to its sink (opgrad: in the second sweep; the first is the plain blend)
+                // a gradient kind's terms go to its sink; opgrad: in the second sweep, the first is the plain blend
+                const bool live = V::opgrad && sweep == 0
+                    ? shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, NoGrad{})
+                    : shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, V::Grad::of_frame());
 #ifdef GSRT_DIAG
                 diag_last = __builtin_amdgcn_s_memtime();
                 diag_shade += diag_last - d1;
