@@ -102,6 +102,7 @@ struct gsrt_comm_state {
 };
 
 using gsrt::fail;
+#define GSRT_TRY(expr) do { if (gsrt_status _s = (expr); _s != GSRT_OK) return _s; } while (0)
 
 namespace gsrt {
 // GSRT_DEBUG_RANK_OF=N or N:r (measurement knob, read on a loopback communicator): one GPU runs rank r's (default 0)
@@ -319,41 +320,294 @@ gsrt_status decide_bands(uint32_t tiles_y, uint32_t nranks, const uint32_t* cur,
     return GSRT_OK;
 }
 
+const char* const kPartitionMismatch = "the ranks rendered different partitions (profile hash mismatch)";
+
+// One sharded frame, described once (describe_frame) and read by every phase of gsrt_render_sharded_async
+struct ShardFrame {
+    uint32_t PN = 1, PR = 0;  // the plan's ranks: the real ones, or the share of a loopback communicator (debug_rank_of)
+    bool emu = false;         // such a share
+    bool root = false;        // unpacks the gathered blocks (the gather buffers belong to the real rank 0)
+    bool cor = false, d8 = false;
+    bool profiled = false;    // takes part in the profile schedule
+    uint32_t key[4] = {};     // {tiles_y, ranks, tile height, root weight bits}: the frame geometry bands are kept for
+    float root_w = 1.0f;
+    gsrt::RenderPlan plan;    // the partition
+    uint32_t per_rank = 0;    // packed stride of every rank in the gather, in tiles
+    Dump8Layout L;
+    size_t send_floats = 0;   // the block each rank sends (in 32-bit words): RGBA32F tiles, or dump codes + escape list
+    size_t px = 0;            // the frame's pixels
+    uint32_t frame = 0;       // its number among the sharded frames
+    bool profile = false;     // a profile frame: the render kernel stores each tile's cost (d_tcost): reduce_profile
+    bool costs = false;       // d_tcost is written (a profile frame, or gsrt_debug_share_costs)
+    uint32_t p = 0, qp = 0;   // the parity of its packed / gather buffers, and of its profile's host copies
+};
+
 // The partition of the next sharded frame (see the file comment): pinned bands, or the current bands of this frame
 // geometry, updated from the profile taken kProfileEvery frames earlier. Profile frames follow a fixed schedule (every
 // kProfileEvery-th sharded COR frame, pinned or not), so every rank joins the same all-reduces; each checks the
-// partition hashes they carried. Deterministic on every rank.
-gsrt_status choose_bands(gsrt_ctx* ctx, const gsrt_ubo& ubo, uint32_t mode, uint32_t PN, bool profiled,
-                         const uint32_t key[4], float root_w, uint32_t tiles_y) {
+// partition hashes they carried. Deterministic on every rank. (F.plan: the even plan of the geometry.)
+gsrt_status choose_bands(gsrt_ctx* ctx, const gsrt_ubo& ubo, uint32_t mode, const ShardFrame& F) {
     gsrt_comm_state* cs = ctx->comm;
+    const uint32_t PN = F.PN, tiles_y = F.plan.tiles_y;
     if (cs->pinned) {
         if (cs->bands.size() != PN + 1 || cs->bands[PN] != tiles_y)
             return gsrt::fail(ctx, GSRT_E_ARG, "the pinned bands (gsrt_set_bands) do not fit this frame");
-    } else if (std::memcmp(key, cs->bands_key, sizeof cs->bands_key) != 0) {  // a new frame geometry: even bands
+    } else if (std::memcmp(F.key, cs->bands_key, sizeof cs->bands_key) != 0) {  // a new frame geometry: even bands
         const gsrt::RenderPlan p0 = gsrt::make_plan(ubo, mode, 0, 0, PN);
         cs->bands.assign(p0.bands.row, p0.bands.row + PN + 1);
-        std::memcpy(cs->bands_key, key, sizeof cs->bands_key);
+        std::memcpy(cs->bands_key, F.key, sizeof cs->bands_key);
     }
     const uint32_t f = cs->frames;
-    if (!profiled || f % kProfileEvery != 0 || f < kProfileEvery) return GSRT_OK;
+    if (!F.profiled || f % kProfileEvery != 0 || f < kProfileEvery) return GSRT_OK;
     const uint32_t q = (f / kProfileEvery + 1) % 2;  // the profile of frame f - kProfileEvery
     if (!cs->prof_pending[q]) return GSRT_OK;
     GSRT_HIP(ctx, hipEventSynchronize(cs->ev_prof[q]));
     cs->prof_pending[q] = false;
-    if (std::memcmp(cs->prof_key[q], key, sizeof cs->bands_key) != 0) return GSRT_OK;  // another geometry's
+    if (std::memcmp(cs->prof_key[q], F.key, sizeof cs->bands_key) != 0) return GSRT_OK;  // another geometry's
     std::vector<uint32_t> nb(PN + 1);
-    if (decide_bands(tiles_y, PN, cs->bands.data(), cs->pinned, cs->h_prof[q], cs->prof_hash[q], root_w, nb.data()) !=
+    if (decide_bands(tiles_y, PN, cs->bands.data(), cs->pinned, cs->h_prof[q], cs->prof_hash[q], F.root_w, nb.data()) !=
         GSRT_OK) {
         cs->comm_error = true;
-        return gsrt::fail(ctx, GSRT_E_COMM, "the ranks rendered different partitions (profile hash mismatch)");
+        return gsrt::fail(ctx, GSRT_E_COMM, kPartitionMismatch);
     }
     cs->bands = nb;
+    return GSRT_OK;
+}
+
+// Who this rank is, the partition of this frame (choose_bands) and what follows from it. Counts the frame.
+gsrt_status describe_frame(gsrt_ctx* ctx, const gsrt_ubo& ubo, uint32_t mode, uint32_t k, ShardFrame& F) {
+    gsrt_comm_state* cs = ctx->comm;
+    const int N = cs->nranks, R = cs->rank;
+    uint32_t en = 0, er = 0;  // rank-share emulation on a loopback communicator (debug_rank_of)
+    F.emu = N == 1 && cs->comm && gsrt::debug_rank_of(mode, en, er);
+    F.PN = F.emu ? en : (uint32_t)N, F.PR = F.emu ? er : (uint32_t)R;
+    F.root = F.emu ? er == 0 : R == 0;
+    F.cor = (mode & 0xffu) == GSRT_MODE_COR;
+    F.d8 = (mode & GSRT_FLAG_OUT_DUMP8) != 0;
+    // the partition: balanced from the ranks' cost profiles on a real N-rank communicator (COR frames)
+    F.plan = gsrt::make_plan(ubo, mode, k, F.PR, F.PN);
+    F.root_w = F.cor ? gsrt::root_weight(F.PN, ubo.samples, mode) : 1.0f;
+    uint32_t wbits;
+    std::memcpy(&wbits, &F.root_w, sizeof wbits);
+    F.key[0] = F.plan.tiles_y, F.key[1] = F.PN, F.key[2] = F.plan.th, F.key[3] = wbits;
+    // profile frames: a fixed schedule of the sharded COR frames, whether this rank pinned its bands or not, so every
+    // rank of the job joins the same all-reduces (a rank share on a loopback communicator takes them too, from its own
+    // rows' costs only: it exercises the profile path on one GPU; the bench pins its bands, which are then kept)
+    F.profiled = F.cor && !(mode & GSRT_FLAG_STATS) && cs->comm && (N > 1 || F.emu);
+    GSRT_TRY(choose_bands(ctx, ubo, mode, F));
+    F.plan = gsrt::make_plan(ubo, mode, k, F.PR, F.PN, cs->bands.data());
+    F.plan.packed = cs->comm != nullptr;  // (without a communicator: one rank, straight into the framebuffer)
+    cs->last_bands = cs->bands;
+    F.frame = cs->frames++;
+    F.px = (size_t)ubo.width * ubo.height;
+    F.per_rank = gsrt::max_local_tiles(F.plan);
+    F.L = dump8_layout(F.per_rank, F.plan.tw * F.plan.th);
+    F.send_floats = F.d8 ? F.L.block : F.per_rank * (4ull * F.plan.tw * F.plan.th);
+    F.profile = F.profiled && F.frame % kProfileEvery == 0;
+    F.costs = F.profile || (cs->share_costs && F.cor && !(mode & GSRT_FLAG_STATS));
+    F.p = cs->parity;
+    F.qp = (F.frame / kProfileEvery) % 2;
+    return GSRT_OK;
+}
+
+// One way to regrow a group of buffers that share a size field: wait until nothing uses the old ones, free them, null
+// them, zero the size (a failed malloc leaves no stale size: the next frame regrows), allocate, set the size. What a
+// group resets or fills beside that stays with its caller; it resets first, so that no flag outlives the buffers it
+// speaks of whichever step fails. What each group waits for:
+//   ctx->d_fb                   rank 0's unpack (comm stream)                                          comm stream
+//   packed[2]                   the share's render (compute streams), the gather (comm stream)         device
+//   gbuf[2], inbound            the gather, the stand-in receive, the unpacks (comm stream)            comm stream
+//   d_tcost                     the share's render, the row sums (comm stream)                         both
+//   d_prof, d_prof_red, h_prof  a render, the row sums, the all-reduce and its copies (comm stream)    both
+//   d_accum[2]                  the share's render                                                     device
+//   d_codes                     rank 0's dump8 unpack (comm stream)                                    comm stream
+enum : unsigned { kQuietComm = 1u, kQuietDevice = 2u };
+struct Slot {  // one buffer of a group; pinned: page-locked host memory
+    void** at;
+    bool pinned;
+    template <class T> Slot(T*& buf, bool pinned = false) : at(reinterpret_cast<void**>(&buf)), pinned(pinned) {}
+};
+template <class Size>
+gsrt_status regrow(gsrt_ctx* ctx, unsigned quiet, std::initializer_list<Slot> group, Size& size, Size need,
+                   size_t bytes) {
+    if (quiet & kQuietComm) GSRT_TRY(gsrt_comm_sync_internal(ctx));
+    if (quiet & kQuietDevice) GSRT_HIP(ctx, hipDeviceSynchronize());
+    for (const Slot& b : group) {
+        (void)(b.pinned ? hipHostFree(*b.at) : hipFree(*b.at));
+        *b.at = nullptr;
+    }
+    size = 0;
+    for (const Slot& b : group) GSRT_HIP(ctx, b.pinned ? hipHostMalloc(b.at, bytes) : hipMalloc(b.at, bytes));
+    size = need;
+    return GSRT_OK;
+}
+template <class Size>  // the zero fill of a buffer regrow just allocated: a failed fill gives the size back
+gsrt_status zero_new(gsrt_ctx* ctx, void* buf, size_t bytes, Size& size) {
+    const hipError_t filled = hipMemset(buf, 0, bytes);
+    if (filled != hipSuccess) size = 0;
+    GSRT_HIP(ctx, filled);
+    return GSRT_OK;
+}
+
+// the context's framebuffer (sharded frames land in d_fb: rank 0's unpack), and what readers of the last frame go by
+gsrt_status prepare_framebuffer(gsrt_ctx* ctx, const gsrt_ubo& ubo, const ShardFrame& F) {
+    if (ctx->fb_pixels < F.px * 4)  // (an unpack may be in flight)
+        GSRT_TRY(regrow(ctx, kQuietComm, {ctx->d_fb}, ctx->fb_pixels, F.px * 4, sizeof(float) * 4 * F.px));
+    ctx->last_w = ubo.width, ctx->last_h = ubo.height;
+    ctx->last_stats = false;
+    ctx->last_depth = ctx->last_feat = false;  // (gsrt_depth_buffer, gsrt_feature_buffer: no depth or feature image)
+    ctx->fb_view = nullptr;
+    ctx->fb_dump8 = F.d8;     // a dump8 frame leaves no RGBA32F image (gsrt_dump8_read reads it)
+    return GSRT_OK;
+}
+
+// the buffers of the exchange and of the profile, before the frame takes its parity
+gsrt_status ensure_exchange_buffers(gsrt_ctx* ctx, const ShardFrame& F) {
+    gsrt_comm_state* cs = ctx->comm;
+    const size_t send = F.send_floats, all = send * F.PN, others = send * (F.PN - 1), fl = sizeof(float);
+    if (cs->packed_floats < send) {
+        cs->esc_at[0] = cs->esc_at[1] = kNoHeader;
+        GSRT_TRY(regrow(ctx, kQuietDevice, {cs->packed[0], cs->packed[1]}, cs->packed_floats, send, fl * send));
+    }
+    if (cs->rank == 0 && cs->gbuf_floats < all) {
+        cs->unpack_pending[0] = cs->unpack_pending[1] = false;
+        GSRT_TRY(regrow(ctx, kQuietComm, {cs->gbuf[0], cs->gbuf[1]}, cs->gbuf_floats, all, fl * all));
+    }
+    if (F.emu && F.root && cs->inbound_floats < others) {
+        GSRT_TRY(regrow(ctx, kQuietComm, {cs->inbound}, cs->inbound_floats, others, fl * others));
+        GSRT_TRY(zero_new(ctx, cs->inbound, fl * others, cs->inbound_floats));
+    }
+    const uint32_t tiles = F.per_rank, words = F.plan.tiles_y + 2;  // (a profile: the row costs + 2 hash words)
+    if (F.costs && cs->tcost_cap < tiles)
+        GSRT_TRY(regrow(ctx, kQuietComm | kQuietDevice, {cs->d_tcost}, cs->tcost_cap, tiles,
+                        sizeof(uint32_t) * (tiles ? tiles : 1)));
+    if (F.profile && cs->prof_rows < words) {
+        cs->prof_pending[0] = cs->prof_pending[1] = false;
+        GSRT_TRY(regrow(ctx, kQuietComm | kQuietDevice,
+                        {cs->d_prof, cs->d_prof_red, {cs->h_prof[0], true}, {cs->h_prof[1], true}}, cs->prof_rows,
+                        words, sizeof(uint32_t) * words));
+        GSRT_TRY(zero_new(ctx, cs->d_prof, sizeof(uint32_t) * words, cs->prof_rows));
+    }
+    return GSRT_OK;
+}
+
+// the dump8 fields of a share's RenderSync: the escape list behind the block's code words, and the sums of spp > 64
+void sync_dump8(gsrt::RenderSync& rsy, float* block, const Dump8Layout& L, float4* accum) {
+    rsy.dump8 = true;
+    rsy.esc = reinterpret_cast<uint4*>(block + L.codes);
+    rsy.esc_cap = L.cap;
+    rsy.accum = accum;
+}
+
+// The share's render into packed[p], once the gather two frames back has sent it; packed[p] is this frame's own buffer,
+// so its render kernel need not follow the previous frame's (slot streams). Records rendered[p].
+gsrt_status render_share(gsrt_scene* sc, const gsrt_ubo& ubo, const ShardFrame& F) {
+    gsrt_ctx* ctx = sc->ctx;
+    gsrt_comm_state* cs = ctx->comm;
+    const uint32_t p = F.p;
+    const size_t tile_px = (size_t)F.per_rank * F.plan.tw * F.plan.th;
+    if (F.d8 && F.plan.passes > 1 && cs->accum_px < tile_px)  // spp > 64: the running sums of packed[p]'s frame
+        GSRT_TRY(regrow(ctx, kQuietDevice, {cs->d_accum[0], cs->d_accum[1]}, cs->accum_px, tile_px,
+                        sizeof(float4) * tile_px));
+    if (F.d8 && cs->esc_at[p] != F.L.codes) {
+        // the render counts its escapes in the header, zeroed after the gather that last read packed[p] (exchange);
+        // here it is at a new place: zero it there, after that gather
+        GSRT_HIP(ctx, hipMemsetAsync(cs->packed[p] + F.L.codes, 0, 16, cs->cstream));
+        GSRT_HIP(ctx, hipEventRecord(cs->gathered[p], cs->cstream));
+    }
+    cs->esc_at[p] = F.d8 ? F.L.codes : kNoHeader;  // an RGBA32F frame writes over the header
+    gsrt::RenderSync rsy;
+    rsy.slot = gsrt::use_slot_streams(ctx, F.PN > 1);
+    rsy.private_out = true;
+    rsy.wait = cs->gathered[p];
+    rsy.sharded = true;
+    rsy.tile_cost = F.costs ? cs->d_tcost : nullptr;
+    if (F.costs) {
+        cs->sc_tiles_x = F.plan.tiles_x, cs->sc_rows = F.plan.tiles_y;
+        cs->sc_row0 = F.plan.row0(), cs->sc_row1 = F.plan.row1();
+    }
+    if (F.d8) sync_dump8(rsy, cs->packed[p], F.L, F.plan.passes > 1 ? cs->d_accum[p] : nullptr);
+    GSRT_TRY(gsrt::launch_render(sc, ubo, F.plan, cs->packed[p], nullptr, &rsy));
+    GSRT_HIP(ctx, hipEventRecord(cs->rendered[p], rsy.stream));
+    return GSRT_OK;
+}
+
+// The exchange, all of it on the comm stream: the gather of packed[p] into gbuf[p] once the share is rendered and the
+// unpack two frames back has read gbuf[p], then the root's unpack of gbuf[p] into d_fb or d_codes
+gsrt_status exchange(gsrt_ctx* ctx, const gsrt_ubo& ubo, const ShardFrame& F) {
+    gsrt_comm_state* cs = ctx->comm;
+    const uint32_t p = F.p;
+    GSRT_HIP(ctx, hipStreamWaitEvent(cs->cstream, cs->rendered[p], 0));
+    if (F.root && cs->unpack_pending[p]) GSRT_HIP(ctx, hipStreamWaitEvent(cs->cstream, cs->unpacked[p], 0));
+    gsrt::timing_mark(ctx, 4, cs->cstream);  // the exchange starts once this rank's share is rendered
+    float* const gb = cs->rank == 0 ? cs->gbuf[p] : nullptr;
+    ncclResult_t r = ncclGather(cs->packed[p], gb, F.send_floats, ncclFloat32, 0, cs->comm, cs->cstream);
+    if (r != ncclSuccess) return fail(ctx, GSRT_E_COMM, std::string("ncclGather: ") + ncclGetErrorString(r));
+    if (F.d8) GSRT_HIP(ctx, hipMemsetAsync(cs->packed[p] + F.L.codes, 0, 16, cs->cstream));  // the next render's count
+    if (F.emu && F.root)  // the other ranks' blocks landing in the gather buffer (stand-in for the receive)
+        gsrt::launch_copy_d2d(cs->cstream, gb + F.send_floats, cs->inbound, sizeof(float) * F.send_floats * (F.PN - 1));
+    GSRT_HIP(ctx, hipGetLastError());
+    GSRT_HIP(ctx, hipEventRecord(cs->gathered[p], cs->cstream));
+    if (F.root) {  // the unpack, after the gather on the comm stream
+        if (F.d8) {  // of the codes into rank 0's code framebuffer (gsrt_dump8_read), grown here, behind the gather
+            if (cs->codes_px < F.px)
+                GSRT_TRY(regrow(ctx, kQuietComm, {cs->d_codes}, cs->codes_px, F.px, sizeof(uint32_t) * F.px));
+            gsrt::launch_unpack_dump8(cs->cstream, reinterpret_cast<const uint32_t*>(gb), cs->d_codes, F.plan,
+                                      ubo.width, ubo.height, F.per_rank, F.L.block);
+        } else {
+            if (cs->fb_on_render) {  // a whole frame rendered into d_fb on the render stream since the last unpack
+                GSRT_HIP(ctx, hipEventRecord(cs->ev_fb, ctx->stream));
+                GSRT_HIP(ctx, hipStreamWaitEvent(cs->cstream, cs->ev_fb, 0));
+                cs->fb_on_render = false;
+            }
+            gsrt::launch_unpack(cs->cstream, gb, ctx->d_fb, F.plan, ubo.width, ubo.height, F.per_rank);
+        }
+        GSRT_HIP(ctx, hipGetLastError());
+        GSRT_HIP(ctx, hipEventRecord(cs->unpacked[p], cs->cstream));
+        cs->unpack_pending[p] = true;
+        if (!F.d8) cs->fb_on_comm = true;
+    }
+    gsrt::timing_mark(ctx, 5, cs->cstream);
+    cs->d8_last = F.d8;  // for gsrt_dump8_read
+    cs->d8_root = F.root;
+    if (F.d8) {
+        cs->d8_plan = F.plan;
+        cs->d8_layout = F.L;
+        cs->d8_w = ubo.width, cs->d8_h = ubo.height;
+    }
+    return GSRT_OK;
+}
+
+// A profile frame, after its exchange on the comm stream: the tile costs (d_tcost) summed per row into d_prof (zeroed
+// after its previous all-reduce), every rank's row costs to every rank (max: a row has one contributor) with this
+// rank's partition hash, and the page-locked copy choose_bands reads kProfileEvery frames on
+gsrt_status reduce_profile(gsrt_ctx* ctx, const ShardFrame& F) {
+    gsrt_comm_state* cs = ctx->comm;
+    const uint32_t qp = F.qp, rows = F.plan.tiles_y;
+    if (cs->prof_pending[qp]) GSRT_HIP(ctx, hipEventSynchronize(cs->ev_prof[qp]));  // h_hash[qp] is free again
+    gsrt::launch_row_sum(cs->cstream, cs->d_tcost, cs->d_prof, F.plan.tiles_x, F.plan.row0(), F.plan.row1());
+    const uint32_t hsh = plan_hash(F.plan, F.per_rank, cs->pinned);
+    cs->h_hash[qp][0] = hsh, cs->h_hash[qp][1] = ~hsh;
+    GSRT_HIP(ctx, hipMemcpyAsync(cs->d_prof + rows, cs->h_hash[qp], 2 * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                 cs->cstream));
+    ncclResult_t r = ncclAllReduce(cs->d_prof, cs->d_prof_red, rows + 2, ncclUint32, ncclMax, cs->comm, cs->cstream);
+    if (r != ncclSuccess) return fail(ctx, GSRT_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
+    GSRT_HIP(ctx, hipMemsetAsync(cs->d_prof, 0, sizeof(uint32_t) * (rows + 2), cs->cstream));
+    GSRT_HIP(ctx, hipMemcpyAsync(cs->h_prof[qp], cs->d_prof_red, sizeof(uint32_t) * (rows + 2), hipMemcpyDeviceToHost,
+                                 cs->cstream));
+    GSRT_HIP(ctx, hipEventRecord(cs->ev_prof[qp], cs->cstream));
+    cs->prof_pending[qp] = true;
+    cs->prof_hash[qp] = hsh;
+    std::memcpy(cs->prof_key[qp], F.key, sizeof F.key);
     return GSRT_OK;
 }
 }  // namespace
 
 extern "C" {
 
+// A sharded frame, phase by phase. The compute streams take the share's render into packed[p]; the comm stream takes,
+// in this order, the gather packed[p] -> gbuf[p], the root's unpack gbuf[p] -> d_fb (or d_codes), and on a profile
+// frame the row sums d_tcost -> d_prof and the all-reduce d_prof -> d_prof_red -> h_prof[qp].
 gsrt_status gsrt_render_sharded_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k) {
     if (!sc || !ubo) return GSRT_E_ARG;
     gsrt_ctx* ctx = sc->ctx;
@@ -365,234 +619,24 @@ gsrt_status gsrt_render_sharded_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint3
         return fail(ctx, GSRT_E_ARG, "triangle meshes are co-traced in REF mode only");
     (void)hipSetDevice(ctx->device);
     gsrt_comm_state* cs = ctx->comm;
-    if (cs->comm_error) return fail(ctx, GSRT_E_COMM, "the ranks rendered different partitions (profile hash mismatch)");
-    const int N = cs->nranks, R = cs->rank;
-    uint32_t en = 0, er = 0;  // rank-share emulation on a loopback communicator (debug_rank_of)
-    const bool emu = N == 1 && cs->comm && gsrt::debug_rank_of(mode, en, er);
-    const uint32_t PN = emu ? en : (uint32_t)N, PR = emu ? er : (uint32_t)R;  // the plan's ranks
-    const bool root = emu ? er == 0 : R == 0;  // unpacks the gathered blocks
-    const bool cor = (mode & 0xffu) == GSRT_MODE_COR;
-    const bool d8 = (mode & GSRT_FLAG_OUT_DUMP8) != 0;
-    if (d8 && (!cor || (mode & GSRT_FLAG_STATS) || !cs->comm))
+    if (cs->comm_error) return fail(ctx, GSRT_E_COMM, kPartitionMismatch);
+    if ((mode & GSRT_FLAG_OUT_DUMP8) && ((mode & 0xffu) != GSRT_MODE_COR || (mode & GSRT_FLAG_STATS) || !cs->comm))
         return fail(ctx, GSRT_E_ARG, "GSRT_FLAG_OUT_DUMP8: COR frames without GSRT_FLAG_STATS on a communicator only");
-    // the partition: balanced from the ranks' cost profiles on a real N-rank communicator (COR frames)
-    const gsrt::RenderPlan even = gsrt::make_plan(*ubo, mode, k, PR, PN);
-    const float root_w = cor ? gsrt::root_weight(PN, ubo->samples, mode) : 1.0f;
-    uint32_t wbits;
-    std::memcpy(&wbits, &root_w, sizeof wbits);
-    const uint32_t key[4] = {even.tiles_y, PN, even.th, wbits};
-    // profile frames: a fixed schedule of the sharded COR frames, whether this rank pinned its bands or not, so every
-    // rank of the job joins the same all-reduces (a rank share on a loopback communicator takes them too, from its own
-    // rows' costs only: it exercises the profile path on one GPU; the bench pins its bands, which are then kept)
-    const bool profiled = cor && !(mode & GSRT_FLAG_STATS) && cs->comm && (N > 1 || emu);
-    if (gsrt_status sb = choose_bands(ctx, *ubo, mode, PN, profiled, key, root_w, even.tiles_y); sb != GSRT_OK) return sb;
-    gsrt::RenderPlan plan = gsrt::make_plan(*ubo, mode, k, PR, PN, cs->bands.data());
-    cs->last_bands = cs->bands;
-    const uint32_t frame = cs->frames++;
-    const size_t px = (size_t)ubo->width * ubo->height;
-    if (ctx->fb_pixels < px * 4) {
-        if (cs->cstream) GSRT_HIP(ctx, hipStreamSynchronize(cs->cstream));  // unpack in flight
-        (void)hipFree(ctx->d_fb);
-        ctx->d_fb = nullptr;
-        ctx->fb_pixels = 0;
-        GSRT_HIP(ctx, hipMalloc(&ctx->d_fb, sizeof(float) * 4 * px));
-        ctx->fb_pixels = px * 4;
-    }
-    ctx->last_w = ubo->width;
-    ctx->last_h = ubo->height;
-    ctx->last_stats = false;
-    ctx->last_depth = false;  // (gsrt_depth_buffer: the last frame wrote no depth image)
-    ctx->last_feat = false;   // (gsrt_feature_buffer likewise)
-    ctx->fb_view = nullptr;  // sharded frames land in d_fb (rank 0's unpack)
-    ctx->fb_dump8 = d8;      // a dump8 frame leaves no RGBA32F image (gsrt_dump8_read reads it)
+    ShardFrame F;
+    GSRT_TRY(describe_frame(ctx, *ubo, mode, k, F));   // cs->bands (choose_bands), last_bands, frames
+    GSRT_TRY(prepare_framebuffer(ctx, *ubo, F));       // d_fb, ctx->last_*
     gsrt::timing_mark(ctx, 0);
-    if (N == 1 && !cs->comm) {  // one rank without a communicator: straight into the framebuffer
-        gsrt_status s1 = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, nullptr);
+    if (cs->nranks == 1 && !cs->comm) {  // one rank without a communicator: straight into the framebuffer
+        gsrt_status s1 = gsrt::launch_render(sc, *ubo, F.plan, ctx->d_fb, nullptr);
         gsrt::timing_mark(ctx, 3);
         return s1;
     }
-    const uint32_t per_rank = gsrt::max_local_tiles(plan);  // packed stride of every rank in the gather
-    const size_t tile_floats = 4ull * plan.tw * plan.th;
-    // the block each rank sends (in 32-bit words): RGBA32F tiles, or dump codes + escape list
-    const Dump8Layout L = dump8_layout(per_rank, plan.tw * plan.th);
-    const size_t send_floats = d8 ? L.block : per_rank * tile_floats;
-    if (cs->packed_floats < send_floats) {
-        GSRT_HIP(ctx, hipDeviceSynchronize());  // the old buffers may still be in flight
-        for (int p = 0; p < 2; ++p) {
-            (void)hipFree(cs->packed[p]);
-            cs->packed[p] = nullptr;
-        }
-        cs->packed_floats = 0;
-        for (int p = 0; p < 2; ++p) {
-            GSRT_HIP(ctx, hipMalloc(&cs->packed[p], sizeof(float) * send_floats));
-            cs->esc_at[p] = kNoHeader;
-        }
-        cs->packed_floats = send_floats;
-    }
-    if (R == 0 && cs->gbuf_floats < send_floats * PN) {
-        if (gsrt_status s0 = gsrt_comm_sync_internal(ctx); s0 != GSRT_OK) return s0;
-        for (int q = 0; q < 2; ++q) {
-            (void)hipFree(cs->gbuf[q]);
-            cs->gbuf[q] = nullptr;
-            cs->unpack_pending[q] = false;
-        }
-        cs->gbuf_floats = 0;
-        for (int q = 0; q < 2; ++q) GSRT_HIP(ctx, hipMalloc(&cs->gbuf[q], sizeof(float) * send_floats * PN));
-        cs->gbuf_floats = send_floats * PN;
-    }
-    if (emu && root && cs->inbound_floats < send_floats * (PN - 1)) {
-        if (gsrt_status s0 = gsrt_comm_sync_internal(ctx); s0 != GSRT_OK) return s0;
-        (void)hipFree(cs->inbound);
-        cs->inbound = nullptr;
-        cs->inbound_floats = 0;
-        GSRT_HIP(ctx, hipMalloc(&cs->inbound, sizeof(float) * send_floats * (PN - 1)));
-        GSRT_HIP(ctx, hipMemset(cs->inbound, 0, sizeof(float) * send_floats * (PN - 1)));
-        cs->inbound_floats = send_floats * (PN - 1);
-    }
-    // a profile frame: the render kernel stores each tile's cost (d_tcost), summed per row into d_prof (zeroed after
-    // its previous all-reduce) on the comm stream
-    const uint32_t rows = plan.tiles_y;
-    const bool profile = profiled && frame % kProfileEvery == 0;
-    const bool costs = profile || (cs->share_costs && cor && !(mode & GSRT_FLAG_STATS));
-    if (costs && cs->tcost_cap < per_rank) {
-        if (gsrt_status s0 = gsrt_comm_sync_internal(ctx); s0 != GSRT_OK) return s0;
-        GSRT_HIP(ctx, hipDeviceSynchronize());  // a render may still write the old buffer
-        (void)hipFree(cs->d_tcost);
-        cs->d_tcost = nullptr;
-        cs->tcost_cap = 0;
-        GSRT_HIP(ctx, hipMalloc(&cs->d_tcost, sizeof(uint32_t) * (per_rank ? per_rank : 1)));
-        cs->tcost_cap = per_rank;
-    }
-    const uint32_t qp = (frame / kProfileEvery) % 2;
-    if (profile && cs->prof_rows < rows + 2) {
-        if (gsrt_status s0 = gsrt_comm_sync_internal(ctx); s0 != GSRT_OK) return s0;
-        GSRT_HIP(ctx, hipDeviceSynchronize());  // a render may still add into the old profile
-        (void)hipFree(cs->d_prof);
-        (void)hipFree(cs->d_prof_red);
-        cs->d_prof = cs->d_prof_red = nullptr;
-        cs->prof_rows = 0;
-        for (int q = 0; q < 2; ++q) {
-            (void)hipHostFree(cs->h_prof[q]);
-            cs->h_prof[q] = nullptr;
-            cs->prof_pending[q] = false;
-        }
-        GSRT_HIP(ctx, hipMalloc(&cs->d_prof, sizeof(uint32_t) * (rows + 2)));
-        GSRT_HIP(ctx, hipMalloc(&cs->d_prof_red, sizeof(uint32_t) * (rows + 2)));
-        for (int q = 0; q < 2; ++q) GSRT_HIP(ctx, hipHostMalloc(&cs->h_prof[q], sizeof(uint32_t) * (rows + 2)));
-        GSRT_HIP(ctx, hipMemset(cs->d_prof, 0, sizeof(uint32_t) * (rows + 2)));
-        cs->prof_rows = rows + 2;
-    }
-    const uint32_t p = cs->parity;
-    cs->parity ^= 1u;
-    cs->last_p = p;
-    const size_t tile_px = (size_t)per_rank * plan.tw * plan.th;
-    if (d8 && plan.passes > 1 && cs->accum_px < tile_px) {
-        GSRT_HIP(ctx, hipDeviceSynchronize());  // a render may still use the old sums
-        for (int q = 0; q < 2; ++q) {
-            (void)hipFree(cs->d_accum[q]);
-            cs->d_accum[q] = nullptr;
-        }
-        cs->accum_px = 0;
-        for (int q = 0; q < 2; ++q) GSRT_HIP(ctx, hipMalloc(&cs->d_accum[q], sizeof(float4) * tile_px));
-        cs->accum_px = tile_px;
-    }
-    if (d8 && cs->esc_at[p] != L.codes) {
-        // the render counts its escapes in the header, zeroed after the gather that last read packed[p] (below);
-        // here it is at a new place: zero it there, after that gather
-        GSRT_HIP(ctx, hipMemsetAsync(cs->packed[p] + L.codes, 0, 16, cs->cstream));
-        GSRT_HIP(ctx, hipEventRecord(cs->gathered[p], cs->cstream));
-    }
-    cs->esc_at[p] = d8 ? L.codes : kNoHeader;  // an RGBA32F frame writes over the header
-    // render into packed[p] once the gather two frames back has sent it; packed[p] is this frame's own buffer, so
-    // its render kernel need not follow the previous frame's (slot streams)
-    plan.packed = true;
-    gsrt::RenderSync rsy;
-    rsy.slot = gsrt::use_slot_streams(ctx, PN > 1);
-    rsy.private_out = true;
-    rsy.wait = cs->gathered[p];
-    rsy.sharded = true;
-    rsy.tile_cost = costs ? cs->d_tcost : nullptr;
-    if (costs) {
-        cs->sc_tiles_x = plan.tiles_x;
-        cs->sc_rows = plan.tiles_y;
-        cs->sc_row0 = plan.row0();
-        cs->sc_row1 = plan.row1();
-    }
-    if (d8) {
-        rsy.dump8 = true;
-        rsy.esc = reinterpret_cast<uint4*>(cs->packed[p] + L.codes);
-        rsy.esc_cap = L.cap;
-        rsy.accum = plan.passes > 1 ? cs->d_accum[p] : nullptr;
-    }
-    gsrt_status s = gsrt::launch_render(sc, *ubo, plan, cs->packed[p], nullptr, &rsy);
-    if (s != GSRT_OK) return s;
-    GSRT_HIP(ctx, hipEventRecord(cs->rendered[p], rsy.stream));
-    // the gather on the comm stream, into gbuf[p] once the unpack two frames back has read it
-    GSRT_HIP(ctx, hipStreamWaitEvent(cs->cstream, cs->rendered[p], 0));
-    if (root && cs->unpack_pending[p]) GSRT_HIP(ctx, hipStreamWaitEvent(cs->cstream, cs->unpacked[p], 0));
-    gsrt::timing_mark(ctx, 4, cs->cstream);  // the exchange starts once this rank's share is rendered
-    float* const gb = R == 0 ? cs->gbuf[p] : nullptr;
-    ncclResult_t r = ncclGather(cs->packed[p], gb, send_floats, ncclFloat32, 0, cs->comm, cs->cstream);
-    if (r != ncclSuccess) return fail(ctx, GSRT_E_COMM, std::string("ncclGather: ") + ncclGetErrorString(r));
-    if (d8) GSRT_HIP(ctx, hipMemsetAsync(cs->packed[p] + L.codes, 0, 16, cs->cstream));  // the next render's count
-    if (emu && root)  // the other ranks' blocks landing in the gather buffer (stand-in for the receive)
-        gsrt::launch_copy_d2d(cs->cstream, gb + send_floats, cs->inbound, sizeof(float) * send_floats * (PN - 1));
-    GSRT_HIP(ctx, hipGetLastError());
-    GSRT_HIP(ctx, hipEventRecord(cs->gathered[p], cs->cstream));
-    if (root && d8) {  // the unpack of the codes into rank 0's code framebuffer (gsrt_dump8_read)
-        if (cs->codes_px < px) {
-            if (gsrt_status s0 = gsrt_comm_sync_internal(ctx); s0 != GSRT_OK) return s0;
-            (void)hipFree(cs->d_codes);
-            cs->d_codes = nullptr;
-            cs->codes_px = 0;
-            GSRT_HIP(ctx, hipMalloc(&cs->d_codes, sizeof(uint32_t) * px));
-            cs->codes_px = px;
-        }
-        gsrt::launch_unpack_dump8(cs->cstream, reinterpret_cast<const uint32_t*>(gb), cs->d_codes, plan, ubo->width,
-                                  ubo->height, per_rank, L.block);
-        GSRT_HIP(ctx, hipGetLastError());
-        GSRT_HIP(ctx, hipEventRecord(cs->unpacked[p], cs->cstream));
-        cs->unpack_pending[p] = true;
-    } else if (root) {  // the unpack, after the gather on the comm stream
-        if (cs->fb_on_render) {  // a whole frame rendered into d_fb on the render stream since the last unpack
-            GSRT_HIP(ctx, hipEventRecord(cs->ev_fb, ctx->stream));
-            GSRT_HIP(ctx, hipStreamWaitEvent(cs->cstream, cs->ev_fb, 0));
-            cs->fb_on_render = false;
-        }
-        gsrt::launch_unpack(cs->cstream, gb, ctx->d_fb, plan, ubo->width, ubo->height, per_rank);
-        GSRT_HIP(ctx, hipGetLastError());
-        GSRT_HIP(ctx, hipEventRecord(cs->unpacked[p], cs->cstream));
-        cs->unpack_pending[p] = true;
-        cs->fb_on_comm = true;
-    }
-    gsrt::timing_mark(ctx, 5, cs->cstream);
-    cs->d8_last = d8;
-    cs->d8_root = root;
-    if (d8) {
-        cs->d8_plan = plan;
-        cs->d8_layout = L;
-        cs->d8_w = ubo->width;
-        cs->d8_h = ubo->height;
-    }
-    if (profile) {
-        // every rank's row costs to every rank (max: a row has one contributor), with this rank's partition hash
-        if (cs->prof_pending[qp]) GSRT_HIP(ctx, hipEventSynchronize(cs->ev_prof[qp]));  // h_hash[qp] is free again
-        gsrt::launch_row_sum(cs->cstream, cs->d_tcost, cs->d_prof, plan.tiles_x, plan.row0(), plan.row1());
-        const uint32_t hsh = plan_hash(plan, per_rank, cs->pinned);
-        cs->h_hash[qp][0] = hsh;
-        cs->h_hash[qp][1] = ~hsh;
-        GSRT_HIP(ctx, hipMemcpyAsync(cs->d_prof + rows, cs->h_hash[qp], 2 * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                     cs->cstream));
-        r = ncclAllReduce(cs->d_prof, cs->d_prof_red, rows + 2, ncclUint32, ncclMax, cs->comm, cs->cstream);
-        if (r != ncclSuccess) return fail(ctx, GSRT_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
-        GSRT_HIP(ctx, hipMemsetAsync(cs->d_prof, 0, sizeof(uint32_t) * (rows + 2), cs->cstream));
-        GSRT_HIP(ctx, hipMemcpyAsync(cs->h_prof[qp], cs->d_prof_red, sizeof(uint32_t) * (rows + 2), hipMemcpyDeviceToHost,
-                                     cs->cstream));
-        GSRT_HIP(ctx, hipEventRecord(cs->ev_prof[qp], cs->cstream));
-        cs->prof_pending[qp] = true;
-        cs->prof_hash[qp] = hsh;
-        std::memcpy(cs->prof_key[qp], key, sizeof key);
-    }
+    GSRT_TRY(ensure_exchange_buffers(ctx, F));         // packed, gbuf, inbound, d_tcost, d_prof / d_prof_red / h_prof
+    cs->parity ^= 1u;  // the frame takes packed[p] and gbuf[p]: the next one renders while this one is exchanged
+    cs->last_p = F.p;
+    GSRT_TRY(render_share(sc, *ubo, F));               // compute streams: d_accum, esc_at[p], packed[p], rendered[p]
+    GSRT_TRY(exchange(ctx, *ubo, F));                  // comm stream: gbuf[p], gathered[p]; d_fb / d_codes, unpacked[p]
+    if (F.profile) GSRT_TRY(reduce_profile(ctx, F));   // comm stream: d_prof, d_prof_red, h_prof[qp], ev_prof[qp]
     gsrt::timing_mark(ctx, 3);  // on the compute stream: the exchange overlaps the next frame
     return GSRT_OK;
 }
@@ -832,12 +876,7 @@ static gsrt_status render_emulated(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t
         gsrt::RenderSync rsy;  // a rank's share: no cost profile
         rsy.sharded = true;
         float* blk = gather + (size_t)r * block;
-        if (d8) {
-            rsy.dump8 = true;
-            rsy.esc = reinterpret_cast<uint4*>(blk + L.codes);
-            rsy.esc_cap = L.cap;
-            rsy.accum = accum;  // the shares render one after the other on the stream
-        }
+        if (d8) sync_dump8(rsy, blk, L, accum);  // (one accum: the shares render one after the other on the stream)
         s = gsrt::launch_render(sc, *ubo, p, blk, nullptr, &rsy);
     }
     if (s == GSRT_OK) {
