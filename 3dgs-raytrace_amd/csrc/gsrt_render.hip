@@ -801,8 +801,13 @@ struct CorRay {
     // alpha > 0; some lane blended (SH evaluated); lane-candidates passing g; lane blends
     uint32_t dg_staged, dg_gpass, dg_contrib, dg_blend, dg_lanes_g, dg_lanes_blend;
     // stages shaded while some lane active; of those, stages some lane blends in; over those, the sum of the largest
-    // number of candidates one lane blends (the SH evaluations of blend_stage; dg_blend counts blend_hit's)
+    // number of candidates one lane blends (dg_blend counts blend_hit's). The SH colour kinds (shade_lanes) count
+    // passes instead: stages some lane passes g in, the passes run, and in dg_lanes_g / dg_lanes_blend the lanes of a pass
+    // and those of them that blend; dg_gpass, dg_contrib and dg_blend stay 0 there
     uint32_t dg_stages, dg_stages_blend, dg_lane_max;
+    // over the stages shaded: the candidates some lane passes g on, and the largest number of candidates one lane passes
+    // g on (both from the okg ballots after phase 1, before any stop clears a lane)
+    uint32_t dg_g_any, dg_g_lane_max;
 #endif
 };
 
@@ -818,7 +823,7 @@ __device__ GSRT_INLINE float sh_channel(const float (&bs)[16], const float (&s)[
     for (int q = 1; q < 16; ++q) a = fmaf(bs[q], s[q], a);
     return a > 0.0f ? a : 0.0f;
 }
-// the stage's LDS copy of candidate c's row. c is wave-uniform (broadcast reads) or the lane's own (blend_stage): the
+// the stage's LDS copy of candidate c's row. c is wave-uniform (broadcast reads) or the lane's own (lane_pass): the
 // stage's rows lie 192 B = 48 banks apart, so lanes reading the same 16-B piece of different rows meet four distinct
 // 4-bank groups, and a ds_read_b128 costs its 4 LDS-array cycles either way
 struct ShFromStage {
@@ -1127,7 +1132,7 @@ struct CorVariant {
     // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
     // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
     // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
-    // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before blend_stage: left at 4 it takes 102.
+    // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before the SH colours went per lane: left at 4 it takes 102.
     static constexpr uint32_t waves =
         opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
         : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
@@ -1195,88 +1200,105 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
     return term;
 }
 
-// The SH colour kinds (plain and depth frames with SH rows) shade a stage in two parts. The colour of a hit does not
-// depend on T, only the blend is ordered: weigh_hit is the ordered part of candidate c (blend_hit's tests, masks and stop
-// handling, and T), which keeps the blend's weight and reads no SH row; blend_stage then evaluates, per lane, the SH
-// colours of the candidates that lane blends. A stage so runs as many SH evaluations as its busiest lane blends
-// candidates, not one per candidate that some lane blends.
+// The SH colour kinds (plain and depth frames with SH rows) run phase 2 of a stage per lane. Slab test, exp and alpha
+// depend only on the (lane, candidate) pair, and T and the stop are ordered per lane: nothing in phase 2 crosses lanes.
+// Pass J so handles every lane's J-th g-passing candidate of the stage end to end (lane_pass), and a stage runs as many
+// passes as its busiest lane passes g on candidates, not one per candidate that some lane passes g on.
 template <class V>
 constexpr bool kShPerLane = V::sh && !V::stats && !V::shgrad && !V::opgrad;
-struct StageBlends {
-    uint64_t blend[kGroup] = {0, 0, 0, 0};  // per candidate the lanes that blend it (ballots: SGPR pairs)
-    float w[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};  // alpha T of the candidate on those lanes
-};
-template <class V>
-__device__ GSRT_INLINE uint64_t weigh_hit(uint32_t c, float alpha, uint64_t contrib, CorRay<V>& ray, StageBlends& sb) {
-    const float tn = ray.T * (1.0f - alpha);
-    const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
-    const uint64_t term = contrib & low;
-    const uint64_t blend = contrib & ~low;
-    sb.blend[c] = blend;
-    sb.w[c] = alpha * ray.T;  // the blend's own weight, read on the blending lanes only
-    ray.T = lane_of(blend) ? tn : ray.T;
-    if (term) {  // wave-uniform: a ray stops once
-        if (lane_of(term)) {
-            ray.active = false;
-            ray.pxs = __builtin_nanf("");  // see blend_hit
-        }
-    }
-    return term;
-}
-// A lane blends its candidates in ascending c, as blend_hit does, with the same weights and the same colour chain: pass
-// J blends every lane's J-th blending candidate of the stage. Which candidate that is comes from the blend ballots by
-// scalar instructions: at[J][c] = the lanes whose J-th blend is candidate c (c >= J). The lane selects its weight and
-// its row by these masks; nothing crosses lanes. Returns false when no lane has a J-th blend (so none has a later one).
-// depth: z is read again from the lane's candidate's record in the stage (one ds_read_b32 per pass); kept in registers
-// from weigh_hit, the four z spilled to scratch inside the loop, whose reloads drain the stage pipeline (vmcnt(0)).
+// Pass J of a stage. at[J][c] = the lanes whose J-th g-passing candidate is candidate c (c >= J), gone = the lanes whose
+// ray stopped in an earlier pass of this stage. The lane selects its candidate index and its g by the masks and reads its
+// candidate's record and, where it blends, SH row at its own address: the stage's records lie 64 B = 16 banks apart and
+// its rows 192 B = 48 banks, so lanes reading the same 16-B piece of different records or rows meet four distinct 4-bank
+// groups and a ds_read_b128 costs its 4 LDS-array cycles as a broadcast read does. Everything up to the masks runs for
+// the whole wave, as in shade_stage's phase 2 (the masks are ballots: wave-uniform values, formed outside divergent
+// code); a lane outside the pass reads candidate J's record and drops out of every mask.
+// The record's layout is per lane here. slab_hit_rel takes min and max of each axis pair, so on an ordered (near, far)
+// record it is ray_box_test as on a general one (gsrt_device.hpp, slab_hit_ordered: the same t and u for a ray that can
+// reach the box, a miss for any other): when every lane of the pass holds an ordered record the cheap test runs,
+// otherwise slab_hit_rel for the pass, with the same result on every lane.
+// A lane meets its candidates in ascending c, with blend_hit's tests, weights and colour chain on the same values.
+// Returns false when no lane has a J-th candidate left (so none has a later one).
 template <class V, uint32_t J>
-__device__ GSRT_INLINE bool blend_pass(const Stage* stg, const uint64_t (&at)[kGroup][kGroup], const float (&ws)[kGroup],
-                                       CorRay<V>& ray) {
+__device__ GSRT_INLINE bool lane_pass(const Stage* stg, const uint64_t (&at)[kGroup][kGroup], const float (&gv)[kGroup],
+                                      uint64_t& gone, const float* lut_s, CorRay<V>& ray) {
+    constexpr bool LUT = V::lut;
     uint64_t any = at[J][J];
     if constexpr (J + 1 < kGroup) any |= at[J][J + 1];
     if constexpr (J + 2 < kGroup) any |= at[J][J + 2];
     if constexpr (J + 3 < kGroup) any |= at[J][J + 3];
+    any &= ~gone;
     if (!any) return false;  // wave-uniform
+    uint32_t cj = J;
+    float g = gv[J];
+    if constexpr (J + 1 < kGroup) {
+        const bool here = lane_of(at[J][J + 1]);
+        cj = here ? J + 1 : cj, g = here ? gv[J + 1] : g;
+    }
+    if constexpr (J + 2 < kGroup) {
+        const bool here = lane_of(at[J][J + 2]);
+        cj = here ? J + 2 : cj, g = here ? gv[J + 2] : g;
+    }
+    if constexpr (J + 3 < kGroup) {
+        const bool here = lane_of(at[J][J + 3]);
+        cj = here ? J + 3 : cj, g = here ? gv[J + 3] : g;
+    }
+    float4 q0 = reinterpret_cast<const float4*>(&stg->rec[cj])[0];        // lo or near, depth
+    const float4 q1 = reinterpret_cast<const float4*>(&stg->rec[cj])[1];  // hi or far, +-opacity
+    asm volatile("" : "+v"(q0.w));  // one ds_read_b128, not a ds_read_b96 (shade_stage)
+    const float lo[3] = {q0.x, q0.y, q0.z}, hi[3] = {q1.x, q1.y, q1.z};
+    const uint64_t general = any & __ballot((int)__float_as_uint(q1.w) < 0);  // the opacity words' sign bits
+    const uint64_t ok = any & (general ? __ballot(slab_hit_rel(ray.R, lo, hi)) : __ballot(slab_hit_ordered(ray.R, lo, hi)));
+    // the LUT index must stay in range on every lane (g in [0, kGMax]); exp_neg_nocheck takes any g (shade_stage)
+    const float gs = LUT ? (lane_of(ok) ? g : 0.0f) : g;
+    const float e = LUT ? linear_exp(lut_s, gs) : exp_neg_nocheck(-gs);
+    const float alpha = __builtin_fminf(fabsf(q1.w) * e, 0.99f);  // v_min: never NaN where it is kept (shade_stage)
+    const uint64_t contrib = ok & __ballot(alpha > kAlphaMin);
+    const float tn = ray.T * (1.0f - alpha);
+    const uint64_t low = __ballot(tn < 1e-4f);  // one compare serves both masks
+    const uint64_t term = contrib & low;
+    const uint64_t blend = contrib & ~low;
 #ifdef GSRT_DIAG
     ray.dg_lane_max += 1u;
+    ray.dg_lanes_g += (uint32_t)__popcll(any);
+    ray.dg_lanes_blend += (uint32_t)__popcll(blend);
 #endif
-    if (lane_of(any)) {
-        uint32_t cj = J;
-        float w = ws[J];
-        if constexpr (J + 1 < kGroup) {
-            const bool here = lane_of(at[J][J + 1]);
-            cj = here ? J + 1 : cj, w = here ? ws[J + 1] : w;
+    if (blend) {  // wave-uniform: no row read when no lane of the pass blends
+        if (lane_of(blend)) {
+            float col[3];
+            ShFromStage{stg, cj}(ray.bs, col);
+            const float w = alpha * ray.T;  // the blend's own weight
+            ray.C[0] = fmaf(col[0], w, ray.C[0]);
+            ray.C[1] = fmaf(col[1], w, ray.C[1]);
+            ray.C[2] = fmaf(col[2], w, ray.C[2]);
+            if constexpr (V::depth) ray.k.D = fmaf(q0.w, w, ray.k.D);
+            ray.T = tn;
         }
-        if constexpr (J + 2 < kGroup) {
-            const bool here = lane_of(at[J][J + 2]);
-            cj = here ? J + 2 : cj, w = here ? ws[J + 2] : w;
+    }
+    if (term) {  // wave-uniform: a ray stops once, and leaves the stage's later passes
+        if (lane_of(term)) {
+            ray.active = false;
+            ray.pxs = __builtin_nanf("");  // see blend_hit
         }
-        if constexpr (J + 3 < kGroup) {
-            const bool here = lane_of(at[J][J + 3]);
-            cj = here ? J + 3 : cj, w = here ? ws[J + 3] : w;
-        }
-        float col[3];
-        ShFromStage{stg, cj}(ray.bs, col);
-        ray.C[0] = fmaf(col[0], w, ray.C[0]);
-        ray.C[1] = fmaf(col[1], w, ray.C[1]);
-        ray.C[2] = fmaf(col[2], w, ray.C[2]);
-        if constexpr (V::depth) ray.k.D = fmaf(stg->rec[cj].depth, w, ray.k.D);
+        gone |= term;
     }
     return true;
 }
+// okg[c]: the lanes that pass g on candidate c (phase 1), gv[c] their g
 template <class V>
-__device__ GSRT_INLINE void blend_stage(const Stage* stg, const StageBlends& sb, CorRay<V>& ray) {
-    static_assert(kGroup == 4, "two bit planes count a lane's earlier blends; blend_pass selects among four");
-    if (!(sb.blend[0] | sb.blend[1] | sb.blend[2] | sb.blend[3])) return;  // wave-uniform: no lane blends in this stage
+__device__ GSRT_INLINE void shade_lanes(const Stage* stg, const uint64_t (&okg)[kGroup], const float (&gv)[kGroup],
+                                        const float* lut_s, CorRay<V>& ray) {
+    static_assert(kGroup == 4, "two bit planes count a lane's earlier candidates; lane_pass selects among four");
+    if (!(okg[0] | okg[1] | okg[2] | okg[3])) return;  // wave-uniform: no lane passes g in this stage
 #ifdef GSRT_DIAG
-    ray.dg_stages_blend += 1u;
+    ray.dg_stages_blend += 1u;  // here: stages some lane passes g in
 #endif
-    // the lanes' counts of earlier blends as two bit planes (p1 p0), candidate by candidate
+    // the lanes' counts of earlier g-passing candidates as two bit planes (p1 p0), candidate by candidate
     uint64_t at[kGroup][kGroup];
     uint64_t p0 = 0, p1 = 0;
 #pragma unroll
     for (uint32_t c = 0; c < kGroup; ++c) {
-        const uint64_t b = sb.blend[c];
+        const uint64_t b = okg[c];
         at[0][c] = b & ~p0 & ~p1;
         at[1][c] = b & p0 & ~p1;
         at[2][c] = b & ~p0 & p1;
@@ -1285,14 +1307,11 @@ __device__ GSRT_INLINE void blend_stage(const Stage* stg, const StageBlends& sb,
         p0 ^= b;
         p1 ^= carry;
     }
-    // the weights as register values before they are selected: selects between loads of sb.w would be folded into one
-    // load at a selected address, which keeps the whole of sb in scratch memory
-    float ws[kGroup] = {sb.w[0], sb.w[1], sb.w[2], sb.w[3]};
-    asm volatile("" : "+v"(ws[0]), "+v"(ws[1]), "+v"(ws[2]), "+v"(ws[3]));
-    if (!blend_pass<V, 0>(stg, at, ws, ray)) return;
-    if (!blend_pass<V, 1>(stg, at, ws, ray)) return;
-    if (!blend_pass<V, 2>(stg, at, ws, ray)) return;
-    blend_pass<V, 3>(stg, at, ws, ray);
+    uint64_t gone = 0;
+    if (!lane_pass<V, 0>(stg, at, gv, gone, lut_s, ray)) return;
+    if (!lane_pass<V, 1>(stg, at, gv, gone, lut_s, ray)) return;
+    if (!lane_pass<V, 2>(stg, at, gv, gone, lut_s, ray)) return;
+    lane_pass<V, 3>(stg, at, gv, gone, lut_s, ray);
 }
 
 // Shade candidates 0..m of one stage (sorted front to back) for every lane's ray. FULL: m == kGroup is known at
@@ -1324,10 +1343,18 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
 #ifdef GSRT_DIAG
         ray.dg_staged += __ballot(ray.active) ? m : 0u;
         ray.dg_stages += __ballot(ray.active) ? 1u : 0u;
+        if (__ballot(ray.active)) {
+            const uint64_t two = (okg[0] & okg[1]) | (okg[2] & okg[3]) | ((okg[0] | okg[1]) & (okg[2] | okg[3]));
+            const uint64_t three = (okg[0] & okg[1] & (okg[2] | okg[3])) | (okg[2] & okg[3] & (okg[0] | okg[1]));
+            ray.dg_g_any += (okg[0] ? 1u : 0u) + (okg[1] ? 1u : 0u) + (okg[2] ? 1u : 0u) + (okg[3] ? 1u : 0u);
+            ray.dg_g_lane_max += (okg[0] & okg[1] & okg[2] & okg[3]) ? 4u : three ? 3u : two ? 2u
+                                 : (okg[0] | okg[1] | okg[2] | okg[3]) ? 1u : 0u;
+        }
 #endif
-        // Phase 2, front to back over the candidates some lane passed: slab test, exp, alpha, blend (the SH colour
-        // kinds: alpha, weight and T here, the stage's blends after the loop, blend_stage)
-        [[maybe_unused]] StageBlends sb;
+        // Phase 2. The SH colour kinds: per lane, in passes (shade_lanes). The others, front to back over the candidates
+        // some lane passed: slab test, exp, alpha, blend
+        if constexpr (kShPerLane<V>) shade_lanes<V>(stg, okg, gv, lut_s, ray);
+        else
 #pragma unroll
         for (uint32_t c = 0; c < kGroup; ++c) {
             if (!okg[c]) continue;
@@ -1359,15 +1386,12 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
 #endif
             grad.candidate(e, fabsf(q1.w));  // what a hit's term may need besides the blend's own values
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
-            uint64_t stopped;
-            if constexpr (kShPerLane<V>) stopped = weigh_hit<V>(c, alpha, contrib, ray, sb);
-            else stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad);
+            const uint64_t stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad);
             if (stopped) {
 #pragma unroll
                 for (uint32_t c1 = c + 1; c1 < kGroup; ++c1) okg[c1] &= ~stopped;
             }
         }
-        if constexpr (kShPerLane<V>) blend_stage<V>(stg, sb, ray);
         if (grad.mask) grad.flush();  // wave-uniform: a stage no lane blended adds nothing
     } else {
         for (uint32_t c = 0; c < m; ++c) {
@@ -2019,6 +2043,7 @@ __device__ GSRT_INLINE CorRay<V> cor_ray(const CorTile::Pixel& p, uint32_t S, ui
 #ifdef GSRT_DIAG
     ray.dg_staged = ray.dg_gpass = ray.dg_contrib = ray.dg_blend = ray.dg_lanes_g = ray.dg_lanes_blend = 0;
     ray.dg_stages = ray.dg_stages_blend = ray.dg_lane_max = 0;
+    ray.dg_g_any = ray.dg_g_lane_max = 0;
 #endif
     return ray;
 }
@@ -2249,6 +2274,8 @@ void k_render_cor(const KArgs karg) {
             for (int q = 0; q < 6; ++q) atomicAdd(kargs().a.counters + 16 + q, (unsigned long long)dg[q]);
             const uint32_t ds[3] = {ray.dg_stages, ray.dg_stages_blend, ray.dg_lane_max};
             for (int q = 0; q < 3; ++q) atomicAdd(kargs().a.counters + 25 + q, (unsigned long long)ds[q]);
+            atomicAdd(kargs().a.counters + 30, (unsigned long long)ray.dg_g_any);
+            atomicAdd(kargs().a.counters + 31, (unsigned long long)ray.dg_g_lane_max);
         }
 #endif
     }

@@ -39,12 +39,18 @@ print(f"{cfg}: k_group_list tile filter split: per-lane tile tests (incl. the ch
 print(f"{cfg}: wave-cycles from entry: tile+ray setup {int(cnt[1]) / tot:.3f}, reduction+store tail {int(cnt[2]) / tot:.3f}")
 waves = W * H * spp / 64
 st, gp, co, bl, lg, lb = (int(x) for x in cnt[16:22])
-print(f"{cfg}: per wave: staged candidates {st / waves:.1f}, some lane passes g {gp / waves:.1f}, some lane alpha > 0 "
-      f"{co / waves:.1f}, some lane blends (SH) {bl / waves:.1f}; lanes per g-survivor {lg / max(gp, 1):.1f}, "
-      f"lanes per blending candidate {lb / max(bl, 1):.1f}")
-# SH colour frames only (blend_stage): stages shaded, stages some lane blends in, and over those the sum of the largest
-# number of candidates one lane blends. E = candidates some lane blends, E' = SH evaluations run, per stage
 ns, nb, lm = (int(x) for x in cnt[25:28])
-if nb:
-    print(f"{cfg}: stages shaded {ns} ({ns / waves:.2f} per wave), with a blend {nb}; per shaded stage E {bl / ns:.3f} "
-          f"E' {lm / ns:.3f}; per stage with a blend E {bl / nb:.3f} E' {lm / nb:.3f}; E'/E {lm / max(bl, 1):.3f}")
+if gp:  # the kinds whose phase 2 runs per candidate (blend_hit)
+    print(f"{cfg}: per wave: staged candidates {st / waves:.1f}, some lane passes g {gp / waves:.1f}, some lane alpha > 0 "
+          f"{co / waves:.1f}, some lane blends {bl / waves:.1f}; lanes per g-survivor {lg / max(gp, 1):.1f}, "
+          f"lanes per blending candidate {lb / max(bl, 1):.1f}")
+elif lm:  # SH colour frames (shade_lanes): phase 2 runs per lane, in passes
+    print(f"{cfg}: per wave: staged candidates {st / waves:.1f}, passes run {lm / waves:.1f}; lanes per pass {lg / lm:.1f}, "
+          f"blending lanes per pass {lb / lm:.1f}")
+    print(f"{cfg}: stages shaded {ns} ({ns / waves:.2f} per wave), with a lane passing g {nb}; passes per shaded stage "
+          f"{lm / ns:.3f}")
+# every kind, from the okg ballots after phase 1: E_g = candidates some lane passes g on, E'_g = the most any one lane
+# passes g on (the passes of shade_lanes, less the passes a stop empties)
+eg, egl = int(cnt[30]), int(cnt[31])
+if ns and eg:
+    print(f"{cfg}: per shaded stage E_g {eg / ns:.3f} E'_g {egl / ns:.3f}; E'_g/E_g {egl / eg:.3f}")
