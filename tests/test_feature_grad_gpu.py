@@ -4,6 +4,10 @@ table, grad[g, c] = sum over the hits i of Gaussian g of w_i G[p, c] / ns.
 The reference of every numeric check is the forward feature kernel, which tests/test_features_gpu.py ties to the oracle:
 a feature frame of a one-hot table (16 Gaussians a frame, one per channel) gives W_g[p], Gaussian g's weight in pixel p,
 exactly at 1 spp (a chain fma(1, w, F) keeps w), and grad_ref[g, c] = sum_p W_g[p] G[p, c] in float64.
+
+The check that is independent of the forward kernel is tests/test_grad_f64_gpu.py (the float64 backward of
+tests/cor_f64.py, on a scene where both clamps fire behind other hits); the references here cover what that one
+cannot: float32 rounding bounds per entry, GSRT_FLAG_LUT frames and the API.
 """
 import ctypes
 

@@ -20,6 +20,10 @@ most N + O(1) roundings, and the reference's T_i differs from the kernel's by at
 N_max the largest hit count of a ray in the frame. The wave's reduction (six adds) and the atomics' order add roundings
 relative to the terms themselves, which are smaller than these magnitudes; each test prints its worst error / bound.
 
+The check that is independent of the forward kernel is tests/test_grad_f64_gpu.py (the float64 backward of
+tests/cor_f64.py, on a scene where both clamps fire behind other hits); the references here cover what that one
+cannot: float32 rounding bounds per entry, GSRT_FLAG_LUT frames and the API.
+
 Every frame here is at most 64x48 pixels.
 """
 import ctypes

@@ -10,6 +10,10 @@ The reference of every numeric check is built from forward kernels that existing
     s_0 = +1 never clamps (a >= 0.78 - 0.225) and s_0 = -4 always does (a <= 0.5 - 1.128 + 0.225).
 ref[g, q, ch] = sum_{p,s} W B M G / ns in float64, bound (N_g + 8) 2^-23 sum W |B| |G| / ns + 4 2^-23 sum W |G| / ns.
 
+The check that is independent of the forward kernel is tests/test_grad_f64_gpu.py (the float64 backward of
+tests/cor_f64.py, on a scene where both clamps fire behind other hits); the references here cover what that one
+cannot: float32 rounding bounds per entry, GSRT_FLAG_LUT frames and the API.
+
 Every frame here is at most 64x48 pixels.
 """
 import ctypes
