@@ -21,7 +21,8 @@
 // --feature-grad FILE --feature-channels C --feature-grad-out FILE (gsrt_render_feature_grad: W*H*C in, n*C out),
 // --sh-grad FILE --sh-grad-out FILE (gsrt_render_sh_grad, a scene with SH rows: the RGBA frame's gradient W*H*4 in, n*48
 // laid out [gauss][coef][rgb] out), --opacity-grad FILE --opacity-grad-out FILE (gsrt_render_opacity_grad: W*H*4 in, n
-// out). Their usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, a gradient run listed before
+// out), --splat-grad FILE --splat-grad-out FILE (gsrt_render_splat_grad: W*H*4 in, n*8 out; the library refuses --lut).
+// Their usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, a gradient run listed before
 // it, one option without the others, C outside 1..16.
 #include <chrono>
 #include <cstdio>
@@ -46,7 +47,7 @@ struct Options {
     int device = 0;
     float fov = 0.0f;  // 0: scene default
     std::string camera, out, binary, text, ply, depth, features, features_out, feature_grad, feature_grad_out;
-    std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out;
+    std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out, splat_grad, splat_grad_out;
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
 };
@@ -73,6 +74,10 @@ const GradOption kGradOptions[] = {
      [](gsrt_scene* s, const gsrt_ubo* u, uint32_t m, const float* g, uint32_t, float* t) {
          return gsrt_render_opacity_grad(s, u, m, 0, g, t, 0);
      }},
+    {"--splat-grad", &Options::splat_grad, &Options::splat_grad_out, 4, 8,
+     [](gsrt_scene* s, const gsrt_ubo* u, uint32_t m, const float* g, uint32_t, float* t) {
+         return gsrt_render_splat_grad(s, u, m, 0, g, t, 0);
+     }},
 };
 bool given(const Options& o, const GradOption& g) { return !(o.*g.in).empty() || !(o.*g.out).empty(); }
 
@@ -86,7 +91,8 @@ bool given(const Options& o, const GradOption& g) { return !(o.*g.in).empty() ||
                  "                   [--depth PFM] [--features FILE --feature-channels C --features-out FILE]\n"
                  "                   [--feature-grad FILE --feature-channels C --feature-grad-out FILE]\n"
                  "                   [--sh-grad FILE --sh-grad-out FILE]\n"
-                 "                   [--opacity-grad FILE --opacity-grad-out FILE]\n");
+                 "                   [--opacity-grad FILE --opacity-grad-out FILE]\n"
+                 "                   [--splat-grad FILE --splat-grad-out FILE]\n");
     std::exit(2);
 }
 
@@ -136,6 +142,8 @@ Options parse(int argc, char** argv) {
         else if (a == "--sh-grad-out") o.sh_grad_out = val();
         else if (a == "--opacity-grad") o.opacity_grad = val();
         else if (a == "--opacity-grad-out") o.opacity_grad_out = val();
+        else if (a == "--splat-grad") o.splat_grad = val();
+        else if (a == "--splat-grad-out") o.splat_grad_out = val();
         else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());

@@ -988,7 +988,7 @@ const float* gsrt_feature_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_feat ?
 // Gradient frames, each kind by its row F of kFrameFlags. With ctx rows (feature: n x 16 floats, 64-B rows; sh: n x 48,
 // 192-B rows in the SH rows' own [rgb][coef] layout: the shapes the render kernel's atomics take) the frame zeroes them, the
 // render kernel adds every blended hit's terms to them and a small kernel compacts them into the caller's table (sh:
-// transposed into [gauss][coef][rgb]). Without (opacity: n floats in API order) the render kernel adds to the caller's
+// transposed into [gauss][coef][rgb]). Without (opacity: n floats in API order; splat: n rows of 8) the render kernel adds to the caller's
 // device table itself, zeroed first unless it accumulates, and nothing is compacted. All in order on the render stream: the
 // kinds share the ctx's buffers.
 static gsrt_status check_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const gsrt::FrameFlag& F,
@@ -1085,6 +1085,71 @@ gsrt_status gsrt_render_opacity_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, 
 gsrt_status gsrt_render_opacity_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                      const float* grad_image, float* grad_table, int accumulate) {
     return grad_frame_blocking(sc, ubo, mode, k, GradKind::opacity, grad_image, 0, grad_table, accumulate);
+}
+gsrt_status gsrt_render_splat_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                         const float* d_grad_image, float* d_grad_splat, int accumulate) {
+    return grad_frame_async(sc, ubo, mode, k, GradKind::splat, d_grad_image, 0, d_grad_splat, accumulate);
+}
+gsrt_status gsrt_render_splat_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, const float* grad_image,
+                                   float* grad_splat, int accumulate) {
+    return grad_frame_blocking(sc, ubo, mode, k, GradKind::splat, grad_image, 0, grad_splat, accumulate);
+}
+
+// The projection's backward (k_splat_grad_to_model) on the render stream, behind the splat gradient frame that wrote the
+// rows. It reads the scene's current parameter array there as a REF frame's projection does: after the update copies
+// the stream has not seen, and an update that retires the array waits for it (serial_pending, serial_reads).
+static gsrt_status check_model_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, const float* rows, const float* gc,
+                                         const float* gv) {
+    if (!sc || !ubo) return GSRT_E_ARG;
+    const char* name = "gsrt_splat_grad_to_model: ";
+    if (!rows) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_splat is NULL");
+    if (!gc) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_center is NULL");
+    if (!gv) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_cov is NULL");
+    if (sc->ntri) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "not for a scene with a triangle mesh");
+    if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, std::string(name) + "before gsrt_build_bvh");
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_splat_grad_to_model_async(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_grad_splat,
+                                           float* d_grad_center, float* d_grad_cov, int accumulate) {
+    gsrt_status s = check_model_grad_args(sc, ubo, d_grad_splat, d_grad_center, d_grad_cov);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (!sc->n) return GSRT_OK;
+    if ((s = gsrt::wait_updates(ctx, ctx->stream)) != GSRT_OK) return s;
+    ctx->serial_pending = true;
+    ctx->serial_reads = true;
+    gsrt::launch_splat_grad_to_model(ctx->stream, sc->n, *ubo, sc->d_params, d_grad_splat, d_grad_center, d_grad_cov,
+                                     accumulate != 0);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_splat_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
+                                     float* grad_cov, int accumulate) {
+    gsrt_status s = check_model_grad_args(sc, ubo, grad_splat, grad_center, grad_cov);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const bool in_dev = is_device_ptr(grad_splat), c_dev = is_device_ptr(grad_center), v_dev = is_device_ptr(grad_cov);
+    if (accumulate && (!c_dev || !v_dev))
+        return fail(ctx, GSRT_E_ARG, "gsrt_splat_grad_to_model: accumulate needs device tables");
+    // the host tables' device copies: one block, rows | centres | covariances
+    const size_t n = sc->n, nn = n ? n : 1;
+    float* tmp = nullptr;
+    if (!in_dev || !c_dev || !v_dev) GSRT_HIP(ctx, hipMalloc(&tmp, sizeof(float) * 17 * nn));
+    void* tmpv = tmp;
+    float* const d_rows = tmp, * const d_c = tmp + 8 * nn, * const d_v = tmp + 11 * nn;
+    if (!in_dev && n && hipMemcpyAsync(d_rows, grad_splat, sizeof(float) * 8 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        s = fail(ctx, GSRT_E_DEVICE, "splat gradient upload failed");
+    if (s == GSRT_OK)
+        s = gsrt_splat_grad_to_model_async(sc, ubo, in_dev ? grad_splat : d_rows, c_dev ? grad_center : d_c,
+                                           v_dev ? grad_cov : d_v, accumulate);
+    return finish_blocking(ctx, s, {{!c_dev && n ? grad_center : nullptr, d_c, sizeof(float) * 3 * n,
+                                     "centre gradient download failed"},
+                                    {!v_dev && n ? grad_cov : nullptr, d_v, sizeof(float) * 6 * n,
+                                     "covariance gradient download failed"}}, &tmpv);
 }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,

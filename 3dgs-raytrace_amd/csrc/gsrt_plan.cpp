@@ -221,8 +221,8 @@ void deal_units(const double* cost, const uint32_t* centre, uint32_t R, uint32_t
 }
 
 // The refusals of a whole frame. Each flag of kFrameFlags in the mode is checked on its own, the gradient flags first and
-// newest first, then the two second outputs oldest first: its entry point, COR, not the counting pass, not dump codes, none
-// of the flags before it in the table, and for a gradient frame no mesh. The first refusal wins; then the checks every frame
+// newest first, then the two second outputs oldest first: its entry point, COR, not the counting pass, not dump codes, not
+// the LUT where its row says so, none of the flags before it in the table, and for a gradient frame no mesh. The first refusal wins; then the checks every frame
 // gets.
 Refusal frame_refusal(uint32_t mode, GradKind caller, uint32_t samples, const SceneFacts& sc) {
     constexpr int N = (int)(sizeof kFrameFlags / sizeof kFrameFlags[0]);
@@ -235,6 +235,7 @@ Refusal frame_refusal(uint32_t mode, GradKind caller, uint32_t samples, const Sc
         if (low != GSRT_MODE_COR) return name + "COR frames only";
         if (mode & GSRT_FLAG_STATS) return name + "not with GSRT_FLAG_STATS";
         if (mode & GSRT_FLAG_OUT_DUMP8) return name + "not with GSRT_FLAG_OUT_DUMP8";
+        if (F.no_lut && (mode & GSRT_FLAG_LUT)) return name + "not with GSRT_FLAG_LUT";
         for (int j = 0; j < i; ++j)
             if (mode & kFrameFlags[j].bit) return name + "not with " + kFrameFlags[j].name;
         return grad && sc.ntri ? name + "not for a scene with a triangle mesh" : "";
@@ -257,9 +258,9 @@ Refusal frame_refusal(uint32_t mode, GradKind caller, uint32_t samples, const Sc
 
 }  // namespace gsrt
 
-extern "C" gsrt_status gsrt_debug_frame_refusal(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
-                                                int has_features, int has_sh, char* msg, size_t cap) {
-    if (caller > (uint32_t)gsrt::GradKind::opacity) return GSRT_E_ARG;
+extern "C" gsrt_status gsrt_debug_frame_refusal_kind(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built,
+                                                     uint32_t ntri, int has_features, int has_sh, char* msg, size_t cap) {
+    if (caller > (uint32_t)gsrt::GradKind::splat) return GSRT_E_ARG;
     const gsrt::Refusal r = gsrt::frame_refusal(mode, (gsrt::GradKind)caller, samples,
                                                 {bvh_built != 0, ntri, has_features != 0, has_sh != 0});
     if (msg && cap) {
@@ -268,6 +269,13 @@ extern "C" gsrt_status gsrt_debug_frame_refusal(uint32_t mode, uint32_t caller, 
         msg[len] = '\0';
     }
     return r.status;
+}
+
+// the hook as it was before the callers past gsrt_render_opacity_grad: those it refuses
+extern "C" gsrt_status gsrt_debug_frame_refusal(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
+                                                int has_features, int has_sh, char* msg, size_t cap) {
+    if (caller > (uint32_t)gsrt::GradKind::opacity) return GSRT_E_ARG;
+    return gsrt_debug_frame_refusal_kind(mode, caller, samples, bvh_built, ntri, has_features, has_sh, msg, cap);
 }
 
 extern "C" gsrt_status gsrt_deal_units(const double* cost, const uint32_t* centre, uint32_t units, uint32_t* perm) {

@@ -70,6 +70,9 @@ constexpr bool kGroupRegSort = GSRT_GROUP_REGSORT != 0;
 #ifndef GSRT_OPGRAD_WAVES
 #define GSRT_OPGRAD_WAVES 4
 #endif
+#ifndef GSRT_SPLATGRAD_WAVES
+#define GSRT_SPLATGRAD_WAVES 3
+#endif
 constexpr uint32_t kFront = 128;   // frontier entries per super-group
 
 
@@ -131,6 +134,8 @@ struct RenderArgs {
     // per Gaussian id, [rgb][coef] as the SH rows are (compacted by launch_sh_grad_compact)
     // An opacity gradient frame (GSRT_FLAG_OPACITY_GRAD, k_render_cor opgrad) likewise: grad_in is the upstream gradient of
     // the RGBA frame, all four channels read, and grad_rows the caller's own table, one float per Gaussian id
+    // A splat gradient frame (GSRT_FLAG_SPLAT_GRAD, k_render_cor splatgrad) likewise: grad_in as for opacity, grad_rows the
+    // caller's own table, one 32-B row of 8 floats per Gaussian id
     const float* grad_in;
     float* grad_rows;
     uint32_t grad_channels;
@@ -915,7 +920,7 @@ __device__ GSRT_INLINE float over_samples(float x, uint32_t ns) {
 //   Payload, load: the lane's upstream gradient in the ray (CorRay::k) and how it is read;
 //   share(ids + g0): one stage's share of the round, a Share: the stage's candidate ids (in the round's list in LDS), the
 //     mask of the candidates some lane blended (bit c, wave-uniform) and the kind's sums. shade_stage tells it each
-//     candidate's exponential and |opacity| before the hit (candidate), blend_hit calls hit for the wave where some lane
+//     candidate's exponential, |opacity| and staged record before the hit (candidate), blend_hit calls hit for the wave where some lane
 //     blends candidate c (T still the hit's T_i, col its colour) and hit_lane on the blending lanes once the colour is
 //     accumulated, and shade_stage ends with flush where mask is set: the stage's terms, summed over the wave, to the table.
 // The lane's upstream gradient of a colour frame: the first N floats of pixel (x, y) of grad_in, an RGBA image, scaled
@@ -943,7 +948,7 @@ struct NoGrad {
     template <class P> __device__ GSRT_INLINE static void load(P&, uint32_t, uint32_t, bool, uint32_t) {}
     struct Share {
         static constexpr uint32_t mask = 0;  // never a flush
-        __device__ GSRT_INLINE void candidate(float, float) {}
+        __device__ GSRT_INLINE void candidate(float, float, const SplatRec*) {}
         template <class Ray> __device__ GSRT_INLINE void hit(uint32_t, uint64_t, float, const float (&)[3], const Ray&) {}
         template <class Ray> __device__ GSRT_INLINE void hit_lane(uint32_t, float, const float (&)[3], const Ray&) {}
         __device__ GSRT_INLINE void flush() const {}
@@ -974,7 +979,7 @@ struct FeatureGrad {
         uint32_t channels;  // channels from here on (G holds +0 there) are left out
         float sums[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
         uint32_t mask = 0;
-        __device__ GSRT_INLINE void candidate(float, float) {}
+        __device__ GSRT_INLINE void candidate(float, float, const SplatRec*) {}
         template <class Ray>
         __device__ GSRT_INLINE void hit(uint32_t c, uint64_t blend, float alpha, const float (&)[3], const Ray& ray) {
             const float w = alpha * ray.T;  // the blend's own weight
@@ -1023,7 +1028,7 @@ struct ShGrad {
         float sums[3][kGroup] = {};
         uint32_t mask = 0;
         struct Rgb { float v[3]; };
-        __device__ GSRT_INLINE void candidate(float, float) {}
+        __device__ GSRT_INLINE void candidate(float, float, const SplatRec*) {}
         template <class Ray>
         __device__ GSRT_INLINE void hit(uint32_t c, uint64_t blend, float alpha, const float (&col)[3], const Ray& ray) {
             const float w = alpha * ray.T;  // the blend's own weight
@@ -1079,7 +1084,7 @@ struct OpacityGrad {
         float t[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
         uint32_t mask = 0;
         float e = 0.0f; bool open = false;
-        __device__ GSRT_INLINE void candidate(float e_, float o) { e = e_, open = o * e_ < 0.99f; }
+        __device__ GSRT_INLINE void candidate(float e_, float o, const SplatRec*) { e = e_, open = o * e_ < 0.99f; }
         template <class Ray>
         __device__ GSRT_INLINE void hit(uint32_t c, uint64_t, float, const float (&)[3], const Ray&) { mask |= 1u << c; }
         template <class Ray>
@@ -1098,15 +1103,79 @@ struct OpacityGrad {
     __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows}; }
 };
 
+// splatgrad (GSRT_FLAG_SPLAT_GRAD): the backward of a plain colour frame to each Gaussian's screen-space splat: the pixel
+// centre (ppx, ppy) and the conic (A, B, C) of g = (A dx^2 + 2 B dx dy + C dy^2) / 2, with or without SH rows; the plain
+// frame's RGBA. Payload and sweeps are opgrad's: the second sweep forms the same d = d(frame . G) / d(alpha) per blended
+// hit. Where the clamp let |o| e through, d(alpha) / dg = -alpha, so q = -alpha d weighs dg / d(ppx, ppy, A, B, C); the
+// lane reads the candidate's centre and conic again from its staged record (words 8..12; the record stores A / 2 and
+// C / 2, exact halves) and forms dx, dy as phase 1 of shade_stage formed them. Slot 5 is opgrad's own term d e. Selects:
+// the lanes that do not blend c and the clamped hits keep the share's +0. The flush pads a candidate's six sums to eight
+// and sums them over the wave as grad's sixteen channels are: candidates 0, 1 and 2, 3 through grad_row_sums, the rows
+// through grad_stage_sums, which leaves candidate c's slot q on lane 8 c + q; one atomic wave-instruction, 24 lanes add.
+struct SplatGrad {
+    float* rows;
+    __device__ GSRT_INLINE static SplatGrad of_frame() { return {kargs().a.grad_rows}; }
+    using Payload = OpacityGrad::Payload;
+    __device__ GSRT_INLINE static void load(Payload& g, uint32_t x, uint32_t y, bool valid, uint32_t ns) {
+        OpacityGrad::load(g, x, y, valid, ns);
+    }
+    static constexpr uint32_t kSlots = 6;  // of a row's 8 floats, the ones a frame adds to
+    struct Share {
+        const uint32_t* ids;
+        float* rows;
+        float t[kGroup][kSlots] = {};
+        uint32_t mask = 0;
+        float e = 0.0f; bool open = false;
+        const SplatRec* rec = nullptr;
+        __device__ GSRT_INLINE void candidate(float e_, float o, const SplatRec* r) { e = e_, open = o * e_ < 0.99f, rec = r; }
+        template <class Ray>
+        __device__ GSRT_INLINE void hit(uint32_t c, uint64_t, float, const float (&)[3], const Ray&) { mask |= 1u << c; }
+        template <class Ray>
+        __device__ GSRT_INLINE void hit_lane(uint32_t c, float alpha, const float (&col)[3], const Ray& ray) {
+            const float r = 1.0f / (1.0f - alpha);  // alpha <= 0.99
+            float d = (ray.k.G[3] * ray.k.fin[3]) * r;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) d = d + ray.k.G[ch] * (ray.T * col[ch] - (ray.k.fin[ch] - ray.C[ch]) * r);
+            const float4 q2 = reinterpret_cast<const float4*>(rec)[2];  // ppx, ppy, A/2, B
+            const float4 q3 = reinterpret_cast<const float4*>(rec)[3];  // C/2, ...
+            const float dx = ray.pxs - q2.x, dy = ray.pys - q2.y;       // the blending lanes' rays are live: no NaN
+            const float A = 2.0f * q2.z, B = q2.w, C = 2.0f * q3.x;
+            const float q = -(alpha * d);
+            t[c][0] = open ? q * -(A * dx + B * dy) : 0.0f;
+            t[c][1] = open ? q * -(B * dx + C * dy) : 0.0f;
+            t[c][2] = open ? q * (0.5f * (dx * dx)) : 0.0f;
+            t[c][3] = open ? q * (dx * dy) : 0.0f;
+            t[c][4] = open ? q * (0.5f * (dy * dy)) : 0.0f;
+            t[c][5] = open ? d * e : 0.0f;
+        }
+        __device__ GSRT_INLINE void flush() const {
+            static_assert(kGroup == 4 && kSlots <= 8, "two candidates of eight slots per grad_row_sums");
+            flush_share<8>(ids, mask, [&] {
+                float lo[16], hi[16];
+#pragma unroll
+                for (uint32_t q = 0; q < 8; ++q) {
+                    lo[q] = q < kSlots ? t[0][q] : 0.0f, lo[8 + q] = q < kSlots ? t[1][q] : 0.0f;
+                    hi[q] = q < kSlots ? t[2][q] : 0.0f, hi[8 + q] = q < kSlots ? t[3][q] : 0.0f;
+                }
+                const float gs[kGroup] = {grad_row_sums(lo), grad_row_sums(hi), 0.0f, 0.0f};
+                return grad_stage_sums(gs);  // lanes 0..15: candidates 0, 1; lanes 16..31: candidates 2, 3
+            }, [&](uint32_t id, uint32_t q, float sum) {
+                if (q < kSlots) atomicAdd(rows + (size_t)id * 8u + q, sum);  // no-return global_atomic_add_f32
+            });
+        }
+    };
+    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows}; }
+};
+
 // ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
 // with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
 // or a gradient frame of the kind RenderSync::grad_kind names (the sinks above). SH: the scene's SH-3 rows are blended;
-// LUT: the ExpLUT instead of the exact exponential. Twenty-two kernels: {plain, stats, depth, opgrad} x SH x LUT and
-// {feat, grad, shgrad} x LUT, named by cor_kernel and nowhere else. What a forward kind adds sits under if constexpr on
+// LUT: the ExpLUT instead of the exact exponential. Twenty-four kernels: {plain, stats, depth, opgrad} x SH x LUT,
+// {feat, grad, shgrad} x LUT and splatgrad x SH (never with the LUT, frame_refusal), named by cor_kernel and nowhere else. What a forward kind adds sits under if constexpr on
 // these members, what a gradient kind adds in its sink: the other kinds' code does not change. The RGBA of feat and
 // grad is the no-SH frame's.
 // A new gradient kind supplies: a CorKind, its sink and line in Grad, a line in `waves`, a case in cor_kernel, launch_cor.
-enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad };
+enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad, splatgrad };
 // waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
 // spill to scratch)
 constexpr uint32_t kFeatWaves = 4;
@@ -1118,6 +1187,9 @@ constexpr uint32_t kShGradWaves = GSRT_SHGRAD_WAVES;
 // and for the four opgrad kernels, likewise (GSRT_OPGRAD_WAVES): 127 VGPRs with SH rows and 94 / 95
 // without, no scratch at 4; at 5 both SH kernels spill (63 and 66 VGPRs to scratch), at 6 two kernels do
 constexpr uint32_t kOpGradWaves = GSRT_OPGRAD_WAVES;
+// and for the two splatgrad kernels, likewise (GSRT_SPLATGRAD_WAVES): a stage's 24 terms per lane
+// beside opgrad's registers, 155 VGPRs with SH rows and 103 without, no scratch at 3; at 4 the SH kernel spills 24 VGPRs
+constexpr uint32_t kSplatGradWaves = GSRT_SPLATGRAD_WAVES;
 struct NoPayload {};
 struct DepthPayload { float D; };      // sum of z w over the blended hits (expected view depth, premultiplied)
 struct ChannelPayload { float F[16]; };  // feat: sum of f_k w over the blended hits per channel
@@ -1126,7 +1198,9 @@ struct CorVariant {
     static constexpr bool sh = SH, lut = LUT;
     static constexpr bool stats = K == CorKind::stats, depth = K == CorKind::depth;
     static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad, shgrad = K == CorKind::shgrad;
-    static constexpr bool opgrad = K == CorKind::opgrad;
+    static constexpr bool opgrad = K == CorKind::opgrad, splatgrad = K == CorKind::splatgrad;
+    static constexpr bool resweep = opgrad || splatgrad;  // every pass is shaded twice: finals, then the sink's terms
+    static_assert(!splatgrad || !LUT, "under the LUT d(alpha) / dg is a segment's slope, not -alpha");
     static_assert(!(feat || grad) || !SH, "feature and gradient frames evaluate no SH");
     static_assert(!shgrad || SH, "an SH gradient frame blends the SH rows");
     // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
@@ -1134,7 +1208,7 @@ struct CorVariant {
     // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
     // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before the SH colours went per lane: left at 4 it takes 102.
     static constexpr uint32_t waves =
-        opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
+        splatgrad ? kSplatGradWaves : opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
         : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
     // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
     // stage, and DMA instructions per stage (one piece per lane each)
@@ -1144,7 +1218,8 @@ struct CorVariant {
     // a gradient kind's sink; what a forward kind adds to a pixel's sums (PixelSums), empty where it adds nothing; and
     // what the kind adds to a ray's state (CorRay): those sums, or its sink's payload
     using Grad = std::conditional_t<grad, FeatureGrad, std::conditional_t<shgrad, ShGrad,
-                                    std::conditional_t<opgrad, OpacityGrad, NoGrad>>>;
+                                    std::conditional_t<opgrad, OpacityGrad,
+                                                       std::conditional_t<splatgrad, SplatGrad, NoGrad>>>>;
     using SumPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat, ChannelPayload, NoPayload>>;
     using RayPayload = std::conditional_t<std::is_same_v<Grad, NoGrad>, SumPayload, typename Grad::Payload>;
 };
@@ -1205,7 +1280,7 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
 // Pass J so handles every lane's J-th g-passing candidate of the stage end to end (lane_pass), and a stage runs as many
 // passes as its busiest lane passes g on candidates, not one per candidate that some lane passes g on.
 template <class V>
-constexpr bool kShPerLane = V::sh && !V::stats && !V::shgrad && !V::opgrad;
+constexpr bool kShPerLane = V::sh && !V::stats && !V::shgrad && !V::resweep;
 // Pass J of a stage. at[J][c] = the lanes whose J-th g-passing candidate is candidate c (c >= J), gone = the lanes whose
 // ray stopped in an earlier pass of this stage. The lane selects its candidate index and its g by the masks and reads its
 // candidate's record and, where it blends, SH row at its own address: the stage's records lie 64 B = 16 banks apart and
@@ -1384,7 +1459,7 @@ __device__ GSRT_INLINE void shade_stage(const Stage* stg, uint32_t m, const floa
             ray.dg_blend += __ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f) ? 1u : 0u;
             ray.dg_lanes_blend += (uint32_t)__popcll(__ballot(alpha > 0.0f && ray.T * (1.0f - alpha) >= 1e-4f));
 #endif
-            grad.candidate(e, fabsf(q1.w));  // what a hit's term may need besides the blend's own values
+            grad.candidate(e, fabsf(q1.w), &stg->rec[c]);  // what a hit's term may need besides the blend's own values
             // lanes whose ray stopped here leave the stage's later masks, under one wave-uniform branch
             const uint64_t stopped = blend_hit<V>(stg, c, q0.w, alpha, contrib, ray, grad);
             if (stopped) {
@@ -2202,7 +2277,7 @@ void k_render_cor(const KArgs karg) {
 #endif
     for (uint32_t pass = 0; pass < passes; ++pass) {
         CorRay<V> ray = cor_ray<V>(tile.pixel(), S, pass, passes);
-        // opgrad: two sweeps over the same rounds. The first is the plain blend and gives the pass its results and the
+        // opgrad and splatgrad (V::resweep): two sweeps over the same rounds. The first is the plain blend and gives the pass its results and the
         // ray its finals; the second sets the ray up again, restarts the rounds from the tile's first list
         // (round_from_list issues it again: prefetched is false by then) and blends the same hits in the same order with
         // the same arithmetic, so that every test falls as it fell, now with the gradient terms (blend_hit)
@@ -2234,7 +2309,7 @@ void k_render_cor(const KArgs karg) {
                 if (cl.total > maxc) maxc = cl.total;
                 // a gradient kind's terms go to its sink (opgrad: in the second sweep; the first is the plain blend)
                 // a gradient kind's terms go to its sink; opgrad: in the second sweep, the first is the plain blend
-                const bool live = V::opgrad && sweep == 0
+                const bool live = V::resweep && sweep == 0
                     ? shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, NoGrad{})
                     : shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, V::Grad::of_frame());
 #ifdef GSRT_DIAG
@@ -2245,7 +2320,7 @@ void k_render_cor(const KArgs karg) {
                 has_lo = true;  // lo = the last (largest) key of this round
                 __syncthreads();
             }
-            if constexpr (V::opgrad) {
+            if constexpr (V::resweep) {
                 if (sweep == 0) {
                     sums.take(ray);  // once per pass, from the first sweep's values
                     const float fin[4] = {ray.C[0], ray.C[1], ray.C[2], ray.T};
@@ -2254,8 +2329,8 @@ void k_render_cor(const KArgs karg) {
                     for (int q = 0; q < 4; ++q) ray.k.fin[q] = fin[q];
                 }
             }
-        } while (V::opgrad && ++sweep < 2);
-        if constexpr (!V::opgrad) sums.take(ray);
+        } while (V::resweep && ++sweep < 2);
+        if constexpr (!V::resweep) sums.take(ray);
         if (passes > 1) {  // then S == 1 (make_plan): the lane's pixel accumulates its passes in order, prev + pass
             const CorTile::Pixel p = tile.pixel();
             if (p.valid) {
@@ -3103,6 +3178,8 @@ static CorLaunch cor_kernel_of(bool sh, bool lut) {
         return lut ? launch_cor_t<CorVariant<K, false, true>> : launch_cor_t<CorVariant<K, false, false>>;
     else if constexpr (K == CorKind::shgrad)  // only for a scene with SH rows (gsrt_api.cpp: GSRT_E_STATE without)
         return lut ? launch_cor_t<CorVariant<K, true, true>> : launch_cor_t<CorVariant<K, true, false>>;
+    else if constexpr (K == CorKind::splatgrad)  // never with the LUT (frame_refusal)
+        return sh ? launch_cor_t<CorVariant<K, true, false>> : launch_cor_t<CorVariant<K, false, false>>;
     else
         return sh ? (lut ? launch_cor_t<CorVariant<K, true, true>> : launch_cor_t<CorVariant<K, true, false>>)
                   : (lut ? launch_cor_t<CorVariant<K, false, true>> : launch_cor_t<CorVariant<K, false, false>>);
@@ -3116,6 +3193,7 @@ static CorLaunch cor_kernel(CorKind kind, bool sh, bool lut) {
         case CorKind::grad: return cor_kernel_of<CorKind::grad>(sh, lut);
         case CorKind::shgrad: return cor_kernel_of<CorKind::shgrad>(sh, lut);
         case CorKind::opgrad: return cor_kernel_of<CorKind::opgrad>(sh, lut);
+        case CorKind::splatgrad: return cor_kernel_of<CorKind::splatgrad>(sh, lut);
     }
     return nullptr;
 }
@@ -3174,6 +3252,7 @@ static gsrt_status launch_cor(gsrt_scene* sc, const RenderPlan& plan, const Fram
     if (A.grad_rows)
         switch (sync->grad_kind) {
             case GradKind::opacity: kind = CorKind::opgrad; break;
+            case GradKind::splat: kind = CorKind::splatgrad; break;
             case GradKind::sh: kind = CorKind::shgrad; break;
             default: kind = CorKind::grad; break;
         }

@@ -26,6 +26,7 @@ FLAG_LUT, FLAG_STATS, FLAG_OUT_DUMP8, FLAG_DEPTH, FLAG_FEATURES = 0x100, 0x200, 
 FLAG_FEATURE_GRAD = 0x2000
 FLAG_SH_GRAD = 0x4000
 FLAG_OPACITY_GRAD = 0x8000
+FLAG_SPLAT_GRAD = 0x20000
 MAX_FEATURES = 16  # GSRT_MAX_FEATURES
 DUMP8_ESCAPE = 1 << 30  # GSRT_DUMP8_ESCAPE
 SYNTH_COR, SYNTH_REF, SYNTH_NEEDLE = 0, 1, 2
@@ -69,6 +70,8 @@ EXPORTS = [
     "gsrt_feature_buffer", "gsrt_render_feature_grad", "gsrt_render_feature_grad_async", "gsrt_group_order",
     "gsrt_unit_order", "gsrt_scene_set_sh", "gsrt_render_sh_grad", "gsrt_render_sh_grad_async",
     "gsrt_render_opacity_grad", "gsrt_render_opacity_grad_async", "gsrt_debug_frame_refusal",
+    "gsrt_render_splat_grad", "gsrt_render_splat_grad_async", "gsrt_splat_grad_to_model", "gsrt_splat_grad_to_model_async",
+    "gsrt_debug_frame_refusal_kind",
 ]
 
 
@@ -187,6 +190,11 @@ def _load():
         "gsrt_render_opacity_grad": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_render_opacity_grad_async": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_debug_frame_refusal": ([u32, u32, u32, i32, u32, i32, i32, ctypes.c_char_p, ctypes.c_size_t], i32),
+        "gsrt_debug_frame_refusal_kind": ([u32, u32, u32, i32, u32, i32, i32, ctypes.c_char_p, ctypes.c_size_t], i32),
+        "gsrt_render_splat_grad": ([P, P, u32, u32, P, P, i32], i32),
+        "gsrt_render_splat_grad_async": ([P, P, u32, u32, P, P, i32], i32),
+        "gsrt_splat_grad_to_model": ([P, P, P, P, P, i32], i32),
+        "gsrt_splat_grad_to_model_async": ([P, P, P, P, P, i32], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -973,6 +981,45 @@ class Scene:
         ordinary device memory) are device addresses; accumulate adds to the table instead of writing it."""
         _check(lib.gsrt_render_opacity_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
                                                   ctypes.c_void_p(d_grad_table or None), 1 if accumulate else 0), self.ctx)
+
+    def splat_grad(self, ubo, grad_image, mode=MODE_COR, k=0):
+        """The backward of a colour frame to each Gaussian's screen-space splat (gsrt_render_splat_grad): grad_image is
+        the upstream gradient of the RGBA frame, (H, W, 4) float32, or (H, W, 3), padded with a zero alpha gradient;
+        returns (n, 8): dL/d(ppx, ppy, A, B, C) of the pixel centre and the conic in slots 0..4, dL/d(opacity) in slot 5
+        (opacity_grad's sum), +0 in slots 6 and 7. Slots 0 and 1 are the view-space positional gradient densification
+        thresholds on. The sum's order is unspecified (float atomics). Not with FLAG_LUT."""
+        g = _rgba_grad("splat_grad", ubo, grad_image)
+        out = np.zeros((self.n, 8), np.float32)
+        _check(lib.gsrt_render_splat_grad(self.handle, _p(ubo), mode, k, _p(g), _p(out), 0), self.ctx)
+        return out
+
+    def splat_grad_async(self, ubo, d_grad_image: int, d_grad_splat: int, accumulate=False, mode=MODE_COR, k=0):
+        """Enqueue one splat gradient frame on ctx.stream: d_grad_image (W*H*4 floats) and d_grad_splat (n*8 floats,
+        ordinary device memory) are device addresses; accumulate adds to the table instead of writing it."""
+        _check(lib.gsrt_render_splat_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
+                                                ctypes.c_void_p(d_grad_splat or None), 1 if accumulate else 0), self.ctx)
+
+    def model_grad(self, ubo, splat):
+        """The projection backwards (gsrt_splat_grad_to_model): splat is the (n, 8) table of splat_grad for the same ubo
+        and scene parameters; returns (grad_center (n, 3), grad_cov (n, 6)), the covariance in cov3d's order xx, xy, xz,
+        yy, yz, zz, an off-diagonal entry counted as the one variable it is. Deterministic."""
+        rows = _f32(splat, (self.n, 8))
+        gc, gv = np.zeros((self.n, 3), np.float32), np.zeros((self.n, 6), np.float32)
+        _check(lib.gsrt_splat_grad_to_model(self.handle, _p(ubo), _p(rows), _p(gc), _p(gv), 0), self.ctx)
+        return gc, gv
+
+    def model_grad_async(self, ubo, d_grad_splat: int, d_grad_center: int, d_grad_cov: int, accumulate=False):
+        """Enqueue the projection's backward on ctx.stream: device addresses of n*8, n*3 and n*6 floats."""
+        _check(lib.gsrt_splat_grad_to_model_async(self.handle, _p(ubo), ctypes.c_void_p(d_grad_splat or None),
+                                                  ctypes.c_void_p(d_grad_center or None),
+                                                  ctypes.c_void_p(d_grad_cov or None), 1 if accumulate else 0), self.ctx)
+
+    def geometry_grad(self, ubo, grad_image, mode=MODE_COR, k=0):
+        """One splat gradient frame and the projection's backward: (grad_center (n, 3), grad_cov (n, 6), grad_opacity
+        (n,)) of <grad_image, frame> with respect to the scene's parameters."""
+        rows = self.splat_grad(ubo, grad_image, mode, k)
+        gc, gv = self.model_grad(ubo, rows)
+        return gc, gv, rows[:, 5].copy()
 
     def render_sharded(self, ubo, mode=MODE_COR, k=0, want_image=True):
         W, H = int(ubo["width"][0]), int(ubo["height"][0])

@@ -10,6 +10,12 @@ and for colour frames: fit the scene's SH table (its appearance) on frozen geome
     rgba = render_colour(scene, ubo, sh)               # sh: (n, 16, 3) or (n, 48) float32 tensor on the scene's device
     loss(rgba).backward()                              # sh.grad: Scene.sh_grad of the loss's gradient
 
+and for a whole model, geometry included: optimise a scene end to end.
+
+    from gsrt.autograd import render_model
+    rgba = render_model(scene, ubo, center, rot, scale, opacity, sh)
+    loss(rgba).backward()                              # .grad of all five, through Scene.splat_grad and Scene.model_grad
+
 torch is imported here only; `import gsrt` never needs it.
 
 Synchronisation is plain and blocking: the current torch stream is synchronised before the library reads a tensor, and
@@ -164,3 +170,84 @@ def render_rgba(scene, ubo, opacity, sh=None, mode=MODE_COR, k=0):
     has run, or the gradient is that of another frame. The forward leaves `opacity` as the scene's opacities and `sh`
     as its SH table; a geometry change made through Scene.update by the caller is not seen by the kept copy."""
     return _RenderRgba.apply(opacity, sh, scene, ubo, mode, k)
+
+
+class _RenderModel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k):
+        n = scene.n
+        params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
+        params[:, 0:3], params[:, 3], params[:, 4:10] = center.detach(), opacity.detach(), cov3d.detach()
+        boxes = aabbs.detach().to(torch.float32).contiguous()
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        rgba = torch.empty((H, W, 4), dtype=torch.float32, device=center.device)
+        table = None if sh is None else sh.contiguous()
+        torch.cuda.current_stream(center.device).synchronize()
+        if table is not None:
+            scene.set_sh(table.data_ptr())  # copied into the scene's own rows
+        scene.update(params=params.data_ptr(), aabbs=boxes.data_ptr())  # copied
+        scene.refit_bvh()  # the BVH's boxes follow the new AABBs
+        scene.render_async(ubo, mode, k, rgba.data_ptr())
+        scene.ctx.synchronize()
+        ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
+        ctx.sh_shape = None if sh is None else tuple(sh.shape)
+        return rgba
+
+    @staticmethod
+    def backward(ctx, grad_rgba):
+        n = ctx.scene.n
+        g = grad_rgba.to(torch.float32).contiguous()
+        rows = torch.empty((n, 8), dtype=torch.float32, device=g.device)
+        d_c = torch.empty((n, 3), dtype=torch.float32, device=g.device)
+        d_v = torch.empty((n, 6), dtype=torch.float32, device=g.device)
+        d_sh = None
+        if ctx.sh_shape is not None and ctx.needs_input_grad[3]:
+            d_sh = torch.empty(ctx.sh_shape, dtype=torch.float32, device=g.device)
+        torch.cuda.current_stream(g.device).synchronize()
+        ctx.scene.splat_grad_async(ctx.ubo, g.data_ptr(), rows.data_ptr(), False, ctx.mode, ctx.k)
+        ctx.scene.model_grad_async(ctx.ubo, rows.data_ptr(), d_c.data_ptr(), d_v.data_ptr(), False)
+        if d_sh is not None:
+            ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
+        ctx.scene.ctx.synchronize()
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None
+
+
+def model_covariance(rot, scale):
+    """cov3d (n, 6) in GaussParam's order xx, xy, xz, yy, yz, zz from rotations (r, x, y, z) and scales, with ordinary
+    differentiable torch operations: Sigma = (S R)^T (S R), R the matrix gsrt_scene_from_model builds (Sphere.hpp's)."""
+    r, x, y, z = rot[:, 0], rot[:, 1], rot[:, 2], rot[:, 3]
+    R = torch.stack([torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y + r * z), 2 * (x * z - r * y)], -1),
+                     torch.stack([2 * (x * y - r * z), 1 - 2 * (x * x + z * z), 2 * (y * z + r * x)], -1),
+                     torch.stack([2 * (x * z + r * y), 2 * (y * z - r * x), 1 - 2 * (x * x + y * y)], -1)], -2)
+    M = scale[:, :, None] * R  # row k of R scaled by s_k
+    S = torch.einsum("nki,nkj->nij", M, M)
+    return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], -1)
+
+
+def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0):
+    """One colour frame of a whole model as a torch tensor rgba[H, W, 4], differentiable with respect to `center` (n, 3),
+    `rot` (n, 4; r, x, y, z, used as given), `scale` (n, 3), `opacity` (n,) and, when given, the SH table `sh` ((n, 16, 3)
+    or (n, 48)): float32 GPU tensors for a scene of n Gaussians with a built BVH. cov3d is formed here with torch
+    operations (model_covariance), the AABBs as centre +- 3 max scale; the forward passes both to Scene.update, refits
+    the BVH and renders. The backward is one splat gradient frame (Scene.splat_grad_async), the projection's backward
+    (Scene.model_grad_async) for the centres and cov3d, slot 5 of the splat rows for the opacities, and
+    Scene.sh_grad_async when `sh` requires a gradient; torch chains cov3d back to `rot` and `scale`. The gradient is that
+    of gsrt.h: clamped hits contribute 0; the hits, their order, the AABB test and the stop are not differentiated. Not
+    with FLAG_LUT.
+    Blocking synchronisation on both sides: torch's current stream before each library call, Context.synchronize()
+    after it.
+    The backward renders the scene again: it keeps a copy of `ubo`, but the scene's arrays (Scene.update, refits,
+    attached arrays, streamed pages) and its SH rows must stay as they were in the forward until backward has run, or
+    the gradient is that of another frame. The forward leaves the model as the scene's."""
+    n = scene.n
+    for name, t, shape in (("center", center, (n, 3)), ("rot", rot, (n, 4)), ("scale", scale, (n, 3)),
+                           ("opacity", opacity, (n,))):
+        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
+            raise ValueError(f"render_model: {name} must be a {shape} float32 tensor on the GPU")
+    if sh is not None and (sh.dtype != torch.float32 or not sh.is_cuda or tuple(sh.shape) not in ((n, 16, 3), (n, 48))):
+        raise ValueError("render_model: sh must be an (n, 16, 3) or (n, 48) float32 tensor on the GPU")
+    cov3d = model_covariance(rot, scale)
+    with torch.no_grad():
+        rad = 3.0 * scale.max(dim=1, keepdim=True).values
+        aabbs = torch.cat([center - rad, center + rad], 1)
+    return _RenderModel.apply(center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k)

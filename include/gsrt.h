@@ -82,8 +82,11 @@ enum {
                                        gsrt_render_feature_grad (below) itself, GSRT_E_ARG through every other entry point */
     GSRT_FLAG_SH_GRAD = 0x4000, /* whole COR frames: the backward of a colour frame to the SH table; set by gsrt_render_sh_grad
                                    (below) itself, GSRT_E_ARG through every other entry point */
-    GSRT_FLAG_OPACITY_GRAD = 0x8000 /* whole COR frames: the backward of a colour frame to the opacities; set by
+    GSRT_FLAG_OPACITY_GRAD = 0x8000, /* whole COR frames: the backward of a colour frame to the opacities; set by
                                        gsrt_render_opacity_grad (below) itself, GSRT_E_ARG through every other entry point */
+    GSRT_FLAG_SPLAT_GRAD = 0x20000 /* whole COR frames: the backward of a colour frame to each Gaussian's screen-space
+                                      centre and conic; set by gsrt_render_splat_grad (below) itself, GSRT_E_ARG through
+                                      every other entry point and with GSRT_FLAG_LUT (0x10000 is no flag: "bad mode") */
 };
 /* synthetic cloud kinds */
 enum { GSRT_SYNTH_COR = 0, GSRT_SYNTH_REF = 1, GSRT_SYNTH_NEEDLE = 2 };
@@ -385,13 +388,65 @@ gsrt_status gsrt_render_sh_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, ui
  * GSRT_E_ARG (gsrt_last_error names GSRT_FLAG_OPACITY_GRAD, and the context renders as before): REF mode; GSRT_FLAG_STATS,
  * GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH, GSRT_FLAG_FEATURES, GSRT_FLAG_FEATURE_GRAD or GSRT_FLAG_SH_GRAD with it; sharded entry
  * points; a scene with a mesh; a NULL grad_image or grad_table; the flag passed to any other entry point.
- * Not provided: gradients with respect to means, covariances or SH (SH: gsrt_render_sh_grad); sharded frames.
+ * Not provided here: gradients with respect to means and covariances (gsrt_render_splat_grad) or SH
+ * (gsrt_render_sh_grad); sharded frames.
  * gsrt_render_opacity_grad blocks until the table is complete, like gsrt_render. */
 gsrt_status gsrt_render_opacity_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                      const float* grad_image, float* grad_table, int accumulate);
 /* the same, enqueued on gsrt_stream(); device pointers only */
 gsrt_status gsrt_render_opacity_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
                                            const float* d_grad_image, float* d_grad_table, int accumulate);
+/* Splat gradient frame (GSRT_FLAG_SPLAT_GRAD): the backward of a plain COR colour frame (RGBA) with respect to what the
+ * projection gives each Gaussian on the screen: the pixel centre (ppx, ppy) and the conic (A, B, C) of
+ * g = (A dx^2 + 2 B dx dy + C dy^2) / 2, dx = px - ppx, dy = py - ppy for a ray through pixel coordinate (px, py). It is
+ * the view-space gradient that densification thresholds on, and gsrt_splat_grad_to_model (below) chains it to the
+ * Gaussians' centres and covariances. Every ray is shaded twice, as for gsrt_render_opacity_grad.
+ * grad_image is the upstream gradient G of the RGBA frame, W*H*4 floats, all four channels used. grad_splat receives n
+ * rows of 8 floats (32 bytes), [gauss][slot].
+ * With alpha_i, T_i, col_i, the finals, Gs and d_i exactly as gsrt_render_opacity_grad defines them, dx and dy the float32
+ * differences the forward forms and e_i its float32 exponential: for every blended hit i of Gaussian g whose
+ * fl(|o_g| e_i) < 0.99f, with q_i = -alpha_i d_i (d alpha / dg = -alpha where the clamp let o e through),
+ *     row[0] += q_i * -(A dx + B dy)     dL/dppx          row[3] += q_i * dx dy            dL/dB
+ *     row[1] += q_i * -(B dx + C dy)     dL/dppy          row[4] += q_i * dy^2 / 2         dL/dC
+ *     row[2] += q_i * dx^2 / 2           dL/dA            row[5] += d_i * e_i              dL/d opacity
+ * and row[6] = row[7] = +0. Slot 5 is the sum gsrt_render_opacity_grad defines: one backward frame serves geometry and
+ * opacity. A hit whose alpha was clamped to 0.99 contributes +0 to every slot (a select). Sets fixed by the forward
+ * frame and not differentiated: the hits taken and their order (the depth key), the AABB slab test, the alpha > 1/255 cut
+ * and gcut, and the stop. The colour does not depend on the geometry: the SH basis is the ray's. The terms are summed
+ * with float atomic adds: the order of a sum is unspecified.
+ * accumulate, host and device pointers, the framebuffer (the plain colour frame's, bit for bit), the in-order path and
+ * timing: as for gsrt_render_opacity_grad; with accumulate != 0 slots 6 and 7 keep what they hold. Scenes with and without
+ * SH rows are both served.
+ * GSRT_E_ARG (gsrt_last_error names GSRT_FLAG_SPLAT_GRAD, and the context renders as before): REF mode; GSRT_FLAG_LUT
+ * (under the LUT the exponential is piecewise linear and d alpha / dg is a segment's slope, not -alpha); GSRT_FLAG_STATS,
+ * GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH, GSRT_FLAG_FEATURES or another gradient flag with it; sharded entry points; a scene
+ * with a mesh; a NULL grad_image or grad_splat; the flag passed to any other entry point.
+ * Not provided: LUT frames; sharded frames; gradients through the hit order, the AABB test or the stop; SH
+ * (gsrt_render_sh_grad).
+ * gsrt_render_splat_grad blocks until the table is complete, like gsrt_render. */
+gsrt_status gsrt_render_splat_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                   const float* grad_image, float* grad_splat, int accumulate);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_render_splat_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                         const float* d_grad_image, float* d_grad_splat, int accumulate);
+/* The COR projection backwards: the splat rows of gsrt_render_splat_grad (n x 8 floats; slots 0..4 are read) chained to
+ * the gradients with respect to each Gaussian's centre, grad_center (n x 3 floats, center_opacity[0..3)), and its
+ * covariance, grad_cov (n x 6 floats in cov3d's order xx, xy, xz, yy, yz, zz; an off-diagonal entry is one variable that
+ * stands twice in Sigma, so its gradient is the sum of both places). ubo is the frame's; the scene's current parameters
+ * are read, a borrowed array included (gsrt_scene_attach). One lane per Gaussian recomputes the projection's float32
+ * intermediates: V = T Sigma T^T + 0.3 I with the 0.3 a constant, Q = V^-1, dL/dV = -Q [[dA, dB/2], [dB/2, dC]] Q; the
+ * centre receives its part through (ppx, ppy), with the general projection matrix, and through T's dependence on the
+ * view-space position. A Gaussian the projection marks invalid (depth <= 0 or det <= 0) gets +0. Nothing flows through
+ * the depth key, the AABB or the footprint. No atomics: the result is deterministic.
+ * accumulate == 0: both tables are written. accumulate != 0: added to; device tables only. All three tables are host or
+ * device pointers (ordinary device memory), each on its own.
+ * GSRT_E_ARG: a NULL pointer; a host table with accumulate; a scene with a mesh. GSRT_E_STATE: before gsrt_build_bvh, as
+ * for a render. gsrt_splat_grad_to_model blocks until the tables are complete. */
+gsrt_status gsrt_splat_grad_to_model(gsrt_scene* scene, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
+                                     float* grad_cov, int accumulate);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_splat_grad_to_model_async(gsrt_scene* scene, const gsrt_ubo* ubo, const float* d_grad_splat,
+                                           float* d_grad_center, float* d_grad_cov, int accumulate);
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into

@@ -52,6 +52,10 @@ gsrt_status gsrt_unit_order(uint32_t units, uint32_t row0, uint32_t row1, uint32
  * text, cut to fit and terminated; empty with GSRT_OK. The frame-size and NULL checks of the entry points come before. */
 gsrt_status gsrt_debug_frame_refusal(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
                                      int has_features, int has_sh, char* msg, size_t cap);
+/* the same with the callers that came later: 4 gsrt_render_splat_grad (gsrt_debug_frame_refusal keeps refusing every
+ * caller above 3 with GSRT_E_ARG). Callers 0..3 answer as above for every mode. */
+gsrt_status gsrt_debug_frame_refusal_kind(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
+                                          int has_features, int has_sh, char* msg, size_t cap);
 /* the context's streams (hipStream_t) in creation order: render, prep H 0, prep L 0, prep H 1, prep L 1, update, comm
  * (NULL before gsrt_comm_init); *n = 7. For the hardware-queue map (profiles/probes/gsrt_queue_map.py) */
 gsrt_status gsrt_debug_streams(gsrt_ctx* ctx, void* out[8], uint32_t* n);
