@@ -725,7 +725,7 @@ __device__ GSRT_INLINE void add_counters(unsigned long long rays, unsigned long 
 
 // LDS stage of one group of sorted candidates: the 64-B records and the SH-3 coefficients. Filled by LDS-DMA
 // (global_load_lds, 16 B per lane, no VGPR destination): the stage is 16-B pieces in lane order, records first.
-// FEAT kernels stage no SH rows: the candidates' 64-B feature rows take the first kGroup * 64 B of sh (feat_row).
+// A kind whose output has its own table (feat: 64-B feature rows) stages its rows at the start of sh, and no SH rows.
 struct Stage {
     SplatRec rec[kGroup];         // kGroup * 64 B
     float sh[kGroup][3][16];      // kGroup * 192 B, device layout [gauss][rgb][coef]
@@ -758,8 +758,8 @@ __device__ GSRT_INLINE uint32_t lds_read_settled(const uint32_t* p) {
 // issue the LDS-DMA of group g0 of ids[0..count) into dst: piece p < 4*kGroup is quarter p&3 of record p>>2,
 // the next 12*kGroup pieces are the SH rows (12 pieces each); piece p lands at byte 16 p of the stage. Every
 // lane computes its piece's address the same way (base, row stride and offset selected, no divergent paths).
-// Waited for by wait_stage before the stage is read. feat: sh is the feature table and a row is 4 pieces (64 B), so
-// the stage is 4 kGroup record pieces and 4 kGroup feature pieces, one DMA instruction.
+// Waited for by wait_stage before the stage is read. sh is the output's table (Out::rows): feat's row is 4 pieces
+// (64 B), so its stage is 4 kGroup record pieces and 4 kGroup feature pieces, one DMA instruction.
 template <class V>
 __device__ GSRT_INLINE void stage_issue(const uint32_t* ids, uint32_t count, uint32_t g0, uint32_t lane, Stage* dst,
                                    const SplatRec* recs, const float* sh) {
@@ -798,7 +798,7 @@ struct CorRay {
     float pxs, pys;
     float bs[16];
     float T, C[3];
-    typename V::RayPayload k;  // the kind's own: depth D, feat F[16] (no bs there), a gradient kind's upstream gradient
+    typename V::RayPayload k;  // the kind's own: its output's sums (feat: no bs there) or its sink's payload
     bool active;
     uint32_t cand, blended, term;
 #ifdef GSRT_DIAG
@@ -848,10 +848,6 @@ struct ShFromStage {
 // This lane's bit of a wave-uniform lane mask (a ballot held in an SGPR pair): the mask itself is the v_cndmask
 // or exec source, no compare forms it again.
 __device__ GSRT_INLINE bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
-// candidate c's feature row in a FEAT kernel's stage (stage_issue): 16 floats at a wave-uniform address
-__device__ GSRT_INLINE const float4* feat_row(const Stage* stg, uint32_t c) {
-    return reinterpret_cast<const float4*>(&stg->sh[0][0][0]) + 4 * c;
-}
 // GRAD: the sums of t[0..16) over the lanes of each 16-lane row, transposed: lane l returns the sum of t[l & 15] over
 // its row. A butterfly that halves the channels a lane carries at every step: partners 15 - i (row_mirror), 7 - i within
 // 8 lanes (row_half_mirror), i ^ 2 and i ^ 1 (quad permutes). A lane keeps the half its own lane bit names and sends
@@ -1060,39 +1056,48 @@ struct ShGrad {
     };
     __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows}; }
 };
-// opgrad (GSRT_FLAG_OPACITY_GRAD): the backward of a plain colour frame to the opacities (one float per Gaussian id),
-// with or without SH rows; the plain frame's RGBA. Every pass shades its rays twice (k_render_cor): the plain blend with
-// NoGrad for the ray's finals, then the same blend again with this sink. In the ray the upstream gradient G_ch / ns of
-// all four channels (alpha depends on opacity) and the first sweep's finals: the colour C_ch and the transmittance
-// T_end. candidate: the hit's exponential e and whether fl(|o| e) < 0.99f, i.e. whether alpha is |o| e and not the
-// clamp's constant. hit_lane: d(frame . G) / d(alpha) of this hit from the finals and the running colour after this
-// hit, times d(alpha) / d|o| = e where the clamp let |o| e through; a select: the lanes that do not blend c keep the
-// share's +0 in t[c]. The flush sums the lanes' terms over the wave (opgrad_stage_sums) and is one atomic
-// wave-instruction, lane c < kGroup adding candidate c's sum.
-struct OpacityGrad {
-    float* rows;
-    __device__ GSRT_INLINE static OpacityGrad of_frame() { return {kargs().a.grad_rows}; }
+// What the sinks of the resweep kinds (opgrad, splatgrad) and their Shares derive from. In the ray the upstream gradient
+// G_ch / ns of all four channels and the first sweep's finals: the colour C_ch and the transmittance T_end. candidate:
+// the hit's exponential e and whether fl(|o| e) < 0.99f, i.e. whether alpha is |o| e and not the clamp's constant.
+// dalpha: d = d(frame . G) / d(alpha) of a blended hit, from the finals and the running colour after this hit
+struct ResweepGrad {
     struct Payload { float G[4], fin[4]; };
     __device__ GSRT_INLINE static void load(Payload& g, uint32_t x, uint32_t y, bool valid, uint32_t ns) {
         load_upstream(g.G, x, y, valid, ns);
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) g.fin[ch] = 0.0f;  // k_render_cor sets them before the second sweep
     }
-    struct Share {
+    template <class Terms>  // t: the lane's terms of the stage, the sink's own array; before mask as it was: DESIGN.md 3
+    struct ShareOf {
         const uint32_t* ids;
         float* rows;
-        float t[kGroup] = {0.0f, 0.0f, 0.0f, 0.0f};
-        uint32_t mask = 0;
-        float e = 0.0f; bool open = false;
+        Terms t = {};
+        uint32_t mask = 0; float e = 0.0f; bool open = false;
         __device__ GSRT_INLINE void candidate(float e_, float o, const SplatRec*) { e = e_, open = o * e_ < 0.99f; }
         template <class Ray>
         __device__ GSRT_INLINE void hit(uint32_t c, uint64_t, float, const float (&)[3], const Ray&) { mask |= 1u << c; }
         template <class Ray>
-        __device__ GSRT_INLINE void hit_lane(uint32_t c, float alpha, const float (&col)[3], const Ray& ray) {
+        __device__ GSRT_INLINE float dalpha(float alpha, const float (&col)[3], const Ray& ray) const {
             const float r = 1.0f / (1.0f - alpha);  // alpha <= 0.99
             float d = (ray.k.G[3] * ray.k.fin[3]) * r;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) d = d + ray.k.G[ch] * (ray.T * col[ch] - (ray.k.fin[ch] - ray.C[ch]) * r);
+            return d;
+        }
+    };
+};
+// opgrad (GSRT_FLAG_OPACITY_GRAD): the backward of a plain colour frame to the opacities (one float per Gaussian id),
+// with or without SH rows; the plain frame's RGBA. Every pass shades its rays twice (k_render_cor): the plain blend with
+// NoGrad for the ray's finals, then the same blend again with this sink. hit_lane: the hit's d (ResweepGrad) times
+// d(alpha) / d|o| = e where the clamp let |o| e through, a select: every other lane keeps the share's +0 in t[c]. The
+// flush sums the lanes' terms over the wave (opgrad_stage_sums): one atomic wave-instruction, lane c < kGroup adds.
+struct OpacityGrad : ResweepGrad {
+    float* rows;
+    __device__ GSRT_INLINE static OpacityGrad of_frame() { return {{}, kargs().a.grad_rows}; }
+    struct Share : ShareOf<float[kGroup]> {
+        template <class Ray>
+        __device__ GSRT_INLINE void hit_lane(uint32_t c, float alpha, const float (&col)[3], const Ray& ray) {
+            const float d = dalpha(alpha, col, ray);
             t[c] = open ? d * e : 0.0f;
         }
         __device__ GSRT_INLINE void flush() const {
@@ -1100,42 +1105,27 @@ struct OpacityGrad {
                            [&](uint32_t id, uint32_t, float sum) { atomicAdd(rows + id, sum); });
         }
     };
-    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows}; }
+    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{{ids, rows}}; }
 };
-
 // splatgrad (GSRT_FLAG_SPLAT_GRAD): the backward of a plain colour frame to each Gaussian's screen-space splat: the pixel
 // centre (ppx, ppy) and the conic (A, B, C) of g = (A dx^2 + 2 B dx dy + C dy^2) / 2, with or without SH rows; the plain
-// frame's RGBA. Payload and sweeps are opgrad's: the second sweep forms the same d = d(frame . G) / d(alpha) per blended
-// hit. Where the clamp let |o| e through, d(alpha) / dg = -alpha, so q = -alpha d weighs dg / d(ppx, ppy, A, B, C); the
-// lane reads the candidate's centre and conic again from its staged record (words 8..12; the record stores A / 2 and
-// C / 2, exact halves) and forms dx, dy as phase 1 of shade_stage formed them. Slot 5 is opgrad's own term d e. Selects:
-// the lanes that do not blend c and the clamped hits keep the share's +0. The flush pads a candidate's six sums to eight
-// and sums them over the wave as grad's sixteen channels are: candidates 0, 1 and 2, 3 through grad_row_sums, the rows
-// through grad_stage_sums, which leaves candidate c's slot q on lane 8 c + q; one atomic wave-instruction, 24 lanes add.
-struct SplatGrad {
+// frame's RGBA. Sweeps as opgrad's: the second forms the same d per blended hit (ResweepGrad). Where the clamp let
+// |o| e through, d(alpha) / dg = -alpha, so q = -alpha d weighs dg / d(ppx, ppy, A, B, C); the lane reads the
+// candidate's centre and conic again from its staged record (words 8..12; the record stores A / 2 and C / 2, exact
+// halves) and forms dx, dy as phase 1 of shade_stage formed them. Slot 5 is opgrad's own term d e. Selects: the lanes
+// that do not blend c and the clamped hits keep the share's +0. The flush pads a candidate's six sums to eight and sums
+// them over the wave as grad's sixteen channels are: candidates 0, 1 and 2, 3 through grad_row_sums, the rows through
+// grad_stage_sums, which leaves candidate c's slot q on lane 8 c + q; one atomic wave-instruction, 24 lanes add.
+struct SplatGrad : ResweepGrad {
     float* rows;
-    __device__ GSRT_INLINE static SplatGrad of_frame() { return {kargs().a.grad_rows}; }
-    using Payload = OpacityGrad::Payload;
-    __device__ GSRT_INLINE static void load(Payload& g, uint32_t x, uint32_t y, bool valid, uint32_t ns) {
-        OpacityGrad::load(g, x, y, valid, ns);
-    }
+    __device__ GSRT_INLINE static SplatGrad of_frame() { return {{}, kargs().a.grad_rows}; }
     static constexpr uint32_t kSlots = 6;  // of a row's 8 floats, the ones a frame adds to
-    struct Share {
-        const uint32_t* ids;
-        float* rows;
-        float t[kGroup][kSlots] = {};
-        uint32_t mask = 0;
-        float e = 0.0f; bool open = false;
+    struct Share : ShareOf<float[kGroup][kSlots]> {
         const SplatRec* rec = nullptr;
-        __device__ GSRT_INLINE void candidate(float e_, float o, const SplatRec* r) { e = e_, open = o * e_ < 0.99f, rec = r; }
-        template <class Ray>
-        __device__ GSRT_INLINE void hit(uint32_t c, uint64_t, float, const float (&)[3], const Ray&) { mask |= 1u << c; }
+        __device__ GSRT_INLINE void candidate(float e_, float o, const SplatRec* r) { ShareOf::candidate(e_, o, r), rec = r; }
         template <class Ray>
         __device__ GSRT_INLINE void hit_lane(uint32_t c, float alpha, const float (&col)[3], const Ray& ray) {
-            const float r = 1.0f / (1.0f - alpha);  // alpha <= 0.99
-            float d = (ray.k.G[3] * ray.k.fin[3]) * r;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) d = d + ray.k.G[ch] * (ray.T * col[ch] - (ray.k.fin[ch] - ray.C[ch]) * r);
+            const float d = dalpha(alpha, col, ray);
             const float4 q2 = reinterpret_cast<const float4*>(rec)[2];  // ppx, ppy, A/2, B
             const float4 q3 = reinterpret_cast<const float4*>(rec)[3];  // C/2, ...
             const float dx = ray.pxs - q2.x, dy = ray.pys - q2.y;       // the blending lanes' rays are live: no NaN
@@ -1164,17 +1154,74 @@ struct SplatGrad {
             });
         }
     };
-    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{ids, rows}; }
+    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{{ids, rows}}; }
+};
+
+// ---- forward outputs. What a forward kind adds to the blend is one type, its output (V::Out); blend_hit, lane_pass,
+// cor_ray and PixelSums name no kind and call it. Sums, zero: the floats it adds to a pixel's sums and, in a forward
+// frame, to the ray (CorRay::k), each a sum of x w over the blended hits. blend: a blended hit's share on the blending
+// lanes, w its weight, z its view depth, c its place in stage stg (wave-uniform in blend_hit, the lane's own in
+// lane_pass). each, each_at: every float in a fixed order, unrolled, alone or with its entry for pixel pix of the
+// output's own row-major image (never packed). rows, row_pieces, own_table: the table staged beside the records
+// (stage_issue), a row's 16-B pieces, and whether it is the output's own, staged in every frame, or the scene's SH rows.
+struct ColourOut {  // colour alone: plain, stats and every gradient kind, whose ray holds its sink's payload in k
+    struct Sums {};
+    static constexpr uint32_t row_pieces = 12; static constexpr bool own_table = false;
+    __device__ GSRT_INLINE static const float* rows() { return kargs().a.sh; }
+    template <class K> __device__ GSRT_INLINE static void zero(K&) {}
+    template <class K> __device__ GSRT_INLINE static void blend(K&, float, float, const Stage*, uint32_t) {}
+    template <class Op> __device__ GSRT_INLINE static void each(Sums&, Op) {}
+    template <class Op> __device__ GSRT_INLINE static void each_at(Sums&, size_t, Op) {}
+};
+// depth (GSRT_FLAG_DEPTH): colour's table, and D, the sum of z w (the expected view depth, premultiplied), to depth_out.
+// z is already in a register from the caller's read of the record (a read of its own measured 1.5 % on the depth kernel)
+struct DepthOut : ColourOut {
+    struct Sums { float D; };
+    __device__ GSRT_INLINE static void zero(Sums& s) { s.D = 0.0f; }
+    __device__ GSRT_INLINE static void blend(Sums& k, float w, float z, const Stage*, uint32_t) { k.D = fmaf(z, w, k.D); }
+    template <class Op> __device__ GSRT_INLINE static void each(Sums& s, Op op) { op(s.D); }
+    template <class Op>
+    __device__ GSRT_INLINE static void each_at(Sums& s, size_t pix, Op op) { op(s.D, kargs().a.depth_out + pix); }
+};
+// feat (GSRT_FLAG_FEATURES): F, the sums of f_k w over the candidate's staged row of the feature table (in blend_hit a
+// wave-uniform address: four broadcast ds_read_b128); to feat_out, feat_channels floats per pixel (a uniform guard)
+struct FeatureOut {
+    struct Sums { float F[16]; };
+    static constexpr uint32_t row_pieces = 4; static constexpr bool own_table = true;
+    __device__ GSRT_INLINE static const float* rows() { return kargs().a.feat_rows; }
+    __device__ GSRT_INLINE static void zero(Sums& s) { each(s, [](float& v) { v = 0.0f; }); }  // not Sums{}: DESIGN.md 3
+    __device__ GSRT_INLINE static void blend(Sums& k, float w, float, const Stage* stg, uint32_t c) {
+        const float4* frow = reinterpret_cast<const float4*>(&stg->sh[0][0][0]) + 4 * c;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 f = frow[q];
+            k.F[4 * q + 0] = fmaf(f.x, w, k.F[4 * q + 0]);
+            k.F[4 * q + 1] = fmaf(f.y, w, k.F[4 * q + 1]);
+            k.F[4 * q + 2] = fmaf(f.z, w, k.F[4 * q + 2]);
+            k.F[4 * q + 3] = fmaf(f.w, w, k.F[4 * q + 3]);
+        }
+    }
+    template <class Op> __device__ GSRT_INLINE static void each(Sums& s, Op op) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) op(s.F[q]);
+    }
+    template <class Op> __device__ GSRT_INLINE static void each_at(Sums& s, size_t pix, Op op) {
+        const uint32_t C = kargs().a.feat_channels;
+        float* of = kargs().a.feat_out + pix * C;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) if ((uint32_t)q < C) op(s.F[q], of + q);
+    }
 };
 
 // ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
 // with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
 // or a gradient frame of the kind RenderSync::grad_kind names (the sinks above). SH: the scene's SH-3 rows are blended;
 // LUT: the ExpLUT instead of the exact exponential. Twenty-four kernels: {plain, stats, depth, opgrad} x SH x LUT,
-// {feat, grad, shgrad} x LUT and splatgrad x SH (never with the LUT, frame_refusal), named by cor_kernel and nowhere else. What a forward kind adds sits under if constexpr on
-// these members, what a gradient kind adds in its sink: the other kinds' code does not change. The RGBA of feat and
-// grad is the no-SH frame's.
-// A new gradient kind supplies: a CorKind, its sink and line in Grad, a line in `waves`, a case in cor_kernel, launch_cor.
+// {feat, grad, shgrad} x LUT and splatgrad x SH (never with the LUT, frame_refusal), named by cor_kernel and nowhere
+// else. What a forward kind adds sits in its output type, what a gradient kind adds in its sink: the other kinds' code
+// does not change, and the shading loop names no kind but stats, another loop body and no output. The RGBA of feat and
+// grad is the no-SH frame's. A new forward kind supplies: a CorKind, its output type and line in Out, a line in `waves`,
+// a case in cor_kernel, launch_cor. A new gradient kind: a CorKind, its sink and line in Grad, and the same three.
 enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad, splatgrad };
 // waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
 // spill to scratch)
@@ -1190,9 +1237,6 @@ constexpr uint32_t kOpGradWaves = GSRT_OPGRAD_WAVES;
 // and for the two splatgrad kernels, likewise (GSRT_SPLATGRAD_WAVES): a stage's 24 terms per lane
 // beside opgrad's registers, 155 VGPRs with SH rows and 103 without, no scratch at 3; at 4 the SH kernel spills 24 VGPRs
 constexpr uint32_t kSplatGradWaves = GSRT_SPLATGRAD_WAVES;
-struct NoPayload {};
-struct DepthPayload { float D; };      // sum of z w over the blended hits (expected view depth, premultiplied)
-struct ChannelPayload { float F[16]; };  // feat: sum of f_k w over the blended hits per channel
 template <CorKind K, bool SH, bool LUT>
 struct CorVariant {
     static constexpr bool sh = SH, lut = LUT;
@@ -1200,8 +1244,8 @@ struct CorVariant {
     static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad, shgrad = K == CorKind::shgrad;
     static constexpr bool opgrad = K == CorKind::opgrad, splatgrad = K == CorKind::splatgrad;
     static constexpr bool resweep = opgrad || splatgrad;  // every pass is shaded twice: finals, then the sink's terms
+    static constexpr bool grey = feat || grad;  // colour 1: the blend keeps C[0] alone, PixelSums::take replicates it
     static_assert(!splatgrad || !LUT, "under the LUT d(alpha) / dg is a segment's slope, not -alpha");
-    static_assert(!(feat || grad) || !SH, "feature and gradient frames evaluate no SH");
     static_assert(!shgrad || SH, "an SH gradient frame blends the SH rows");
     // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
     // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
@@ -1210,24 +1254,20 @@ struct CorVariant {
     static constexpr uint32_t waves =
         splatgrad ? kSplatGradWaves : opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
         : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
-    // stage geometry (stage_issue): 16-B pieces of a row of the staged table (SH rows: 12, feature rows: 4), pieces per
-    // stage, and DMA instructions per stage (one piece per lane each)
-    static constexpr uint32_t row_pieces = feat ? 4u : 12u;
-    static constexpr uint32_t stage_pieces = SH ? 16 * kGroup : (feat ? 8 * kGroup : 4 * kGroup);
+    // a gradient kind's sink, a forward kind's output, and which of the two holds the ray's own state (CorRay::k)
+    using Grad = std::conditional_t<grad, FeatureGrad, std::conditional_t<shgrad, ShGrad, std::conditional_t<
+                     opgrad, OpacityGrad, std::conditional_t<splatgrad, SplatGrad, NoGrad>>>>;
+    using Out = std::conditional_t<depth, DepthOut, std::conditional_t<feat, FeatureOut, ColourOut>>;
+    static constexpr bool forward = std::is_same_v<Grad, NoGrad>;
+    using RayPayload = std::conditional_t<forward, typename Out::Sums, typename Grad::Payload>;
+    // stage geometry (stage_issue): a staged row's 16-B pieces, pieces per stage (4 a record), DMA instructions per stage
+    static constexpr uint32_t row_pieces = Out::row_pieces;
+    static constexpr uint32_t stage_pieces = (4 + (SH || Out::own_table ? row_pieces : 0)) * kGroup;
     static constexpr uint32_t stage_ops = (stage_pieces + 63) / 64;
-    // a gradient kind's sink; what a forward kind adds to a pixel's sums (PixelSums), empty where it adds nothing; and
-    // what the kind adds to a ray's state (CorRay): those sums, or its sink's payload
-    using Grad = std::conditional_t<grad, FeatureGrad, std::conditional_t<shgrad, ShGrad,
-                                    std::conditional_t<opgrad, OpacityGrad,
-                                                       std::conditional_t<splatgrad, SplatGrad, NoGrad>>>>;
-    using SumPayload = std::conditional_t<depth, DepthPayload, std::conditional_t<feat, ChannelPayload, NoPayload>>;
-    using RayPayload = std::conditional_t<std::is_same_v<Grad, NoGrad>, SumPayload, typename Grad::Payload>;
+    static_assert(!(grad || Out::own_table) || !SH, "no SH in feature gradient frames, nor beside an output's own table");
 };
-// z: the candidate's view depth (SplatRec::depth), already in a register from shade_stage's read of the record (a read
-// of its own from the stage here measured 1.5 % on the depth kernel). depth: the blend's own w also weighs it into ray.k.D
-// feat: w weighs the 16 floats of the candidate's staged feature row (feat_row) into ray.k.F, and the colour (1, as
-// without SH) into C[0] alone: r = g = b, replicated once the ray is done (PixelSums::take); grad's colour is feat's.
-// grad: the stage's share of the frame's sink (Share of V::Grad, or of NoGrad), told of the hit where some lane blends
+// z: the candidate's view depth (SplatRec::depth), for the frame's output (V::Out). A grey kind's colour (1, as without
+// SH) goes into C[0] alone. grad: the stage's share of the frame's sink, told of the hit where some lane blends
 template <class V, class Sh>
 __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z, float alpha, uint64_t contrib,
                                           CorRay<V>& ray, Sh& grad) {
@@ -1242,24 +1282,11 @@ __device__ GSRT_INLINE uint64_t blend_hit(const Stage* stg, uint32_t c, float z,
         if (lane_of(blend)) {
             const float w = alpha * ray.T;
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
-            if constexpr (!V::feat && !V::grad) {
+            if constexpr (!V::grey) {
                 ray.C[1] = fmaf(col[1], w, ray.C[1]);
                 ray.C[2] = fmaf(col[2], w, ray.C[2]);
             }
-            if constexpr (V::depth) ray.k.D = fmaf(z, w, ray.k.D);
-            if constexpr (V::feat) {
-                // the row's address is wave-uniform: four broadcast ds_read_b128, under the lane mask (only the
-                // blending lanes use the values)
-                const float4* frow = feat_row(stg, c);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 f = frow[q];
-                    ray.k.F[4 * q + 0] = fmaf(f.x, w, ray.k.F[4 * q + 0]);
-                    ray.k.F[4 * q + 1] = fmaf(f.y, w, ray.k.F[4 * q + 1]);
-                    ray.k.F[4 * q + 2] = fmaf(f.z, w, ray.k.F[4 * q + 2]);
-                    ray.k.F[4 * q + 3] = fmaf(f.w, w, ray.k.F[4 * q + 3]);
-                }
-            }
+            V::Out::blend(ray.k, w, z, stg, c);
             grad.hit_lane(c, alpha, col, ray);  // the colour after this hit, ray.T still T_i
             ray.T = tn;
             if (V::stats) ++ray.blended;
@@ -1346,7 +1373,7 @@ __device__ GSRT_INLINE bool lane_pass(const Stage* stg, const uint64_t (&at)[kGr
             ray.C[0] = fmaf(col[0], w, ray.C[0]);
             ray.C[1] = fmaf(col[1], w, ray.C[1]);
             ray.C[2] = fmaf(col[2], w, ray.C[2]);
-            if constexpr (V::depth) ray.k.D = fmaf(q0.w, w, ray.k.D);
+            V::Out::blend(ray.k, w, q0.w, stg, cj);
             ray.T = tn;
         }
     }
@@ -2035,36 +2062,19 @@ struct CorTile {
     }
 };
 
-// What a pixel outputs, summed over its samples: the colour and what the kind adds (depth: D, feat: 16 channels).
-// each visits every float in a fixed order (rgba, depth, channels 0..15), unrolled: nothing is indexed dynamically.
+// What a pixel outputs, summed over its samples: the colour, then what the frame's output adds; each: in that fixed order
 template <class V>
 struct PixelSums {
     float rgba[4];
-    typename V::SumPayload k;
+    typename V::Out::Sums k;
     template <class Op>
     __device__ GSRT_INLINE void each(Op op) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) op(rgba[q]);
-        if constexpr (V::depth) op(k.D);
-        if constexpr (V::feat) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) op(k.F[q]);
-        }
+        V::Out::each(k, op);
     }
-    // the floats beyond the colour with their entries in the frame's other image, pixel pix of a row-major frame (a depth
-    // or feature frame is never packed): depth_out, or feat_channels floats per pixel of feat_out, and only those
-    // (a uniform guard)
-    template <class Op>
-    __device__ GSRT_INLINE void each_extra_at(size_t pix, Op op) {
-        if constexpr (V::depth) op(k.D, kargs().a.depth_out + pix);
-        if constexpr (V::feat) {
-            const uint32_t C = kargs().a.feat_channels;
-            float* of = kargs().a.feat_out + pix * C;
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if ((uint32_t)q < C) op(k.F[q], of + q);
-        }
-    }
+    template <class Op>  // the floats beyond the colour with their entries in the output's own image
+    __device__ GSRT_INLINE void each_extra_at(size_t pix, Op op) { V::Out::each_at(k, pix, op); }
     // every float with its entry in its own image; colour: the pixel's four floats
     template <class Op>
     __device__ GSRT_INLINE void each_at(float* colour, size_t pix, Op op) {
@@ -2072,15 +2082,10 @@ struct PixelSums {
         for (int q = 0; q < 4; ++q) op(rgba[q], colour + q);
         each_extra_at(pix, op);
     }
-    // a finished pass's results (= 0 + x exactly, x >= +0). feat, grad: colour 1, the blend kept one channel (blend_hit)
+    // a finished pass's results (= 0 + x exactly, x >= +0). A grey kind's blend kept one channel (blend_hit)
     __device__ GSRT_INLINE void take(const CorRay<V>& ray) {
-        constexpr bool grey = V::feat || V::grad;
-        rgba[0] = ray.C[0]; rgba[1] = ray.C[grey ? 0 : 1]; rgba[2] = ray.C[grey ? 0 : 2]; rgba[3] = 1.0f - ray.T;
-        if constexpr (V::depth) k.D = ray.k.D;
-        if constexpr (V::feat) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) k.F[q] = ray.k.F[q];
-        }
+        rgba[0] = ray.C[0]; rgba[1] = ray.C[V::grey ? 0 : 1]; rgba[2] = ray.C[V::grey ? 0 : 2]; rgba[3] = 1.0f - ray.T;
+        if constexpr (V::forward) k = ray.k;
     }
 };
 
@@ -2106,11 +2111,7 @@ __device__ GSRT_INLINE CorRay<V> cor_ray(const CorTile::Pixel& p, uint32_t S, ui
     }
     ray.T = 1.0f;
     ray.C[0] = ray.C[1] = ray.C[2] = 0.0f;
-    if constexpr (V::depth) ray.k.D = 0.0f;
-    if constexpr (V::feat) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) ray.k.F[q] = 0.0f;
-    }
+    V::Out::zero(ray.k);
     V::Grad::load(ray.k, p.x, p.y, p.valid, S * passes);  // a gradient kind: the pixel's upstream gradient
     ray.active = p.valid;
     if (!p.valid) ray.pxs = __builtin_nanf("");  // see blend_hit
@@ -2222,7 +2223,7 @@ void k_render_cor(const KArgs karg) {
     uint32_t* const ids = L.l.ids;
     uint32_t* const lhdr = L.l.hdr;
     const SplatRec* const recs = kargs().a.recs;  // stage DMA sources, read once (kargs() is not hoisted)
-    const float* const shp = V::feat ? kargs().a.feat_rows : kargs().a.sh;
+    const float* const shp = V::Out::rows();
     (void)karg;  // read through kargs()
     const uint32_t lane = lane_id();
 #ifdef GSRT_DIAG
@@ -2307,8 +2308,7 @@ void k_render_cor(const KArgs karg) {
 #endif
                 ++st_rounds;
                 if (cl.total > maxc) maxc = cl.total;
-                // a gradient kind's terms go to its sink (opgrad: in the second sweep; the first is the plain blend)
-                // a gradient kind's terms go to its sink; opgrad: in the second sweep, the first is the plain blend
+                // a gradient kind's terms go to its sink, in a resweep kind's second sweep: the first is the plain blend
                 const bool live = V::resweep && sweep == 0
                     ? shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, NoGrad{})
                     : shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, V::Grad::of_frame());
