@@ -22,6 +22,8 @@
 // --sh-grad FILE --sh-grad-out FILE (gsrt_render_sh_grad, a scene with SH rows: the RGBA frame's gradient W*H*4 in, n*48
 // laid out [gauss][coef][rgb] out), --opacity-grad FILE --opacity-grad-out FILE (gsrt_render_opacity_grad: W*H*4 in, n
 // out), --splat-grad FILE --splat-grad-out FILE (gsrt_render_splat_grad: W*H*4 in, n*8 out; the library refuses --lut).
+// --depth-grad FILE beside the --splat-grad pair (the depth image's gradient, W*H): gsrt_render_splat_depth_grad instead,
+// the same table out; without --splat-grad it is a usage error.
 // Their usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, a gradient run listed before
 // it, one option without the others, C outside 1..16.
 #include <chrono>
@@ -47,7 +49,7 @@ struct Options {
     int device = 0;
     float fov = 0.0f;  // 0: scene default
     std::string camera, out, binary, text, ply, depth, features, features_out, feature_grad, feature_grad_out;
-    std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out, splat_grad, splat_grad_out;
+    std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out, splat_grad, splat_grad_out, depth_grad;
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
 };
@@ -92,7 +94,7 @@ bool given(const Options& o, const GradOption& g) { return !(o.*g.in).empty() ||
                  "                   [--feature-grad FILE --feature-channels C --feature-grad-out FILE]\n"
                  "                   [--sh-grad FILE --sh-grad-out FILE]\n"
                  "                   [--opacity-grad FILE --opacity-grad-out FILE]\n"
-                 "                   [--splat-grad FILE --splat-grad-out FILE]\n");
+                 "                   [--splat-grad FILE --splat-grad-out FILE] [--depth-grad FILE]\n");
     std::exit(2);
 }
 
@@ -144,6 +146,7 @@ Options parse(int argc, char** argv) {
         else if (a == "--opacity-grad-out") o.opacity_grad_out = val();
         else if (a == "--splat-grad") o.splat_grad = val();
         else if (a == "--splat-grad-out") o.splat_grad_out = val();
+        else if (a == "--depth-grad") o.depth_grad = val();
         else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
@@ -154,6 +157,7 @@ Options parse(int argc, char** argv) {
     if (!o.width || !o.height) usage("empty frame");
     if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
     if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
+    if (!o.depth_grad.empty() && o.splat_grad.empty()) usage("--depth-grad goes with --splat-grad and --splat-grad-out");
     for (const GradOption* g = std::end(kGradOptions); g-- != kGradOptions;) {  // newest first
         if (!given(o, *g)) continue;
         const std::string n = g->name;
@@ -301,7 +305,21 @@ int main(int argc, char** argv) {
                          grad->image_channels ? "4" : "channels");
             rc = 1;
         }
-        if (!rc) rc = check(grad->call(scene, &ubo, mode, gimg.data(), C, gtab.data()), ctx, "render");
+        std::vector<float> gdepth(o.depth_grad.empty() ? 0 : (size_t)o.width * o.height);  // with --splat-grad (parse)
+        if (!rc && !gdepth.empty()) {
+            f = std::fopen(o.depth_grad.c_str(), "rb");
+            const bool all = f && std::fread(gdepth.data(), sizeof(float), gdepth.size(), f) == gdepth.size() &&
+                             std::fgetc(f) == EOF;
+            if (f) std::fclose(f);
+            if (!all) {
+                std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels)\n", o.depth_grad.c_str(), gdepth.size());
+                rc = 1;
+            }
+        }
+        if (!rc && !gdepth.empty())
+            rc = check(gsrt_render_splat_depth_grad(scene, &ubo, mode, 0, gimg.data(), gdepth.data(), gtab.data(), 0), ctx,
+                       "render");
+        else if (!rc) rc = check(grad->call(scene, &ubo, mode, gimg.data(), C, gtab.data()), ctx, "render");
         if (!rc) {
             f = std::fopen(out.c_str(), "wb");
             const bool ok = f && std::fwrite(gtab.data(), sizeof(float), gtab.size(), f) == gtab.size();

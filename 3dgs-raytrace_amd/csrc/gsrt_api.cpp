@@ -804,6 +804,7 @@ struct GradFrame {
     float* d_rows;       // the table the render kernel adds to: the zeroed ctx rows, or the caller's table (kFrameFlags)
     uint32_t channels;
     GradKind kind;
+    const float* d_in2;  // a kind's second image (FrameFlag::image2_channels: the depth image's gradient), or nullptr
 };
 
 // a frame's device outputs: a caller fills the ones its frame has, the others stay nullptr
@@ -877,6 +878,7 @@ static gsrt_status render_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mo
             rsy.grad_rows = out.grad->d_rows;
             rsy.grad_channels = out.grad->channels;
             rsy.grad_kind = out.grad->kind;
+            rsy.grad_depth_in = out.grad->d_in2;
         }
         s = gsrt::launch_render(sc, *ubo, plan, ctx->d_fb, d_rs, d_rs && !depth && !feat && !grad ? nullptr : &rsy);
         if (s != GSRT_OK) return s;
@@ -990,23 +992,26 @@ const float* gsrt_feature_buffer(gsrt_ctx* ctx) { return ctx && ctx->last_feat ?
 // render kernel adds every blended hit's terms to them and a small kernel compacts them into the caller's table (sh:
 // transposed into [gauss][coef][rgb]). Without (opacity: n floats in API order; splat: n rows of 8) the render kernel adds to the caller's
 // device table itself, zeroed first unless it accumulates, and nothing is compacted. All in order on the render stream: the
-// kinds share the ctx's buffers.
+// kinds share the ctx's buffers. A kind with a second image (splat_depth: the depth image's gradient) takes it as image2.
 static gsrt_status check_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, const gsrt::FrameFlag& F,
-                                   const float* grad_image, uint32_t channels, const float* grad_table) {
+                                   const float* grad_image, uint32_t channels, const float* grad_table,
+                                   const float* grad_image2) {
     if (!sc || !ubo) return GSRT_E_ARG;
     const std::string name = std::string(F.name) + ": ";
     if (!F.image_channels && (channels < 1 || channels > GSRT_MAX_FEATURES))
         return fail(sc->ctx, GSRT_E_ARG, name + "channels must be 1..GSRT_MAX_FEATURES");
     if (!grad_image) return fail(sc->ctx, GSRT_E_ARG, name + "grad_image is NULL");
+    if (F.image2_channels && !grad_image2) return fail(sc->ctx, GSRT_E_ARG, name + "grad_depth is NULL");
     if (!grad_table) return fail(sc->ctx, GSRT_E_ARG, name + "grad_table is NULL");
     return check_render_args(sc, ubo, mode, F.kind);
 }
 
 static gsrt_status grad_frame_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, GradKind kind,
-                                    const float* d_image, uint32_t channels, float* d_table, int accumulate) {
+                                    const float* d_image, uint32_t channels, float* d_table, int accumulate,
+                                    const float* d_image2 = nullptr) {
     const gsrt::FrameFlag& F = gsrt::grad_flag(kind);
     mode |= F.bit;
-    gsrt_status s = check_grad_args(sc, ubo, mode, F, d_image, channels, d_table);
+    gsrt_status s = check_grad_args(sc, ubo, mode, F, d_image, channels, d_table, d_image2);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
@@ -1021,7 +1026,7 @@ static gsrt_status grad_frame_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_
     } else if (!accumulate && sc->n) {
         GSRT_HIP(ctx, hipMemsetAsync(d_table, 0, sizeof(float) * F.table_floats * sc->n, ctx->stream));
     }
-    const GradFrame gf{d_image, F.row_floats ? ctx->d_grad_rows : d_table, channels, kind};
+    const GradFrame gf{d_image, F.row_floats ? ctx->d_grad_rows : d_table, channels, kind, d_image2};
     FrameOut out;
     out.grad = &gf;
     s = render_async(sc, ubo, mode, k, out);
@@ -1034,20 +1039,24 @@ static gsrt_status grad_frame_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_
 
 // a host image and a host table go through the gradient frames' buffers of the ctx (d_grad_in, d_grad_out)
 static gsrt_status grad_frame_blocking(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, GradKind kind,
-                                       const float* grad_image, uint32_t channels, float* grad_table, int accumulate) {
+                                       const float* grad_image, uint32_t channels, float* grad_table, int accumulate,
+                                       const float* grad_image2 = nullptr) {
     const gsrt::FrameFlag& F = gsrt::grad_flag(kind);
     mode |= F.bit;
-    gsrt_status s = check_grad_args(sc, ubo, mode, F, grad_image, channels, grad_table);
+    gsrt_status s = check_grad_args(sc, ubo, mode, F, grad_image, channels, grad_table, grad_image2);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
     const bool in_dev = is_device_ptr(grad_image), out_dev = is_device_ptr(grad_table);
+    const bool in2_host = grad_image2 && !is_device_ptr(grad_image2);  // its device copy follows the first image's
     if (accumulate && !out_dev) return fail(ctx, GSRT_E_ARG, std::string(F.name) + ": accumulate needs a device grad_table");
     const size_t in_floats = (size_t)ubo->width * ubo->height * (F.image_channels ? F.image_channels : channels);
+    const size_t in2_floats = (size_t)ubo->width * ubo->height * F.image2_channels;
+    const size_t in_need = (in_dev ? 0 : in_floats) + (in2_host ? in2_floats : 0);
     const size_t out_floats = (size_t)sc->n * (F.table_floats ? F.table_floats : channels);
-    if (!in_dev && (ctx->grad_in_floats < in_floats || !ctx->d_grad_in)) {
+    if (in_need && (ctx->grad_in_floats < in_need || !ctx->d_grad_in)) {
         if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
-        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_floats)) != GSRT_OK) return s;
+        if ((s = grow(ctx, &ctx->d_grad_in, &ctx->grad_in_floats, in_need)) != GSRT_OK) return s;
     }
     if (!out_dev && (ctx->grad_out_floats < out_floats || !ctx->d_grad_out)) {
         if ((s = gsrt::sync_all(ctx)) != GSRT_OK) return s;
@@ -1055,8 +1064,11 @@ static gsrt_status grad_frame_blocking(gsrt_scene* sc, const gsrt_ubo* ubo, uint
     }
     if (!in_dev)
         GSRT_HIP(ctx, hipMemcpyAsync(ctx->d_grad_in, grad_image, sizeof(float) * in_floats, hipMemcpyHostToDevice, ctx->stream));
+    float* const d_in2 = in2_host ? ctx->d_grad_in + (in_dev ? 0 : in_floats) : nullptr;
+    if (in2_host)
+        GSRT_HIP(ctx, hipMemcpyAsync(d_in2, grad_image2, sizeof(float) * in2_floats, hipMemcpyHostToDevice, ctx->stream));
     s = grad_frame_async(sc, ubo, mode, k, kind, in_dev ? grad_image : ctx->d_grad_in, channels,
-                         out_dev ? grad_table : ctx->d_grad_out, accumulate);
+                         out_dev ? grad_table : ctx->d_grad_out, accumulate, in2_host ? d_in2 : grad_image2);
     return finish_blocking(ctx, s, {{!out_dev && out_floats ? grad_table : nullptr, ctx->d_grad_out,
                                      sizeof(float) * out_floats, "gradient table download failed"}});
 }
@@ -1094,14 +1106,24 @@ gsrt_status gsrt_render_splat_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t
                                    float* grad_splat, int accumulate) {
     return grad_frame_blocking(sc, ubo, mode, k, GradKind::splat, grad_image, 0, grad_splat, accumulate);
 }
+gsrt_status gsrt_render_splat_depth_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                               const float* d_grad_image, const float* d_grad_depth, float* d_grad_splat,
+                                               int accumulate) {
+    return grad_frame_async(sc, ubo, mode, k, GradKind::splat_depth, d_grad_image, 0, d_grad_splat, accumulate, d_grad_depth);
+}
+gsrt_status gsrt_render_splat_depth_grad(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                         const float* grad_image, const float* grad_depth, float* grad_splat,
+                                         int accumulate) {
+    return grad_frame_blocking(sc, ubo, mode, k, GradKind::splat_depth, grad_image, 0, grad_splat, accumulate, grad_depth);
+}
 
 // The projection's backward (k_splat_grad_to_model) on the render stream, behind the splat gradient frame that wrote the
 // rows. It reads the scene's current parameter array there as a REF frame's projection does: after the update copies
 // the stream has not seen, and an update that retires the array waits for it (serial_pending, serial_reads).
 static gsrt_status check_model_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, const float* rows, const float* gc,
-                                         const float* gv) {
+                                         const float* gv, bool depth) {
     if (!sc || !ubo) return GSRT_E_ARG;
-    const char* name = "gsrt_splat_grad_to_model: ";
+    const char* name = depth ? "gsrt_splat_depth_grad_to_model: " : "gsrt_splat_grad_to_model: ";
     if (!rows) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_splat is NULL");
     if (!gc) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_center is NULL");
     if (!gv) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_cov is NULL");
@@ -1110,9 +1132,10 @@ static gsrt_status check_model_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, co
     return GSRT_OK;
 }
 
-gsrt_status gsrt_splat_grad_to_model_async(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_grad_splat,
-                                           float* d_grad_center, float* d_grad_cov, int accumulate) {
-    gsrt_status s = check_model_grad_args(sc, ubo, d_grad_splat, d_grad_center, d_grad_cov);
+// depth: the rows are gsrt_render_splat_depth_grad's and slot 6 is chained too (k_splat_grad_to_model<true>)
+static gsrt_status model_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_grad_splat, float* d_grad_center,
+                                    float* d_grad_cov, int accumulate, bool depth) {
+    gsrt_status s = check_model_grad_args(sc, ubo, d_grad_splat, d_grad_center, d_grad_cov, depth);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
@@ -1121,20 +1144,21 @@ gsrt_status gsrt_splat_grad_to_model_async(gsrt_scene* sc, const gsrt_ubo* ubo, 
     ctx->serial_pending = true;
     ctx->serial_reads = true;
     gsrt::launch_splat_grad_to_model(ctx->stream, sc->n, *ubo, sc->d_params, d_grad_splat, d_grad_center, d_grad_cov,
-                                     accumulate != 0);
+                                     accumulate != 0, depth);
     GSRT_HIP(ctx, hipGetLastError());
     return GSRT_OK;
 }
 
-gsrt_status gsrt_splat_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
-                                     float* grad_cov, int accumulate) {
-    gsrt_status s = check_model_grad_args(sc, ubo, grad_splat, grad_center, grad_cov);
+static gsrt_status model_grad_blocking(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
+                                       float* grad_cov, int accumulate, bool depth) {
+    gsrt_status s = check_model_grad_args(sc, ubo, grad_splat, grad_center, grad_cov, depth);
     if (s != GSRT_OK) return s;
     gsrt_ctx* ctx = sc->ctx;
     (void)hipSetDevice(ctx->device);
     const bool in_dev = is_device_ptr(grad_splat), c_dev = is_device_ptr(grad_center), v_dev = is_device_ptr(grad_cov);
     if (accumulate && (!c_dev || !v_dev))
-        return fail(ctx, GSRT_E_ARG, "gsrt_splat_grad_to_model: accumulate needs device tables");
+        return fail(ctx, GSRT_E_ARG, std::string(depth ? "gsrt_splat_depth_grad_to_model" : "gsrt_splat_grad_to_model") +
+                                         ": accumulate needs device tables");
     // the host tables' device copies: one block, rows | centres | covariances
     const size_t n = sc->n, nn = n ? n : 1;
     float* tmp = nullptr;
@@ -1144,12 +1168,29 @@ gsrt_status gsrt_splat_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, const 
     if (!in_dev && n && hipMemcpyAsync(d_rows, grad_splat, sizeof(float) * 8 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         s = fail(ctx, GSRT_E_DEVICE, "splat gradient upload failed");
     if (s == GSRT_OK)
-        s = gsrt_splat_grad_to_model_async(sc, ubo, in_dev ? grad_splat : d_rows, c_dev ? grad_center : d_c,
-                                           v_dev ? grad_cov : d_v, accumulate);
+        s = model_grad_async(sc, ubo, in_dev ? grad_splat : d_rows, c_dev ? grad_center : d_c, v_dev ? grad_cov : d_v,
+                             accumulate, depth);
     return finish_blocking(ctx, s, {{!c_dev && n ? grad_center : nullptr, d_c, sizeof(float) * 3 * n,
                                      "centre gradient download failed"},
                                     {!v_dev && n ? grad_cov : nullptr, d_v, sizeof(float) * 6 * n,
                                      "covariance gradient download failed"}}, &tmpv);
+}
+
+gsrt_status gsrt_splat_grad_to_model_async(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_grad_splat,
+                                           float* d_grad_center, float* d_grad_cov, int accumulate) {
+    return model_grad_async(sc, ubo, d_grad_splat, d_grad_center, d_grad_cov, accumulate, false);
+}
+gsrt_status gsrt_splat_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
+                                     float* grad_cov, int accumulate) {
+    return model_grad_blocking(sc, ubo, grad_splat, grad_center, grad_cov, accumulate, false);
+}
+gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_grad_splat,
+                                                 float* d_grad_center, float* d_grad_cov, int accumulate) {
+    return model_grad_async(sc, ubo, d_grad_splat, d_grad_center, d_grad_cov, accumulate, true);
+}
+gsrt_status gsrt_splat_depth_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
+                                           float* grad_cov, int accumulate) {
+    return model_grad_blocking(sc, ubo, grad_splat, grad_center, grad_cov, accumulate, true);
 }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,

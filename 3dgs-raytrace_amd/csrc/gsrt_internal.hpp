@@ -306,7 +306,7 @@ void launch_mesh_thit(hipStream_t s, const gsrt_ubo& ubo, const gsrt_scene* sc, 
 // ---- frame kinds on the host. A whole COR frame may carry one second output or be one gradient frame; each is a flag of
 // the mode word and one row here, in the order they were introduced. Everything the host does per kind reads the row: the
 // refusals (frame_refusal, gsrt_plan.cpp; gsrt_comm.cpp), the allowed mode bits, the gradient entry points (gsrt_api.cpp).
-enum class GradKind : uint32_t { none, feature, sh, opacity, splat };  // which gradient frame (none: the caller is no gradient call)
+enum class GradKind : uint32_t { none, feature, sh, opacity, splat, splat_depth };  // which gradient frame (none: the caller is no gradient call)
 struct FrameFlag {
     uint32_t bit;
     const char* name;         // as the messages spell it
@@ -317,6 +317,7 @@ struct FrameFlag {
     uint32_t table_floats;    // the caller's table, floats per Gaussian; 0: the caller's `channels`
     bool needs_sh;            // the scene must have SH rows
     bool no_lut;              // refused with GSRT_FLAG_LUT (its derivative is of the exact exponential)
+    uint32_t image2_channels = 0;  // a second gradient image's channels (the depth image's); 0: the kind has none
 };
 constexpr FrameFlag kFrameFlags[] = {
     {GSRT_FLAG_DEPTH, "GSRT_FLAG_DEPTH", GradKind::none, nullptr, 0, 0, 0, false, false},
@@ -325,6 +326,8 @@ constexpr FrameFlag kFrameFlags[] = {
     {GSRT_FLAG_SH_GRAD, "GSRT_FLAG_SH_GRAD", GradKind::sh, "gsrt_render_sh_grad", 48, 4, 48, true, false},
     {GSRT_FLAG_OPACITY_GRAD, "GSRT_FLAG_OPACITY_GRAD", GradKind::opacity, "gsrt_render_opacity_grad", 0, 4, 1, false, false},
     {GSRT_FLAG_SPLAT_GRAD, "GSRT_FLAG_SPLAT_GRAD", GradKind::splat, "gsrt_render_splat_grad", 0, 4, 8, false, true},
+    {GSRT_FLAG_SPLAT_DEPTH_GRAD, "GSRT_FLAG_SPLAT_DEPTH_GRAD", GradKind::splat_depth, "gsrt_render_splat_depth_grad", 0, 4, 8,
+     false, true, 1},
 };
 constexpr uint32_t frame_flag_bits() {  // every row's bit (the allowed mode bits beside the low byte, LUT and STATS)
     uint32_t m = 0;
@@ -409,10 +412,12 @@ struct RenderSync {
     float* feat = nullptr;
     // a gradient frame (likewise; grad_kind says which, kFrameFlags): the upstream gradient image, W x H x grad_channels
     // floats, and the table the frame adds to, n rows of the kind's row width (feature 16, sh 48 floats, zeroed ctx rows;
-    // opacity: the caller's own device table, n floats; splat: likewise, n rows of 8 floats); or nullptr
+    // opacity: the caller's own device table, n floats; splat and splat_depth: likewise, n rows of 8 floats); or nullptr.
+    // grad_depth_in: a splat_depth frame's second image, the depth image's upstream gradient, W x H floats
     const float* grad_in = nullptr;
     float* grad_rows = nullptr;
     uint32_t grad_channels = 0;
+    const float* grad_depth_in = nullptr;
     GradKind grad_kind = GradKind::none;
 };
 gsrt_status launch_render(gsrt_scene* sc, const gsrt_ubo& ubo, const RenderPlan& plan, float* d_rgba,
@@ -446,9 +451,10 @@ void launch_sh_rows(hipStream_t s, float* rows, const float* src, uint32_t n);
 // SH gradient rows (gsrt_scene.hip): dst[g][coef][rgb] = rows[g][rgb][coef], or += when accumulate
 void launch_sh_grad_compact(hipStream_t s, float* dst, const float* rows, uint32_t n, bool accumulate);
 // the COR projection's backward (gsrt_scene.hip): splat rows (n x 8, gsrt_render_splat_grad) to the gradients of the
-// centres (n x 3) and the cov3d entries (n x 6), written or added to
+// centres (n x 3) and the cov3d entries (n x 6), written or added to; depth: the rows are gsrt_render_splat_depth_grad's
+// and slot 6 (dL/d view depth) goes to the centre as well
 void launch_splat_grad_to_model(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params,
-                                const float* rows, float* grad_center, float* grad_cov, bool accumulate);
+                                const float* rows, float* grad_center, float* grad_cov, bool accumulate, bool depth = false);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into
 inline float* framebuffer_of(gsrt_ctx* ctx) { return ctx->fb_view ? ctx->fb_view : ctx->d_fb; }
 // the prep stream must not overtake what is on ctx->stream now (scene upload/update, BVH build/refit)

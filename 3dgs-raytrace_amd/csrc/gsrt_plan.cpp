@@ -258,9 +258,9 @@ Refusal frame_refusal(uint32_t mode, GradKind caller, uint32_t samples, const Sc
 
 }  // namespace gsrt
 
-extern "C" gsrt_status gsrt_debug_frame_refusal_kind(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built,
-                                                     uint32_t ntri, int has_features, int has_sh, char* msg, size_t cap) {
-    if (caller > (uint32_t)gsrt::GradKind::splat) return GSRT_E_ARG;
+extern "C" gsrt_status gsrt_debug_frame_refusal_any(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built,
+                                                    uint32_t ntri, int has_features, int has_sh, char* msg, size_t cap) {
+    if (caller > (uint32_t)gsrt::GradKind::splat_depth) return GSRT_E_ARG;
     const gsrt::Refusal r = gsrt::frame_refusal(mode, (gsrt::GradKind)caller, samples,
                                                 {bvh_built != 0, ntri, has_features != 0, has_sh != 0});
     if (msg && cap) {
@@ -269,6 +269,13 @@ extern "C" gsrt_status gsrt_debug_frame_refusal_kind(uint32_t mode, uint32_t cal
         msg[len] = '\0';
     }
     return r.status;
+}
+
+// the hook as it was before the callers past gsrt_render_splat_grad: those it refuses
+extern "C" gsrt_status gsrt_debug_frame_refusal_kind(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built,
+                                                     uint32_t ntri, int has_features, int has_sh, char* msg, size_t cap) {
+    if (caller > (uint32_t)gsrt::GradKind::splat) return GSRT_E_ARG;
+    return gsrt_debug_frame_refusal_any(mode, caller, samples, bvh_built, ntri, has_features, has_sh, msg, cap);
 }
 
 // the hook as it was before the callers past gsrt_render_opacity_grad: those it refuses

@@ -73,6 +73,9 @@ constexpr bool kGroupRegSort = GSRT_GROUP_REGSORT != 0;
 #ifndef GSRT_SPLATGRAD_WAVES
 #define GSRT_SPLATGRAD_WAVES 3
 #endif
+#ifndef GSRT_SPLATDEPTHGRAD_WAVES
+#define GSRT_SPLATDEPTHGRAD_WAVES 3
+#endif
 constexpr uint32_t kFront = 128;   // frontier entries per super-group
 
 
@@ -139,6 +142,9 @@ struct RenderArgs {
     const float* grad_in;
     float* grad_rows;
     uint32_t grad_channels;
+    // A splat-depth gradient frame (GSRT_FLAG_SPLAT_DEPTH_GRAD, k_render_cor splatdepthgrad), likewise appended: grad_in and
+    // grad_rows as for a splat gradient frame, and the upstream gradient of the depth image, width x height floats
+    const float* grad_depth_in;
 };
 
 #ifdef GSRT_WAVE_TIMES
@@ -1156,6 +1162,83 @@ struct SplatGrad : ResweepGrad {
     };
     __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{{ids, rows}}; }
 };
+// splatdepthgrad (GSRT_FLAG_SPLAT_DEPTH_GRAD): the backward of a depth frame, RGBA and D = sum z w together, to the splat
+// rows; the plain frame's RGBA. Depth is one more blended channel whose colour is the hit's own z, the staged record's
+// view depth (word 3: the value DepthOut::blend takes and the hits are keyed by). In the ray, beside ResweepGrad's
+// payload: Gd, the depth image's upstream gradient over ns, the first sweep's final D (finD) and the running D, which both
+// sweeps form as the depth frame does (fma(z, w, D) from +0). The first sweep runs with Finals, whose hit_lane adds to D
+// and nothing else; the second forms d as splatgrad does plus Gd (T z - (finD - Dafter) r), r the reciprocal of 1 - alpha
+// that dalpha divides by, and slots 0..5 from that d with splatgrad's own formulas. Slot 6 is dL/dz = w Gd on every
+// blending lane, clamped alpha or not: dD/dz = w does not pass through the clamp. The flush is SplatGrad's with seven
+// slots: 28 lanes add.
+struct SplatDepthGrad : ResweepGrad {
+    float* rows;
+    __device__ GSRT_INLINE static SplatDepthGrad of_frame() { return {{}, kargs().a.grad_rows}; }
+    struct Payload { float G[4], Gd, fin[4], finD, D; };
+    __device__ GSRT_INLINE static void load(Payload& g, uint32_t x, uint32_t y, bool valid, uint32_t ns) {
+        load_upstream(g.G, x, y, valid, ns);
+        const KArgs& K = kargs();
+        g.Gd = valid ? over_samples(K.a.grad_depth_in[(size_t)y * K.a.width + x], ns) : 0.0f;
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) g.fin[ch] = 0.0f;  // k_render_cor sets them, and finD, before the second sweep
+        g.finD = 0.0f, g.D = 0.0f;
+    }
+    // the first sweep's sink: the plain blend (no terms, never a flush) that also leaves the ray's D
+    struct Finals {
+        struct Share {
+            static constexpr uint32_t mask = 0;
+            const SplatRec* rec = nullptr;
+            __device__ GSRT_INLINE void candidate(float, float, const SplatRec* r) { rec = r; }
+            template <class Ray> __device__ GSRT_INLINE void hit(uint32_t, uint64_t, float, const float (&)[3], const Ray&) {}
+            template <class Ray> __device__ GSRT_INLINE void hit_lane(uint32_t, float alpha, const float (&)[3], Ray& ray) {
+                ray.k.D = fmaf(rec->depth, alpha * ray.T, ray.k.D);
+            }
+            __device__ GSRT_INLINE void flush() const {}
+        };
+        __device__ GSRT_INLINE Share share(const uint32_t*) const { return {}; }
+    };
+    static constexpr uint32_t kSlots = 7;  // of a row's 8 floats, the ones a frame adds to
+    struct Share : ShareOf<float[kGroup][kSlots]> {
+        const SplatRec* rec = nullptr;
+        __device__ GSRT_INLINE void candidate(float e_, float o, const SplatRec* r) { ShareOf::candidate(e_, o, r), rec = r; }
+        template <class Ray>
+        __device__ GSRT_INLINE void hit_lane(uint32_t c, float alpha, const float (&col)[3], Ray& ray) {
+            const float z = rec->depth;
+            const float w = alpha * ray.T;  // the blend's own weight
+            ray.k.D = fmaf(z, w, ray.k.D);  // Dafter_i
+            const float r = 1.0f / (1.0f - alpha);  // dalpha's own
+            const float d = dalpha(alpha, col, ray) + ray.k.Gd * (ray.T * z - (ray.k.finD - ray.k.D) * r);
+            const float4 q2 = reinterpret_cast<const float4*>(rec)[2];  // ppx, ppy, A/2, B
+            const float4 q3 = reinterpret_cast<const float4*>(rec)[3];  // C/2, ...
+            const float dx = ray.pxs - q2.x, dy = ray.pys - q2.y;       // the blending lanes' rays are live: no NaN
+            const float A = 2.0f * q2.z, B = q2.w, C = 2.0f * q3.x;
+            const float q = -(alpha * d);
+            t[c][0] = open ? q * -(A * dx + B * dy) : 0.0f;
+            t[c][1] = open ? q * -(B * dx + C * dy) : 0.0f;
+            t[c][2] = open ? q * (0.5f * (dx * dx)) : 0.0f;
+            t[c][3] = open ? q * (dx * dy) : 0.0f;
+            t[c][4] = open ? q * (0.5f * (dy * dy)) : 0.0f;
+            t[c][5] = open ? d * e : 0.0f;
+            t[c][6] = w * ray.k.Gd;  // only the blending lanes get here: every other lane keeps the share's +0
+        }
+        __device__ GSRT_INLINE void flush() const {
+            static_assert(kGroup == 4 && kSlots <= 8, "two candidates of eight slots per grad_row_sums");
+            flush_share<8>(ids, mask, [&] {
+                float lo[16], hi[16];
+#pragma unroll
+                for (uint32_t q = 0; q < 8; ++q) {
+                    lo[q] = q < kSlots ? t[0][q] : 0.0f, lo[8 + q] = q < kSlots ? t[1][q] : 0.0f;
+                    hi[q] = q < kSlots ? t[2][q] : 0.0f, hi[8 + q] = q < kSlots ? t[3][q] : 0.0f;
+                }
+                const float gs[kGroup] = {grad_row_sums(lo), grad_row_sums(hi), 0.0f, 0.0f};
+                return grad_stage_sums(gs);  // lanes 0..15: candidates 0, 1; lanes 16..31: candidates 2, 3
+            }, [&](uint32_t id, uint32_t q, float sum) {
+                if (q < kSlots) atomicAdd(rows + (size_t)id * 8u + q, sum);  // no-return global_atomic_add_f32
+            });
+        }
+    };
+    __device__ GSRT_INLINE Share share(const uint32_t* ids) const { return Share{{ids, rows}}; }
+};
 
 // ---- forward outputs. What a forward kind adds to the blend is one type, its output (V::Out); blend_hit, lane_pass,
 // cor_ray and PixelSums name no kind and call it. Sums, zero: the floats it adds to a pixel's sums and, in a forward
@@ -1216,13 +1299,13 @@ struct FeatureOut {
 // ---- the variants of k_render_cor. A frame is of one kind: plain colour, the counting pass (GSRT_FLAG_STATS), colour
 // with the expected view depth (GSRT_FLAG_DEPTH, RenderArgs::depth_out), a feature frame (GSRT_FLAG_FEATURES, feat_out)
 // or a gradient frame of the kind RenderSync::grad_kind names (the sinks above). SH: the scene's SH-3 rows are blended;
-// LUT: the ExpLUT instead of the exact exponential. Twenty-four kernels: {plain, stats, depth, opgrad} x SH x LUT,
-// {feat, grad, shgrad} x LUT and splatgrad x SH (never with the LUT, frame_refusal), named by cor_kernel and nowhere
+// LUT: the ExpLUT instead of the exact exponential. Twenty-six kernels: {plain, stats, depth, opgrad} x SH x LUT,
+// {feat, grad, shgrad} x LUT and {splatgrad, splatdepthgrad} x SH (never with the LUT, frame_refusal), named by cor_kernel and nowhere
 // else. What a forward kind adds sits in its output type, what a gradient kind adds in its sink: the other kinds' code
 // does not change, and the shading loop names no kind but stats, another loop body and no output. The RGBA of feat and
 // grad is the no-SH frame's. A new forward kind supplies: a CorKind, its output type and line in Out, a line in `waves`,
 // a case in cor_kernel, launch_cor. A new gradient kind: a CorKind, its sink and line in Grad, and the same three.
-enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad, splatgrad };
+enum class CorKind { plain, stats, depth, feat, grad, shgrad, opgrad, splatgrad, splatdepthgrad };
 // waves/SIMD asked for the two feat kernels, from the compiler's register report (109 VGPRs; at 5 and 6 waves they
 // spill to scratch)
 constexpr uint32_t kFeatWaves = 4;
@@ -1237,26 +1320,34 @@ constexpr uint32_t kOpGradWaves = GSRT_OPGRAD_WAVES;
 // and for the two splatgrad kernels, likewise (GSRT_SPLATGRAD_WAVES): a stage's 24 terms per lane
 // beside opgrad's registers, 155 VGPRs with SH rows and 103 without, no scratch at 3; at 4 the SH kernel spills 24 VGPRs
 constexpr uint32_t kSplatGradWaves = GSRT_SPLATGRAD_WAVES;
+// and for the two splatdepthgrad kernels, likewise (GSRT_SPLATDEPTHGRAD_WAVES): a stage's 28 terms per
+// lane and three more payload floats beside splatgrad's registers, 163 VGPRs with SH rows and 106 without, no scratch at
+// 3; at 4 the SH kernel spills 54 VGPRs (84 B of scratch a lane)
+constexpr uint32_t kSplatDepthGradWaves = GSRT_SPLATDEPTHGRAD_WAVES;
 template <CorKind K, bool SH, bool LUT>
 struct CorVariant {
     static constexpr bool sh = SH, lut = LUT;
     static constexpr bool stats = K == CorKind::stats, depth = K == CorKind::depth;
     static constexpr bool feat = K == CorKind::feat, grad = K == CorKind::grad, shgrad = K == CorKind::shgrad;
     static constexpr bool opgrad = K == CorKind::opgrad, splatgrad = K == CorKind::splatgrad;
-    static constexpr bool resweep = opgrad || splatgrad;  // every pass is shaded twice: finals, then the sink's terms
+    static constexpr bool splatdepthgrad = K == CorKind::splatdepthgrad;
+    static constexpr bool resweep = opgrad || splatgrad || splatdepthgrad;  // every pass is shaded twice: finals, then the sink's terms
     static constexpr bool grey = feat || grad;  // colour 1: the blend keeps C[0] alone, PixelSums::take replicates it
-    static_assert(!splatgrad || !LUT, "under the LUT d(alpha) / dg is a segment's slope, not -alpha");
+    static_assert(!(splatgrad || splatdepthgrad) || !LUT, "under the LUT d(alpha) / dg is a segment's slope, not -alpha");
     static_assert(!shgrad || SH, "an SH gradient frame blends the SH rows");
     // waves/SIMD targets (VGPR budget 512 / waves): the three 1-KB stage buffers + ids make 6 KB of LDS per wave, so
     // at most 26 waves per CU; 6 per SIMD (80 VGPRs) for both variants. The no-SH kernel asked for 8 before the
     // third stage buffer, and the compiler, unable to reach it, left it at 101 VGPRs = 4 waves (C4 -6 %, C5 -12 %).
     // The plain SH + LUT kernel asks for the 5 it had at a target of 4 (96 VGPRs) before the SH colours went per lane: left at 4 it takes 102.
     static constexpr uint32_t waves =
-        splatgrad ? kSplatGradWaves : opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
+        splatdepthgrad ? kSplatDepthGradWaves : splatgrad ? kSplatGradWaves : opgrad ? kOpGradWaves : shgrad ? kShGradWaves : grad ? kGradWaves : feat ? kFeatWaves
         : SH ? (LUT ? (K == CorKind::plain ? 5 : 4) : 6) : (LUT ? 5 : 6);
     // a gradient kind's sink, a forward kind's output, and which of the two holds the ray's own state (CorRay::k)
     using Grad = std::conditional_t<grad, FeatureGrad, std::conditional_t<shgrad, ShGrad, std::conditional_t<
-                     opgrad, OpacityGrad, std::conditional_t<splatgrad, SplatGrad, NoGrad>>>>;
+                     opgrad, OpacityGrad, std::conditional_t<splatgrad, SplatGrad, std::conditional_t<
+                     splatdepthgrad, SplatDepthGrad, NoGrad>>>>>;
+    // a resweep kind's first sweep: the plain blend, which for splatdepthgrad also leaves the ray's D
+    using Finals = std::conditional_t<splatdepthgrad, SplatDepthGrad::Finals, NoGrad>;
     using Out = std::conditional_t<depth, DepthOut, std::conditional_t<feat, FeatureOut, ColourOut>>;
     static constexpr bool forward = std::is_same_v<Grad, NoGrad>;
     using RayPayload = std::conditional_t<forward, typename Out::Sums, typename Grad::Payload>;
@@ -2278,7 +2369,7 @@ void k_render_cor(const KArgs karg) {
 #endif
     for (uint32_t pass = 0; pass < passes; ++pass) {
         CorRay<V> ray = cor_ray<V>(tile.pixel(), S, pass, passes);
-        // opgrad and splatgrad (V::resweep): two sweeps over the same rounds. The first is the plain blend and gives the pass its results and the
+        // opgrad, splatgrad and splatdepthgrad (V::resweep): two sweeps over the same rounds. The first is the plain blend and gives the pass its results and the
         // ray its finals; the second sets the ray up again, restarts the rounds from the tile's first list
         // (round_from_list issues it again: prefetched is false by then) and blends the same hits in the same order with
         // the same arithmetic, so that every test falls as it fell, now with the gradient terms (blend_hit)
@@ -2310,7 +2401,7 @@ void k_render_cor(const KArgs karg) {
                 if (cl.total > maxc) maxc = cl.total;
                 // a gradient kind's terms go to its sink, in a resweep kind's second sweep: the first is the plain blend
                 const bool live = V::resweep && sweep == 0
-                    ? shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, NoGrad{})
+                    ? shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, typename V::Finals{})
                     : shade_sorted<V>(ids, cl.count, &stA, &stB, &stC, lut_s, ray, recs, shp, V::Grad::of_frame());
 #ifdef GSRT_DIAG
                 diag_last = __builtin_amdgcn_s_memtime();
@@ -2324,9 +2415,12 @@ void k_render_cor(const KArgs karg) {
                 if (sweep == 0) {
                     sums.take(ray);  // once per pass, from the first sweep's values
                     const float fin[4] = {ray.C[0], ray.C[1], ray.C[2], ray.T};
+                    [[maybe_unused]] float finD = 0.0f;
+                    if constexpr (V::splatdepthgrad) finD = ray.k.D;
                     ray = cor_ray<V>(tile.pixel(), S, pass, passes);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) ray.k.fin[q] = fin[q];
+                    if constexpr (V::splatdepthgrad) ray.k.finD = finD;
                 }
             }
         } while (V::resweep && ++sweep < 2);
@@ -2858,6 +2952,7 @@ static void fill_args(KArgs& k, const gsrt_scene* sc, const gsrt_ubo& ubo, const
     A.grad_in = grad ? sync->grad_in : nullptr;
     A.grad_rows = grad ? sync->grad_rows : nullptr;
     A.grad_channels = grad ? sync->grad_channels : 0u;
+    A.grad_depth_in = grad ? sync->grad_depth_in : nullptr;
     A.ray_stats = f.stats ? ctx->d_ray_stats : nullptr;
     A.counters = ctx->d_counters;
     A.n = sc->n;
@@ -3178,7 +3273,7 @@ static CorLaunch cor_kernel_of(bool sh, bool lut) {
         return lut ? launch_cor_t<CorVariant<K, false, true>> : launch_cor_t<CorVariant<K, false, false>>;
     else if constexpr (K == CorKind::shgrad)  // only for a scene with SH rows (gsrt_api.cpp: GSRT_E_STATE without)
         return lut ? launch_cor_t<CorVariant<K, true, true>> : launch_cor_t<CorVariant<K, true, false>>;
-    else if constexpr (K == CorKind::splatgrad)  // never with the LUT (frame_refusal)
+    else if constexpr (K == CorKind::splatgrad || K == CorKind::splatdepthgrad)  // never with the LUT (frame_refusal)
         return sh ? launch_cor_t<CorVariant<K, true, false>> : launch_cor_t<CorVariant<K, false, false>>;
     else
         return sh ? (lut ? launch_cor_t<CorVariant<K, true, true>> : launch_cor_t<CorVariant<K, true, false>>)
@@ -3194,6 +3289,7 @@ static CorLaunch cor_kernel(CorKind kind, bool sh, bool lut) {
         case CorKind::shgrad: return cor_kernel_of<CorKind::shgrad>(sh, lut);
         case CorKind::opgrad: return cor_kernel_of<CorKind::opgrad>(sh, lut);
         case CorKind::splatgrad: return cor_kernel_of<CorKind::splatgrad>(sh, lut);
+        case CorKind::splatdepthgrad: return cor_kernel_of<CorKind::splatdepthgrad>(sh, lut);
     }
     return nullptr;
 }
@@ -3253,6 +3349,7 @@ static gsrt_status launch_cor(gsrt_scene* sc, const RenderPlan& plan, const Fram
         switch (sync->grad_kind) {
             case GradKind::opacity: kind = CorKind::opgrad; break;
             case GradKind::splat: kind = CorKind::splatgrad; break;
+            case GradKind::splat_depth: kind = CorKind::splatdepthgrad; break;
             case GradKind::sh: kind = CorKind::shgrad; break;
             default: kind = CorKind::grad; break;
         }

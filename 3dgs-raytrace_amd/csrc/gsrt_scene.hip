@@ -125,7 +125,11 @@ void launch_project(hipStream_t st, uint32_t n, uint32_t mode, const gsrt_ubo& u
 // The longest chain of rounded operations from the inputs to an output (the tests' N) ends in a centre entry by way of
 // the conic: t (4), id (1), id^2 (1), j02 (1), T0 (1), u0 (3), v00 (4), det (1), 1 / det (1), A (1), Q G (2), W (2),
 // dL/dT0 (2), dL/dj02 (3), dL/d(id) (4), dL/dt2 (1), + the ppx, ppy part (1), MV^T dL/dt (4): 37.
+// DEPTH (the second instantiation, gsrt_splat_depth_grad_to_model): the row is gsrt_render_splat_depth_grad's, whose
+// slot 6 holds dL/d(depth), depth = -t2: one more step, dL/dt2 - row[6] (1), before MV^T dL/dt: 38. Without DEPTH slot 6
+// is never read. Nothing of it reaches cov3d.
 // Not a prep kernel: ordinary priority, 256 lanes a workgroup as the scene build's kernels.
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void k_splat_grad_to_model(uint32_t n, const gsrt_ubo ubo,
                                                              const gsrt_gauss_param* __restrict__ params,
                                                              const float* __restrict__ rows, float* __restrict__ grad_center,
@@ -204,6 +208,7 @@ __global__ __launch_bounds__(256) void k_splat_grad_to_model(uint32_t n, const g
             const float gp0 = gnx * iw, gp1 = gny * iw, gp3 = -((gnx * ph[0] + gny * ph[1]) * (iw * iw));
 #pragma unroll
             for (int c = 0; c < 4; ++c) gt[c] = gt[c] + ((cm(P, c, 0) * gp0 + cm(P, c, 1) * gp1) + cm(P, c, 3) * gp3);
+            if constexpr (DEPTH) gt[2] = gt[2] - row[6];  // depth = -t2
 #pragma unroll
             for (int k = 0; k < 3; ++k)
                 dc[k] = ((cm(MV, k, 0) * gt[0] + cm(MV, k, 1) * gt[1]) + cm(MV, k, 2) * gt[2]) + cm(MV, k, 3) * gt[3];
@@ -218,10 +223,14 @@ __global__ __launch_bounds__(256) void k_splat_grad_to_model(uint32_t n, const g
 }
 
 void launch_splat_grad_to_model(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params,
-                                const float* rows, float* grad_center, float* grad_cov, bool accumulate) {
+                                const float* rows, float* grad_center, float* grad_cov, bool accumulate, bool depth) {
     if (!n) return;
-    hipLaunchKernelGGL(k_splat_grad_to_model, dim3((n + 255) / 256), dim3(256), 0, s, n, ubo, params, rows, grad_center,
-                       grad_cov, accumulate ? 1u : 0u);
+    if (depth)
+        hipLaunchKernelGGL(k_splat_grad_to_model<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, ubo, params, rows,
+                           grad_center, grad_cov, accumulate ? 1u : 0u);
+    else
+        hipLaunchKernelGGL(k_splat_grad_to_model<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, ubo, params, rows,
+                           grad_center, grad_cov, accumulate ? 1u : 0u);
 }
 
 // Scene-update copies (gsrt_scene_update / refit / stream_pages from device sources) beside the previous frames'

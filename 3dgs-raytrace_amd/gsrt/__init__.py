@@ -27,6 +27,7 @@ FLAG_FEATURE_GRAD = 0x2000
 FLAG_SH_GRAD = 0x4000
 FLAG_OPACITY_GRAD = 0x8000
 FLAG_SPLAT_GRAD = 0x20000
+FLAG_SPLAT_DEPTH_GRAD = 0x80000
 MAX_FEATURES = 16  # GSRT_MAX_FEATURES
 DUMP8_ESCAPE = 1 << 30  # GSRT_DUMP8_ESCAPE
 SYNTH_COR, SYNTH_REF, SYNTH_NEEDLE = 0, 1, 2
@@ -71,7 +72,8 @@ EXPORTS = [
     "gsrt_unit_order", "gsrt_scene_set_sh", "gsrt_render_sh_grad", "gsrt_render_sh_grad_async",
     "gsrt_render_opacity_grad", "gsrt_render_opacity_grad_async", "gsrt_debug_frame_refusal",
     "gsrt_render_splat_grad", "gsrt_render_splat_grad_async", "gsrt_splat_grad_to_model", "gsrt_splat_grad_to_model_async",
-    "gsrt_debug_frame_refusal_kind",
+    "gsrt_debug_frame_refusal_kind", "gsrt_render_splat_depth_grad", "gsrt_render_splat_depth_grad_async",
+    "gsrt_splat_depth_grad_to_model", "gsrt_splat_depth_grad_to_model_async", "gsrt_debug_frame_refusal_any",
 ]
 
 
@@ -191,10 +193,15 @@ def _load():
         "gsrt_render_opacity_grad_async": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_debug_frame_refusal": ([u32, u32, u32, i32, u32, i32, i32, ctypes.c_char_p, ctypes.c_size_t], i32),
         "gsrt_debug_frame_refusal_kind": ([u32, u32, u32, i32, u32, i32, i32, ctypes.c_char_p, ctypes.c_size_t], i32),
+        "gsrt_debug_frame_refusal_any": ([u32, u32, u32, i32, u32, i32, i32, ctypes.c_char_p, ctypes.c_size_t], i32),
         "gsrt_render_splat_grad": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_render_splat_grad_async": ([P, P, u32, u32, P, P, i32], i32),
         "gsrt_splat_grad_to_model": ([P, P, P, P, P, i32], i32),
         "gsrt_splat_grad_to_model_async": ([P, P, P, P, P, i32], i32),
+        "gsrt_render_splat_depth_grad": ([P, P, u32, u32, P, P, P, i32], i32),
+        "gsrt_render_splat_depth_grad_async": ([P, P, u32, u32, P, P, P, i32], i32),
+        "gsrt_splat_depth_grad_to_model": ([P, P, P, P, P, i32], i32),
+        "gsrt_splat_depth_grad_to_model_async": ([P, P, P, P, P, i32], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -999,26 +1006,56 @@ class Scene:
         _check(lib.gsrt_render_splat_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
                                                 ctypes.c_void_p(d_grad_splat or None), 1 if accumulate else 0), self.ctx)
 
-    def model_grad(self, ubo, splat):
+    def splat_depth_grad(self, ubo, grad_image, grad_depth, mode=MODE_COR, k=0):
+        """The backward of a depth frame, RGBA and expected depth together, to the splat rows
+        (gsrt_render_splat_depth_grad): grad_image as for splat_grad, grad_depth the upstream gradient of the depth image,
+        (H, W) float32. Returns (n, 8): slots 0..5 as splat_grad's with the depth's part in every hit's d, dL/d(view
+        depth) in slot 6 (w * Gdepth / ns summed over the blended hits, clamped or not), +0 in slot 7. Not with FLAG_LUT."""
+        g = _rgba_grad("splat_depth_grad", ubo, grad_image)
+        gd = np.asarray(grad_depth, np.float32)
+        if gd.shape != (int(ubo["height"][0]), int(ubo["width"][0])):
+            raise GsrtError(E_ARG, "splat_depth_grad: grad_depth is an (H, W) array")
+        gd = np.ascontiguousarray(gd)
+        out = np.zeros((self.n, 8), np.float32)
+        _check(lib.gsrt_render_splat_depth_grad(self.handle, _p(ubo), mode, k, _p(g), _p(gd), _p(out), 0), self.ctx)
+        return out
+
+    def splat_depth_grad_async(self, ubo, d_grad_image: int, d_grad_depth: int, d_grad_splat: int, accumulate=False,
+                               mode=MODE_COR, k=0):
+        """Enqueue one splat-depth gradient frame on ctx.stream: d_grad_image (W*H*4 floats), d_grad_depth (W*H floats)
+        and d_grad_splat (n*8 floats, ordinary device memory) are device addresses; accumulate adds to the table."""
+        _check(lib.gsrt_render_splat_depth_grad_async(self.handle, _p(ubo), mode, k, ctypes.c_void_p(d_grad_image or None),
+                                                      ctypes.c_void_p(d_grad_depth or None),
+                                                      ctypes.c_void_p(d_grad_splat or None), 1 if accumulate else 0),
+               self.ctx)
+
+    def model_grad(self, ubo, splat, depth=False):
         """The projection backwards (gsrt_splat_grad_to_model): splat is the (n, 8) table of splat_grad for the same ubo
         and scene parameters; returns (grad_center (n, 3), grad_cov (n, 6)), the covariance in cov3d's order xx, xy, xz,
-        yy, yz, zz, an off-diagonal entry counted as the one variable it is. Deterministic."""
+        yy, yz, zz, an off-diagonal entry counted as the one variable it is. Deterministic. depth: the table is
+        splat_depth_grad's and slot 6 is chained to the centre too (gsrt_splat_depth_grad_to_model)."""
         rows = _f32(splat, (self.n, 8))
         gc, gv = np.zeros((self.n, 3), np.float32), np.zeros((self.n, 6), np.float32)
-        _check(lib.gsrt_splat_grad_to_model(self.handle, _p(ubo), _p(rows), _p(gc), _p(gv), 0), self.ctx)
+        fn = lib.gsrt_splat_depth_grad_to_model if depth else lib.gsrt_splat_grad_to_model
+        _check(fn(self.handle, _p(ubo), _p(rows), _p(gc), _p(gv), 0), self.ctx)
         return gc, gv
 
-    def model_grad_async(self, ubo, d_grad_splat: int, d_grad_center: int, d_grad_cov: int, accumulate=False):
+    def model_grad_async(self, ubo, d_grad_splat: int, d_grad_center: int, d_grad_cov: int, accumulate=False, depth=False):
         """Enqueue the projection's backward on ctx.stream: device addresses of n*8, n*3 and n*6 floats."""
-        _check(lib.gsrt_splat_grad_to_model_async(self.handle, _p(ubo), ctypes.c_void_p(d_grad_splat or None),
-                                                  ctypes.c_void_p(d_grad_center or None),
-                                                  ctypes.c_void_p(d_grad_cov or None), 1 if accumulate else 0), self.ctx)
+        fn = lib.gsrt_splat_depth_grad_to_model_async if depth else lib.gsrt_splat_grad_to_model_async
+        _check(fn(self.handle, _p(ubo), ctypes.c_void_p(d_grad_splat or None), ctypes.c_void_p(d_grad_center or None),
+                  ctypes.c_void_p(d_grad_cov or None), 1 if accumulate else 0), self.ctx)
 
-    def geometry_grad(self, ubo, grad_image, mode=MODE_COR, k=0):
+    def geometry_grad(self, ubo, grad_image, mode=MODE_COR, k=0, grad_depth=None):
         """One splat gradient frame and the projection's backward: (grad_center (n, 3), grad_cov (n, 6), grad_opacity
-        (n,)) of <grad_image, frame> with respect to the scene's parameters."""
-        rows = self.splat_grad(ubo, grad_image, mode, k)
-        gc, gv = self.model_grad(ubo, rows)
+        (n,)) of <grad_image, frame> with respect to the scene's parameters. grad_depth: the (H, W) upstream gradient of
+        the depth image, for <grad_image, frame> + <grad_depth, depth> (splat_depth_grad and the depth chain)."""
+        if grad_depth is None:
+            rows = self.splat_grad(ubo, grad_image, mode, k)
+            gc, gv = self.model_grad(ubo, rows)
+        else:
+            rows = self.splat_depth_grad(ubo, grad_image, grad_depth, mode, k)
+            gc, gv = self.model_grad(ubo, rows, depth=True)
         return gc, gv, rows[:, 5].copy()
 
     def render_sharded(self, ubo, mode=MODE_COR, k=0, want_image=True):

@@ -15,6 +15,7 @@ and for a whole model, geometry included: optimise a scene end to end.
     from gsrt.autograd import render_model
     rgba = render_model(scene, ubo, center, rot, scale, opacity, sh)
     loss(rgba).backward()                              # .grad of all five, through Scene.splat_grad and Scene.model_grad
+    rgba, depth = render_model(..., depth=True)        # the expected depth too, for depth supervision
 
 torch is imported here only; `import gsrt` never needs it.
 
@@ -212,6 +213,55 @@ class _RenderModel(torch.autograd.Function):
         return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None
 
 
+class _RenderModelDepth(torch.autograd.Function):
+    """_RenderModel with the expected depth as a second differentiable output (render_model(..., depth=True))"""
+
+    @staticmethod
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k):
+        n = scene.n
+        params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
+        params[:, 0:3], params[:, 3], params[:, 4:10] = center.detach(), opacity.detach(), cov3d.detach()
+        boxes = aabbs.detach().to(torch.float32).contiguous()
+        W, H = int(ubo["width"][0]), int(ubo["height"][0])
+        rgba = torch.empty((H, W, 4), dtype=torch.float32, device=center.device)
+        depth = torch.empty((H, W), dtype=torch.float32, device=center.device)
+        table = None if sh is None else sh.contiguous()
+        torch.cuda.current_stream(center.device).synchronize()
+        if table is not None:
+            scene.set_sh(table.data_ptr())  # copied into the scene's own rows
+        scene.update(params=params.data_ptr(), aabbs=boxes.data_ptr())  # copied
+        scene.refit_bvh()  # the BVH's boxes follow the new AABBs
+        scene.render_depth_async(ubo, mode, k, rgba.data_ptr(), depth.data_ptr())
+        scene.ctx.synchronize()
+        ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
+        ctx.sh_shape = None if sh is None else tuple(sh.shape)
+        ctx.image = (H, W, center.device)
+        return rgba, depth
+
+    @staticmethod
+    def backward(ctx, grad_rgba, grad_depth):
+        n = ctx.scene.n
+        H, W, device = ctx.image
+        # an output the loss does not use has no upstream gradient: zeros
+        g = (torch.zeros((H, W, 4), dtype=torch.float32, device=device) if grad_rgba is None
+             else grad_rgba.to(torch.float32).contiguous())
+        gd = (torch.zeros((H, W), dtype=torch.float32, device=device) if grad_depth is None
+              else grad_depth.to(torch.float32).contiguous())
+        rows = torch.empty((n, 8), dtype=torch.float32, device=device)
+        d_c = torch.empty((n, 3), dtype=torch.float32, device=device)
+        d_v = torch.empty((n, 6), dtype=torch.float32, device=device)
+        d_sh = None
+        if ctx.sh_shape is not None and ctx.needs_input_grad[3]:
+            d_sh = torch.empty(ctx.sh_shape, dtype=torch.float32, device=device)
+        torch.cuda.current_stream(device).synchronize()
+        ctx.scene.splat_depth_grad_async(ctx.ubo, g.data_ptr(), gd.data_ptr(), rows.data_ptr(), False, ctx.mode, ctx.k)
+        ctx.scene.model_grad_async(ctx.ubo, rows.data_ptr(), d_c.data_ptr(), d_v.data_ptr(), False, depth=True)
+        if d_sh is not None:  # the depth does not depend on SH
+            ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
+        ctx.scene.ctx.synchronize()
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None
+
+
 def model_covariance(rot, scale):
     """cov3d (n, 6) in GaussParam's order xx, xy, xz, yy, yz, zz from rotations (r, x, y, z) and scales, with ordinary
     differentiable torch operations: Sigma = (S R)^T (S R), R the matrix gsrt_scene_from_model builds (Sphere.hpp's)."""
@@ -224,7 +274,7 @@ def model_covariance(rot, scale):
     return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], -1)
 
 
-def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0):
+def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0, depth=False):
     """One colour frame of a whole model as a torch tensor rgba[H, W, 4], differentiable with respect to `center` (n, 3),
     `rot` (n, 4; r, x, y, z, used as given), `scale` (n, 3), `opacity` (n,) and, when given, the SH table `sh` ((n, 16, 3)
     or (n, 48)): float32 GPU tensors for a scene of n Gaussians with a built BVH. cov3d is formed here with torch
@@ -238,7 +288,11 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
     after it.
     The backward renders the scene again: it keeps a copy of `ubo`, but the scene's arrays (Scene.update, refits,
     attached arrays, streamed pages) and its SH rows must stay as they were in the forward until backward has run, or
-    the gradient is that of another frame. The forward leaves the model as the scene's."""
+    the gradient is that of another frame. The forward leaves the model as the scene's.
+    depth=True: returns (rgba, depth), depth[H, W] the expected view depth of Scene.render_depth (premultiplied, like the
+    colour), both differentiable. The forward is Scene.render_depth_async; the backward is one splat-depth gradient frame
+    (Scene.splat_depth_grad_async) of both upstream gradients and the depth chain (Scene.model_grad_async(depth=True)),
+    the rest as above; an output the loss does not use counts as a zero upstream gradient."""
     n = scene.n
     for name, t, shape in (("center", center, (n, 3)), ("rot", rot, (n, 4)), ("scale", scale, (n, 3)),
                            ("opacity", opacity, (n,))):
@@ -250,4 +304,5 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
     with torch.no_grad():
         rad = 3.0 * scale.max(dim=1, keepdim=True).values
         aabbs = torch.cat([center - rad, center + rad], 1)
-    return _RenderModel.apply(center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k)
+    fn = _RenderModelDepth if depth else _RenderModel
+    return fn.apply(center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k)

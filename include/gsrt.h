@@ -84,9 +84,13 @@ enum {
                                    (below) itself, GSRT_E_ARG through every other entry point */
     GSRT_FLAG_OPACITY_GRAD = 0x8000, /* whole COR frames: the backward of a colour frame to the opacities; set by
                                        gsrt_render_opacity_grad (below) itself, GSRT_E_ARG through every other entry point */
-    GSRT_FLAG_SPLAT_GRAD = 0x20000 /* whole COR frames: the backward of a colour frame to each Gaussian's screen-space
+    GSRT_FLAG_SPLAT_GRAD = 0x20000, /* whole COR frames: the backward of a colour frame to each Gaussian's screen-space
                                       centre and conic; set by gsrt_render_splat_grad (below) itself, GSRT_E_ARG through
                                       every other entry point and with GSRT_FLAG_LUT (0x10000 is no flag: "bad mode") */
+    GSRT_FLAG_SPLAT_DEPTH_GRAD = 0x80000 /* whole COR frames: the backward of a depth frame (RGBA and depth image) to the
+                                            splat rows; set by gsrt_render_splat_depth_grad (below) itself, GSRT_E_ARG
+                                            through every other entry point and with GSRT_FLAG_LUT (0x40000, like
+                                            0x10000, is no flag: "bad mode") */
 };
 /* synthetic cloud kinds */
 enum { GSRT_SYNTH_COR = 0, GSRT_SYNTH_REF = 1, GSRT_SYNTH_NEEDLE = 2 };
@@ -447,6 +451,49 @@ gsrt_status gsrt_splat_grad_to_model(gsrt_scene* scene, const gsrt_ubo* ubo, con
 /* the same, enqueued on gsrt_stream(); device pointers only */
 gsrt_status gsrt_splat_grad_to_model_async(gsrt_scene* scene, const gsrt_ubo* ubo, const float* d_grad_splat,
                                            float* d_grad_center, float* d_grad_cov, int accumulate);
+/* Splat-depth gradient frame (GSRT_FLAG_SPLAT_DEPTH_GRAD): the backward of a depth frame (gsrt_render_depth: the RGBA frame
+ * and the expected depth D = sum_i z_i w_i together) to the splat rows of gsrt_render_splat_grad, with the view depth's own
+ * gradient in slot 6. Depth is one more blended channel whose colour is the hit's own z_i, and that colour has a gradient
+ * of its own. Every ray is shaded twice, as for gsrt_render_splat_grad.
+ * grad_image is the upstream gradient G of the RGBA frame, W*H*4 floats; grad_depth the upstream gradient Gdepth of the
+ * depth image, W*H floats; Gs = G[p] / ns and Gd = Gdepth[p] / ns, each formed once (x * (1/ns) for a power of two, x / ns
+ * otherwise). grad_splat receives n rows of 8 floats, [gauss][slot].
+ * Per sample ray, over exactly the hits the colour blend takes (the same order, alpha and stop), with z_i the float32 view
+ * depth the depth frame blends and the hits are keyed by, and everything else as gsrt_render_splat_grad names it:
+ *     Dafter_i = fma(z_i, w_i, Dafter_{i-1}) from +0,  D = Dafter_N      (the depth frame's own arithmetic)
+ *     d_i  = (gsrt_render_splat_grad's d_i)  +  Gd * (T_i z_i - (D - Dafter_i) * r),   r = 1 / (1 - alpha_i),
+ * r the same single float32 reciprocal d_i's other terms are divided by. Slots 0..5 are gsrt_render_splat_grad's formulas
+ * with this d_i; a hit whose alpha the clamp at 0.99 replaced contributes +0 to them (a select). Further
+ *     row[6] += w_i * Gd                 dL/dz (the view depth, -t_2 of the centre's view-space position)
+ * on every blended hit, clamped or not: dD/dz_i = w_i does not pass through the clamp. row[7] = +0. Not differentiated, as
+ * for gsrt_render_splat_grad: the hits taken and their order (the depth key), the AABB slab test, the alpha > 1/255 cut
+ * and gcut, and the stop. The terms are summed with float atomic adds: the order of a sum is unspecified.
+ * accumulate, host and device pointers, the framebuffer (the plain colour frame's, bit for bit; gsrt_depth_buffer and
+ * gsrt_feature_buffer read NULL), the in-order path (gsrt_slot_streams reads 0) and timing: as for
+ * gsrt_render_splat_grad; with accumulate != 0 slot 7 keeps what it holds. Scenes with and without SH rows are served.
+ * GSRT_E_ARG (gsrt_last_error names GSRT_FLAG_SPLAT_DEPTH_GRAD, and the context renders as before): REF mode;
+ * GSRT_FLAG_LUT; GSRT_FLAG_STATS, GSRT_FLAG_OUT_DUMP8, GSRT_FLAG_DEPTH, GSRT_FLAG_FEATURES or another gradient flag with it;
+ * sharded entry points; a scene with a mesh; a NULL grad_image, grad_depth or grad_splat; the flag passed to any other
+ * entry point.
+ * Not provided: LUT frames; sharded frames; gradients through the hit order; a normalised depth's backward (divide in the
+ * caller: with a = rgba[3], d(D / a) takes Gdepth / a here and -Gdepth D / a^2 into G's alpha channel).
+ * gsrt_render_splat_depth_grad blocks until the table is complete, like gsrt_render. */
+gsrt_status gsrt_render_splat_depth_grad(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                         const float* grad_image, const float* grad_depth, float* grad_splat,
+                                         int accumulate);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_render_splat_depth_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, uint32_t mode, uint32_t k,
+                                               const float* d_grad_image, const float* d_grad_depth, float* d_grad_splat,
+                                               int accumulate);
+/* gsrt_splat_grad_to_model for the rows of gsrt_render_splat_depth_grad: slots 0..4 and 6 are read. The view depth is
+ * -t_2 with t = MV (c, 1), so slot 6 enters as dL/dt_2 -= row[6] before the final MV^T dL/dt; nothing of it flows to
+ * grad_cov, which is gsrt_splat_grad_to_model's byte for byte. Same contract otherwise: invalid Gaussians get +0, no
+ * atomics, accumulate with device tables only. */
+gsrt_status gsrt_splat_depth_grad_to_model(gsrt_scene* scene, const gsrt_ubo* ubo, const float* grad_splat,
+                                           float* grad_center, float* grad_cov, int accumulate);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* scene, const gsrt_ubo* ubo, const float* d_grad_splat,
+                                                 float* d_grad_center, float* d_grad_cov, int accumulate);
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into

@@ -56,6 +56,10 @@ gsrt_status gsrt_debug_frame_refusal(uint32_t mode, uint32_t caller, uint32_t sa
  * caller above 3 with GSRT_E_ARG). Callers 0..3 answer as above for every mode. */
 gsrt_status gsrt_debug_frame_refusal_kind(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
                                           int has_features, int has_sh, char* msg, size_t cap);
+/* the same with every caller the library has: 5 gsrt_render_splat_depth_grad (gsrt_debug_frame_refusal_kind keeps
+ * refusing every caller above 4 with GSRT_E_ARG). Callers 0..4 answer as above for every mode. */
+gsrt_status gsrt_debug_frame_refusal_any(uint32_t mode, uint32_t caller, uint32_t samples, int bvh_built, uint32_t ntri,
+                                         int has_features, int has_sh, char* msg, size_t cap);
 /* the context's streams (hipStream_t) in creation order: render, prep H 0, prep L 0, prep H 1, prep L 1, update, comm
  * (NULL before gsrt_comm_init); *n = 7. For the hardware-queue map (profiles/probes/gsrt_queue_map.py) */
 gsrt_status gsrt_debug_streams(gsrt_ctx* ctx, void* out[8], uint32_t* n);
