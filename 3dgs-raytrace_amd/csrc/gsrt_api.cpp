@@ -36,6 +36,19 @@ gsrt_status grow(gsrt_ctx* ctx, T** p, size_t* have, size_t need) {
     return GSRT_OK;
 }
 
+// a blocking call's device copies of host arrays: regions of whole 16-byte units of one block, handed out in order
+struct Staging {
+    char* base = nullptr;
+    size_t used = 0;
+    static size_t unit(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+    template <class T>
+    T* take(size_t count) {
+        T* p = reinterpret_cast<T*>(base + used);
+        used += unit(sizeof(T) * count);
+        return p;
+    }
+};
+
 gsrt_status upload_common(gsrt_ctx* ctx, uint32_t n, const float* sh, gsrt_scene* sc) {
     sc->d_buf[0][0] = sc->d_params;
     sc->d_buf[1][0] = sc->d_aabbs;
@@ -239,6 +252,7 @@ void gsrt_destroy(gsrt_ctx* ctx) {
     (void)hipFree(ctx->d_grad_rows);
     (void)hipFree(ctx->d_grad_in);
     (void)hipFree(ctx->d_grad_out);
+    (void)hipFree(ctx->d_densify_ws);
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_tile_counter);
     (void)hipFree(ctx->d_lut);
@@ -354,17 +368,27 @@ gsrt_status gsrt_scene_from_model(gsrt_ctx* ctx, const float* center, const floa
     }
     if (n) {
         hipStream_t st = ctx->stream;
-        if (hipMemcpyAsync(tmp, center, 12ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(tmp + 3ull * n, rot, 16ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(tmp + 7ull * n, scale, 12ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(tmp + 10ull * n, opacity, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess)
+        const auto kind = [](const void* p) { return is_device_ptr(p) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; };
+        if (hipMemcpyAsync(tmp, center, 12ull * n, kind(center), st) != hipSuccess ||
+            hipMemcpyAsync(tmp + 3ull * n, rot, 16ull * n, kind(rot), st) != hipSuccess ||
+            hipMemcpyAsync(tmp + 7ull * n, scale, 12ull * n, kind(scale), st) != hipSuccess ||
+            hipMemcpyAsync(tmp + 10ull * n, opacity, 4ull * n, kind(opacity), st) != hipSuccess)
             s = fail(ctx, GSRT_E_DEVICE, "scene upload failed");
         if (s == GSRT_OK) {
             gsrt::launch_cov3d(st, n, tmp, tmp + 3ull * n, tmp + 7ull * n, tmp + 10ull * n, sc->d_params, sc->d_aabbs);
             if (hipGetLastError() != hipSuccess) s = fail(ctx, GSRT_E_DEVICE, "cov3d launch failed");
         }
     }
-    if (s == GSRT_OK) s = upload_common(ctx, n, sh, sc);
+    // a device sh takes gsrt_scene_set_sh's device path: k_sh_rows, the same two float32 operations as the host fold
+    const bool sh_dev = sh && n && is_device_ptr(sh);
+    if (s == GSRT_OK) s = upload_common(ctx, n, sh_dev ? nullptr : sh, sc);
+    if (s == GSRT_OK && sh_dev) {
+        if (hipMalloc(&sc->d_sh, sizeof(float) * 48ull * n) != hipSuccess) s = fail(ctx, GSRT_E_OOM, "scene allocation failed");
+        else {
+            gsrt::launch_sh_rows(ctx->stream, sc->d_sh, sh, n);
+            if (hipGetLastError() != hipSuccess) s = fail(ctx, GSRT_E_DEVICE, "sh rows launch failed");
+        }
+    }
     if (s == GSRT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) s = fail(ctx, GSRT_E_DEVICE, "scene build sync");
     (void)hipFree(tmp);
     if (s != GSRT_OK) { gsrt_destroy_scene(sc); return s; }
@@ -1191,6 +1215,234 @@ gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* sc, const gsrt_ubo*
 gsrt_status gsrt_splat_depth_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
                                            float* grad_cov, int accumulate) {
     return model_grad_blocking(sc, ubo, grad_splat, grad_center, grad_cov, accumulate, true);
+}
+
+// ---- adaptive density control (gsrt_densify.hip) ------------------------------------------------------------------
+// Everything runs on the render stream: the statistic follows the gradient frame that wrote its rows in stream order.
+// The calls work on model arrays, not on a scene, so no scene array is read and no update ordering is involved.
+static gsrt_status check_densify_params(gsrt_ctx* ctx, const char* name, const gsrt_densify_params* P) {
+    if (!P) return fail(ctx, GSRT_E_ARG, std::string(name) + ": params is NULL");
+    if (P->reserved[0] | P->reserved[1] | P->reserved[2])
+        return fail(ctx, GSRT_E_ARG, std::string(name) + ": params.reserved must be zero");
+    if (!(P->shrink > 0.0f)) return fail(ctx, GSRT_E_ARG, std::string(name) + ": params.shrink must be > 0");
+    return GSRT_OK;
+}
+
+// the count kernel's workgroup totals and one word for a blocking call's n_out
+static gsrt_status densify_workspace(gsrt_ctx* ctx, uint32_t n) {
+    const size_t need = (size_t)gsrt::densify_blocks(n) + 1;
+    if (ctx->d_densify_ws && ctx->densify_ws_words >= need) return GSRT_OK;
+    GSRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a queued call may still use the smaller one
+    return grow(ctx, &ctx->d_densify_ws, &ctx->densify_ws_words, need);
+}
+
+gsrt_status gsrt_density_stats_add_async(gsrt_ctx* ctx, uint32_t n, uint32_t width, uint32_t height,
+                                         const float* d_grad_splat, float* d_stats) {
+    if (!ctx) return GSRT_E_ARG;
+    if (!d_grad_splat || !d_stats) return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: a NULL pointer");
+    if (!width || !height) return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: width and height must be non-zero");
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: n above GSRT_MAX_GAUSSIANS");
+    if (reinterpret_cast<uintptr_t>(d_grad_splat) % 16u)
+        return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: grad_splat must be 16-byte aligned on the device");
+    (void)hipSetDevice(ctx->device);
+    gsrt::launch_density_stats(ctx->stream, n, width, height, d_grad_splat, d_stats);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_density_stats_add(gsrt_ctx* ctx, uint32_t n, uint32_t width, uint32_t height, const float* grad_splat,
+                                   float* stats) {
+    if (!ctx) return GSRT_E_ARG;
+    if (!grad_splat || !stats) return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: a NULL pointer");
+    if (!width || !height) return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: width and height must be non-zero");
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: n above GSRT_MAX_GAUSSIANS");
+    (void)hipSetDevice(ctx->device);
+    const bool dev = is_device_ptr(grad_splat);
+    if (dev != is_device_ptr(stats))
+        return fail(ctx, GSRT_E_ARG, "gsrt_density_stats_add: grad_splat and stats must both be host or both be device pointers");
+    if (dev) return finish_blocking(ctx, gsrt_density_stats_add_async(ctx, n, width, height, grad_splat, stats), {});
+    if (!n) return GSRT_OK;
+    Staging tmp;
+    GSRT_HIP(ctx, hipMalloc(&tmp.base, Staging::unit(sizeof(float) * 8 * n) + Staging::unit(sizeof(float) * 2 * n)));
+    void* const tmpv = tmp.base;
+    float* const d_rows = tmp.take<float>(8 * (size_t)n);
+    float* const d_stats = tmp.take<float>(2 * (size_t)n);
+    gsrt_status s = GSRT_OK;
+    if (hipMemcpyAsync(d_rows, grad_splat, sizeof(float) * 8 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(d_stats, stats, sizeof(float) * 2 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        s = fail(ctx, GSRT_E_DEVICE, "density statistic upload failed");
+    if (s == GSRT_OK) s = gsrt_density_stats_add_async(ctx, n, width, height, d_rows, d_stats);
+    return finish_blocking(ctx, s, {{stats, d_stats, sizeof(float) * 2 * n, "density statistic download failed"}}, &tmpv);
+}
+
+gsrt_status gsrt_densify_count(gsrt_ctx* ctx, uint32_t n, const float* scale, const float* opacity, const float* stats,
+                               const gsrt_densify_params* params, uint32_t* n_out) {
+    if (!ctx) return GSRT_E_ARG;
+    if (!n_out || (n && (!scale || !opacity || !stats))) return fail(ctx, GSRT_E_ARG, "gsrt_densify_count: a NULL pointer");
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, "gsrt_densify_count: n above GSRT_MAX_GAUSSIANS");
+    gsrt_status s = check_densify_params(ctx, "gsrt_densify_count", params);
+    if (s != GSRT_OK) return s;
+    *n_out = 0;
+    if (!n) return GSRT_OK;
+    (void)hipSetDevice(ctx->device);
+    if ((s = densify_workspace(ctx, n)) != GSRT_OK) return s;
+    const float* src[3] = {scale, opacity, stats};
+    const size_t floats[3] = {3 * (size_t)n, (size_t)n, 2 * (size_t)n};
+    Staging tmp;
+    size_t bytes = 0;
+    for (int a = 0; a < 3; ++a)
+        if (!is_device_ptr(src[a])) bytes += Staging::unit(sizeof(float) * floats[a]);
+    if (bytes) GSRT_HIP(ctx, hipMalloc(&tmp.base, bytes));
+    void* const tmpv = tmp.base;
+    for (int a = 0; a < 3 && s == GSRT_OK; ++a)
+        if (!is_device_ptr(src[a])) {
+            float* d = tmp.take<float>(floats[a]);
+            if (hipMemcpyAsync(d, src[a], sizeof(float) * floats[a], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+                s = fail(ctx, GSRT_E_DEVICE, "gsrt_densify_count: upload failed");
+            src[a] = d;
+        }
+    uint32_t* const d_n = ctx->d_densify_ws + gsrt::densify_blocks(n);
+    if (s == GSRT_OK) {
+        gsrt::launch_densify_count(ctx->stream, n, *params, src[0], src[1], src[2], ctx->d_densify_ws, d_n);
+        if (hipGetLastError() != hipSuccess) s = fail(ctx, GSRT_E_DEVICE, "gsrt_densify_count: launch failed");
+    }
+    return finish_blocking(ctx, s, {{n_out, d_n, sizeof(uint32_t), "gsrt_densify_count: download failed"}}, &tmpv);
+}
+
+// the arrays of a model in a fixed order with their floats per Gaussian (SH and features only when present)
+struct ModelField {
+    float* gsrt_model_arrays::*member;
+    uint32_t floats;
+};
+static uint32_t model_fields(const gsrt_model_arrays& m, ModelField out[6]) {
+    uint32_t k = 0;
+    out[k++] = {&gsrt_model_arrays::center, 3};
+    out[k++] = {&gsrt_model_arrays::rot_rxyz, 4};
+    out[k++] = {&gsrt_model_arrays::scale, 3};
+    out[k++] = {&gsrt_model_arrays::opacity, 1};
+    if (m.sh) out[k++] = {&gsrt_model_arrays::sh, 48};
+    if (m.features) out[k++] = {&gsrt_model_arrays::features, m.feature_channels};
+    return k;
+}
+
+// what both forms of gsrt_densify refuse before anything is queued
+static gsrt_status check_densify_args(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats,
+                                      const float* noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
+                                      const int32_t* origin, uint32_t cap, const uint32_t* n_out) {
+    if (!ctx) return GSRT_E_ARG;
+    const std::string name = "gsrt_densify: ";
+    if (!in || !out || !n_out) return fail(ctx, GSRT_E_ARG, name + "in, out or n_out is NULL");
+    if (gsrt_status s = check_densify_params(ctx, "gsrt_densify", params); s != GSRT_OK) return s;
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, name + "n above GSRT_MAX_GAUSSIANS");
+    for (const gsrt_model_arrays* m : {in, out})
+        if (m->feature_channels > GSRT_MAX_FEATURES || (m->features == nullptr) != (m->feature_channels == 0))
+            return fail(ctx, GSRT_E_ARG, name + "features need 1..GSRT_MAX_FEATURES channels, NULL exactly with 0 channels");
+    if ((in->sh == nullptr) != (out->sh == nullptr) || in->feature_channels != out->feature_channels)
+        return fail(ctx, GSRT_E_ARG, name + "in and out must agree on sh, features and feature_channels");
+    if (n && (!in->center || !in->rot_rxyz || !in->scale || !in->opacity || !stats || !noise))
+        return fail(ctx, GSRT_E_ARG, name + "a NULL input array");
+    if (n && cap && (!out->center || !out->rot_rxyz || !out->scale || !out->opacity || !origin))
+        return fail(ctx, GSRT_E_ARG, name + "a NULL output array");
+    ModelField f[6];
+    const uint32_t nf = model_fields(*in, f);
+    for (uint32_t a = 0; a < nf; ++a)
+        if (in->*f[a].member && in->*f[a].member == out->*f[a].member)
+            return fail(ctx, GSRT_E_ARG, name + "an out array is the matching in array (the pass is not in place)");
+    return GSRT_OK;
+}
+
+// both kernels of the pass on the render stream; every pointer is a device pointer and the arguments are checked
+static gsrt_status densify_enqueue(gsrt_ctx* ctx, const gsrt_model_arrays& in, uint32_t n, const float* d_stats,
+                                   const float* d_noise, const gsrt_densify_params& P, const gsrt_model_arrays& out,
+                                   int32_t* d_origin, uint32_t cap, uint32_t* d_n_out) {
+    if ((reinterpret_cast<uintptr_t>(in.sh) | reinterpret_cast<uintptr_t>(out.sh)) % 16u)
+        return fail(ctx, GSRT_E_ARG, "gsrt_densify: sh must be 16-byte aligned on the device");
+    if (gsrt_status s = densify_workspace(ctx, n); s != GSRT_OK) return s;
+    gsrt::launch_densify_count(ctx->stream, n, P, in.scale, in.opacity, d_stats, ctx->d_densify_ws, d_n_out);
+    gsrt::launch_densify_write(ctx->stream, n, P, in, d_stats, d_noise, out, d_origin, cap, ctx->d_densify_ws, d_n_out);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_densify_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* d_stats,
+                               const float* d_noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
+                               int32_t* d_origin, uint32_t cap, uint32_t* d_n_out) {
+    gsrt_status s = check_densify_args(ctx, in, n, d_stats, d_noise, params, out, d_origin, cap, d_n_out);
+    if (s != GSRT_OK) return s;
+    (void)hipSetDevice(ctx->device);
+    return densify_enqueue(ctx, *in, n, d_stats, d_noise, *params, *out, d_origin, cap, d_n_out);
+}
+
+gsrt_status gsrt_densify(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats, const float* noise,
+                         const gsrt_densify_params* params, const gsrt_model_arrays* out, int32_t* origin, uint32_t cap,
+                         uint32_t* n_out) {
+    gsrt_status s = check_densify_args(ctx, in, n, stats, noise, params, out, origin, cap, n_out);
+    if (s != GSRT_OK) return s;
+    *n_out = 0;
+    if (!n) return GSRT_OK;
+    (void)hipSetDevice(ctx->device);
+    ModelField f[6];
+    const uint32_t nf = model_fields(*in, f);
+    // all on the host or all on the device (absent arrays take no side)
+    uint32_t on_dev = 0, given = 0;
+    const auto side = [&](const void* p) {
+        if (!p) return;
+        ++given;
+        if (is_device_ptr(p)) ++on_dev;
+    };
+    for (uint32_t a = 0; a < nf; ++a) {
+        side(in->*f[a].member);
+        side(out->*f[a].member);
+    }
+    side(stats);
+    side(noise);
+    side(origin);
+    if (on_dev && on_dev != given)
+        return fail(ctx, GSRT_E_ARG, "gsrt_densify: the arrays must all be host pointers or all be device pointers");
+    if ((s = densify_workspace(ctx, n)) != GSRT_OK) return s;
+    uint32_t* const d_n = ctx->d_densify_ws + gsrt::densify_blocks(n);
+    const auto refuse = [&](uint32_t rows) {
+        return fail(ctx, GSRT_E_ARG, "gsrt_densify: " + std::to_string(rows) + " output rows needed, cap is " +
+                                         std::to_string(cap) + " (at most GSRT_MAX_GAUSSIANS rows)");
+    };
+    if (on_dev) {
+        s = densify_enqueue(ctx, *in, n, stats, noise, *params, *out, origin, cap, d_n);
+        s = finish_blocking(ctx, s, {{n_out, d_n, sizeof(uint32_t), "gsrt_densify: count download failed"}});
+        if (s == GSRT_OK && (*n_out > cap || *n_out > GSRT_MAX_GAUSSIANS)) return refuse(*n_out);
+        return s;
+    }
+    // host arrays: one device block, inputs | stats | noise | outputs | origin
+    size_t bytes = Staging::unit(sizeof(float) * 2 * n) + Staging::unit(sizeof(float) * 6 * n) +
+                   Staging::unit(sizeof(int32_t) * (size_t)cap);
+    for (uint32_t a = 0; a < nf; ++a)
+        bytes += Staging::unit(sizeof(float) * f[a].floats * n) + Staging::unit(sizeof(float) * f[a].floats * (size_t)cap);
+    Staging tmp;
+    GSRT_HIP(ctx, hipMalloc(&tmp.base, bytes));
+    void* const tmpv = tmp.base;
+    gsrt_model_arrays d_in = *in, d_out = *out;
+    const auto upload = [&](const float* src, size_t floats) {
+        float* d = tmp.take<float>(floats);
+        if (s == GSRT_OK && hipMemcpyAsync(d, src, sizeof(float) * floats, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "gsrt_densify: upload failed");
+        return d;
+    };
+    for (uint32_t a = 0; a < nf; ++a) d_in.*f[a].member = upload(in->*f[a].member, (size_t)f[a].floats * n);
+    const float* const d_stats = upload(stats, 2 * (size_t)n);
+    const float* const d_noise = upload(noise, 6 * (size_t)n);
+    for (uint32_t a = 0; a < nf; ++a) d_out.*f[a].member = tmp.take<float>((size_t)f[a].floats * cap);
+    int32_t* const d_origin = tmp.take<int32_t>(cap);
+    if (s == GSRT_OK) s = densify_enqueue(ctx, d_in, n, d_stats, d_noise, *params, d_out, d_origin, cap, d_n);
+    if (s == GSRT_OK && (hipMemcpyAsync(n_out, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                         hipStreamSynchronize(ctx->stream) != hipSuccess))
+        s = fail(ctx, GSRT_E_DEVICE, "gsrt_densify: count download failed");
+    if (s == GSRT_OK && (*n_out > cap || *n_out > GSRT_MAX_GAUSSIANS)) s = refuse(*n_out);
+    const size_t rows = s == GSRT_OK ? *n_out : 0;
+    for (uint32_t a = 0; a < nf && rows; ++a)
+        if (s == GSRT_OK && hipMemcpyAsync(out->*f[a].member, d_out.*f[a].member, sizeof(float) * f[a].floats * rows,
+                                           hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "gsrt_densify: download failed");
+    return finish_blocking(ctx, s, {{rows ? origin : nullptr, d_origin, sizeof(int32_t) * rows,
+                                     "gsrt_densify: origin download failed"}}, &tmpv);
 }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,

@@ -166,6 +166,10 @@ struct gsrt_ctx {
     size_t grad_in_floats = 0;
     float* d_grad_out = nullptr;
     size_t grad_out_floats = 0;
+    // gsrt_densify / gsrt_densify_count: the workgroup totals of the count kernel (scanned in place), then one word for a
+    // blocking call's n_out; grown on demand, used in stream order on `stream`
+    uint32_t* d_densify_ws = nullptr;
+    size_t densify_ws_words = 0;
     unsigned long long* d_counters = nullptr;  // kCounters words: [0..7] stats, [kErrWord] sticky error word
     uint32_t* d_tile_counter = nullptr;
     uint32_t last_w = 0, last_h = 0;
@@ -455,6 +459,17 @@ void launch_sh_grad_compact(hipStream_t s, float* dst, const float* rows, uint32
 // and slot 6 (dL/d view depth) goes to the centre as well
 void launch_splat_grad_to_model(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params,
                                 const float* rows, float* grad_center, float* grad_cov, bool accumulate, bool depth = false);
+// adaptive density control (gsrt_densify.hip). launch_density_stats: stats[g] += {norm, 1} for every seen splat row.
+// launch_densify_count: the count kernel's workgroup totals into block_total[0..densify_blocks(n)), scanned in place to
+// the workgroups' first output rows, and the sum into *d_n_out. launch_densify_write: the compaction pass, which reads
+// both and stores nothing when *d_n_out exceeds cap
+uint32_t densify_blocks(uint32_t n);
+void launch_density_stats(hipStream_t s, uint32_t n, uint32_t width, uint32_t height, const float* rows, float* stats);
+void launch_densify_count(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const float* scale, const float* opacity,
+                          const float* stats, uint32_t* block_total, uint32_t* d_n_out);
+void launch_densify_write(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const gsrt_model_arrays& in,
+                          const float* stats, const float* noise, const gsrt_model_arrays& out, int32_t* origin,
+                          uint32_t cap, const uint32_t* block_base, const uint32_t* d_n_out);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into
 inline float* framebuffer_of(gsrt_ctx* ctx) { return ctx->fb_view ? ctx->fb_view : ctx->d_fb; }
 // the prep stream must not overtake what is on ctx->stream now (scene upload/update, BVH build/refit)

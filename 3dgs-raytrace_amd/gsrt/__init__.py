@@ -74,6 +74,7 @@ EXPORTS = [
     "gsrt_render_splat_grad", "gsrt_render_splat_grad_async", "gsrt_splat_grad_to_model", "gsrt_splat_grad_to_model_async",
     "gsrt_debug_frame_refusal_kind", "gsrt_render_splat_depth_grad", "gsrt_render_splat_depth_grad_async",
     "gsrt_splat_depth_grad_to_model", "gsrt_splat_depth_grad_to_model_async", "gsrt_debug_frame_refusal_any",
+    "gsrt_density_stats_add", "gsrt_density_stats_add_async", "gsrt_densify_count", "gsrt_densify", "gsrt_densify_async",
 ]
 
 
@@ -202,6 +203,11 @@ def _load():
         "gsrt_render_splat_depth_grad_async": ([P, P, u32, u32, P, P, P, i32], i32),
         "gsrt_splat_depth_grad_to_model": ([P, P, P, P, P, i32], i32),
         "gsrt_splat_depth_grad_to_model_async": ([P, P, P, P, P, i32], i32),
+        "gsrt_density_stats_add": ([P, u32, u32, u32, P, P], i32),
+        "gsrt_density_stats_add_async": ([P, u32, u32, u32, P, P], i32),
+        "gsrt_densify_count": ([P, u32, P, P, P, P, P], i32),
+        "gsrt_densify": ([P, P, u32, P, P, P, P, P, u32, P], i32),
+        "gsrt_densify_async": ([P, P, u32, P, P, P, P, P, u32, P], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -511,6 +517,123 @@ def comm_unique_id() -> bytes:
     return buf.tobytes()
 
 
+# ---------------------------------------------------------------- adaptive density control
+
+class ModelArrays(ctypes.Structure):
+    """gsrt_model_arrays: addresses of a model's arrays in the gsrt_scene_from_model convention (0 / None: absent)"""
+    _fields_ = [("center", ctypes.c_void_p), ("rot_rxyz", ctypes.c_void_p), ("scale", ctypes.c_void_p),
+                ("opacity", ctypes.c_void_p), ("sh", ctypes.c_void_p), ("features", ctypes.c_void_p),
+                ("feature_channels", ctypes.c_uint32)]
+
+
+class DensifyParams(ctypes.Structure):
+    """gsrt_densify_params"""
+    _fields_ = [("grad_threshold", ctypes.c_float), ("split_scale", ctypes.c_float), ("min_opacity", ctypes.c_float),
+                ("max_scale", ctypes.c_float), ("shrink", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
+
+
+assert ctypes.sizeof(DensifyParams) == 32
+
+
+def densify_params(grad_threshold, split_scale, min_opacity, max_scale=0.0, shrink=1.6) -> DensifyParams:
+    """densify when the mean view-space gradient norm is >= grad_threshold: split when the largest scale is > split_scale,
+    clone otherwise; prune unless opacity >= min_opacity, and when the largest scale is > max_scale (<= 0: no such test);
+    a split child's scales are the parent's / shrink"""
+    return DensifyParams(grad_threshold, split_scale, min_opacity, max_scale, shrink)
+
+
+def _addr(a):
+    return ctypes.c_void_p(a or None) if a is None or isinstance(a, int) else _p(a)
+
+
+def density_stats_add(ctx, grad_splat, stats, width, height, n=None, asynchronous=False):
+    """Add one view's densification statistic to stats (gsrt_density_stats_add): grad_splat the (n, 8) rows of
+    Scene.splat_grad or Scene.splat_depth_grad for a width x height frame, stats an (n, 2) float32 array [sum, count],
+    changed in place and returned: where any of a row's slots 0..5 is non-zero, sum += the norm of (row[0] width / 2,
+    row[1] height / 2) and count += 1. Both numpy arrays, or both device addresses (int) with n given; asynchronous
+    (device addresses only) enqueues on ctx.stream without waiting."""
+    if isinstance(grad_splat, int) or isinstance(stats, int):
+        if n is None:
+            raise GsrtError(E_ARG, "density_stats_add: device addresses need n")
+        fn = lib.gsrt_density_stats_add_async if asynchronous else lib.gsrt_density_stats_add
+        _check(fn(ctx.handle, n, width, height, _addr(grad_splat), _addr(stats)), ctx)
+        return stats
+    if not (isinstance(stats, np.ndarray) and stats.dtype == np.float32 and stats.flags.c_contiguous and
+            stats.ndim == 2 and stats.shape[1] == 2):
+        raise GsrtError(E_ARG, "density_stats_add: stats is a C-contiguous (n, 2) float32 array, added to in place")
+    rows = _f32(grad_splat, (stats.shape[0], 8))
+    _check(lib.gsrt_density_stats_add(ctx.handle, stats.shape[0], width, height, _p(rows), _p(stats)), ctx)
+    return stats
+
+
+def densify_count(ctx, scale, opacity, stats, params, n=None) -> int:
+    """the rows densify would write (gsrt_densify_count): scale (n, 3), opacity (n,), stats (n, 2) as numpy arrays or
+    device addresses (int, with n given), params a DensifyParams"""
+    keep = []
+    if n is None:
+        n = np.asarray(opacity).reshape(-1).shape[0]
+
+    def arg(x, shape):
+        if x is None or isinstance(x, int):
+            return _addr(x)
+        keep.append(_f32(x, shape))
+        return _p(keep[-1])
+    out = ctypes.c_uint32(0)
+    _check(lib.gsrt_densify_count(ctx.handle, n, arg(scale, (n, 3)), arg(opacity, (n,)), arg(stats, (n, 2)),
+                                  ctypes.byref(params), ctypes.byref(out)), ctx)
+    return int(out.value)
+
+
+def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features=None, *, n=None, feature_channels=0,
+            out=None, origin=None, cap=None, d_n_out=None):
+    """Clone, split, prune or keep every Gaussian of a model and write the new one, in input order (gsrt_densify; the
+    rule and the arithmetic are in gsrt.h). stats: (n, 2) from density_stats_add; noise: (n, 2, 3), the caller's normal
+    draws for the two children of a split; params: a DensifyParams (densify_params).
+    numpy arrays: center (n, 3), rot (n, 4), scale (n, 3), opacity (n,), sh (n, 16, 3) / (n, 48) or None, features
+    (n, C) or None. Returns (center', rot', scale', opacity', sh' or None, features' or None, origin), each of n_out rows,
+    sized with densify_count; origin[row] is g for Gaussian g itself and -1 - g for a row newly made from g.
+    device addresses (int; sh / features 0 or None when absent): n, feature_channels, out = the six output addresses in
+    the same order, origin and cap (rows of room) are needed. Blocks and returns n_out (GsrtError E_ARG when it exceeds
+    cap: nothing was written then); with d_n_out, the device address of one uint32, the pass is only enqueued on
+    ctx.stream (gsrt_densify_async) and None is returned."""
+    if isinstance(center, int):
+        if n is None or out is None or origin is None or cap is None:
+            raise GsrtError(E_ARG, "densify: device addresses need n, out, origin and cap")
+        a_in = ModelArrays(center, rot, scale, opacity, sh or None, features or None, feature_channels)
+        a_out = ModelArrays(*[x or None for x in out], feature_channels)
+        if d_n_out is not None:
+            _check(lib.gsrt_densify_async(ctx.handle, ctypes.byref(a_in), n, _addr(stats), _addr(noise), ctypes.byref(params),
+                                          ctypes.byref(a_out), _addr(origin), cap, _addr(d_n_out)), ctx)
+            return None
+        got = ctypes.c_uint32(0)
+        _check(lib.gsrt_densify(ctx.handle, ctypes.byref(a_in), n, _addr(stats), _addr(noise), ctypes.byref(params),
+                                ctypes.byref(a_out), _addr(origin), cap, ctypes.byref(got)), ctx)
+        return int(got.value)
+    center = _f32(center, (-1, 3))
+    n = center.shape[0]
+    rot, scale, opacity = _f32(rot, (n, 4)), _f32(scale, (n, 3)), _f32(opacity, (n,))
+    stats, noise = _f32(stats, (n, 2)), _f32(noise, (n, 2, 3))
+    sh_shape = None if sh is None else np.asarray(sh).shape[1:]
+    sh = None if sh is None else _f32(sh, (n, 48))
+    features = None if features is None else _f32(features, (n, -1) if n else np.asarray(features).shape)
+    fc = 0 if features is None else features.shape[1]
+    rows = densify_count(ctx, scale, opacity, stats, params) if cap is None else cap
+    o = [np.zeros((rows, 3), np.float32), np.zeros((rows, 4), np.float32), np.zeros((rows, 3), np.float32),
+         np.zeros(rows, np.float32), None if sh is None else np.zeros((rows, 48), np.float32),
+         None if features is None else np.zeros((rows, fc), np.float32)]
+    org = np.zeros(rows, np.int32)
+    a_in = ModelArrays(*[None if a is None else a.ctypes.data for a in (center, rot, scale, opacity, sh, features)], fc)
+    a_out = ModelArrays(*[None if a is None else a.ctypes.data for a in o], fc)
+    got = ctypes.c_uint32(0)
+    _check(lib.gsrt_densify(ctx.handle, ctypes.byref(a_in), n, _p(stats), _p(noise), ctypes.byref(params),
+                            ctypes.byref(a_out), _p(org), rows, ctypes.byref(got)), ctx)
+    k = int(got.value)
+    o = [None if a is None else a[:k] for a in o]
+    if o[4] is not None:
+        o[4] = o[4].reshape((k,) + tuple(sh_shape))
+    return o[0], o[1], o[2], o[3], o[4], o[5], org[:k]
+
+
 # ---------------------------------------------------------------- context / scene
 
 class Context:
@@ -756,6 +879,16 @@ class Scene:
         h = ctypes.c_void_p()
         _check(lib.gsrt_scene_from_model(ctx.handle, _p(center), _p(rot), _p(scale), _p(opacity), _p(sh), n,
                                          ctypes.byref(h)), ctx)
+        return cls(ctx, h)
+
+    @classmethod
+    def from_model_device(cls, ctx: Context, n, d_center, d_rot, d_scale, d_opacity, d_sh=0) -> "Scene":
+        """from_model of arrays that live on the device: addresses (int, e.g. a torch tensor's data_ptr()) of n x 3,
+        n x 4, n x 3, n and, optionally, n x 48 floats, read without a host round trip (gsrt_scene_from_model with
+        device sources). The arrays must hold their data when the call is made; it returns once they have been read."""
+        h = ctypes.c_void_p()
+        _check(lib.gsrt_scene_from_model(ctx.handle, _addr(d_center), _addr(d_rot), _addr(d_scale), _addr(d_opacity),
+                                         _addr(d_sh or None), n, ctypes.byref(h)), ctx)
         return cls(ctx, h)
 
     @property

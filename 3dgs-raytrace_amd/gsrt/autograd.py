@@ -17,6 +17,10 @@ and for a whole model, geometry included: optimise a scene end to end.
     loss(rgba).backward()                              # .grad of all five, through Scene.splat_grad and Scene.model_grad
     rgba, depth = render_model(..., depth=True)        # the expected depth too, for depth supervision
 
+and adaptive density control between steps: render_model(..., density_stats=t) accumulates the densification statistic
+in its backward, densify clones, splits and prunes the model on the device, remap_state carries optimiser state across
+(the whole loop: densify's docstring).
+
 torch is imported here only; `import gsrt` never needs it.
 
 Synchronisation is plain and blocking: the current torch stream is synchronised before the library reads a tensor, and
@@ -25,7 +29,8 @@ Context.synchronize() returns before torch reads what the library wrote. The lib
 """
 import torch
 
-from . import MODE_COR
+from . import MODE_COR, density_stats_add
+from . import densify as _densify
 
 
 class _RenderFeatures(torch.autograd.Function):
@@ -173,9 +178,17 @@ def render_rgba(scene, ubo, opacity, sh=None, mode=MODE_COR, k=0):
     return _RenderRgba.apply(opacity, sh, scene, ubo, mode, k)
 
 
+def _add_density_stats(ctx, rows):
+    """render_model(..., density_stats=t): this view's statistic from the splat rows just queued, behind them on the stream"""
+    if ctx.density_stats is not None:
+        W, H = int(ctx.ubo["width"][0]), int(ctx.ubo["height"][0])
+        density_stats_add(ctx.scene.ctx, rows.data_ptr(), ctx.density_stats.data_ptr(), W, H, n=ctx.scene.n,
+                          asynchronous=True)
+
+
 class _RenderModel(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k):
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k, density_stats):
         n = scene.n
         params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
         params[:, 0:3], params[:, 3], params[:, 4:10] = center.detach(), opacity.detach(), cov3d.detach()
@@ -192,6 +205,7 @@ class _RenderModel(torch.autograd.Function):
         scene.ctx.synchronize()
         ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
         ctx.sh_shape = None if sh is None else tuple(sh.shape)
+        ctx.density_stats = density_stats
         return rgba
 
     @staticmethod
@@ -206,18 +220,19 @@ class _RenderModel(torch.autograd.Function):
             d_sh = torch.empty(ctx.sh_shape, dtype=torch.float32, device=g.device)
         torch.cuda.current_stream(g.device).synchronize()
         ctx.scene.splat_grad_async(ctx.ubo, g.data_ptr(), rows.data_ptr(), False, ctx.mode, ctx.k)
+        _add_density_stats(ctx, rows)
         ctx.scene.model_grad_async(ctx.ubo, rows.data_ptr(), d_c.data_ptr(), d_v.data_ptr(), False)
         if d_sh is not None:
             ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
         ctx.scene.ctx.synchronize()
-        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None, None
 
 
 class _RenderModelDepth(torch.autograd.Function):
     """_RenderModel with the expected depth as a second differentiable output (render_model(..., depth=True))"""
 
     @staticmethod
-    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k):
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k, density_stats):
         n = scene.n
         params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
         params[:, 0:3], params[:, 3], params[:, 4:10] = center.detach(), opacity.detach(), cov3d.detach()
@@ -236,6 +251,7 @@ class _RenderModelDepth(torch.autograd.Function):
         ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
         ctx.sh_shape = None if sh is None else tuple(sh.shape)
         ctx.image = (H, W, center.device)
+        ctx.density_stats = density_stats
         return rgba, depth
 
     @staticmethod
@@ -255,11 +271,12 @@ class _RenderModelDepth(torch.autograd.Function):
             d_sh = torch.empty(ctx.sh_shape, dtype=torch.float32, device=device)
         torch.cuda.current_stream(device).synchronize()
         ctx.scene.splat_depth_grad_async(ctx.ubo, g.data_ptr(), gd.data_ptr(), rows.data_ptr(), False, ctx.mode, ctx.k)
+        _add_density_stats(ctx, rows)
         ctx.scene.model_grad_async(ctx.ubo, rows.data_ptr(), d_c.data_ptr(), d_v.data_ptr(), False, depth=True)
         if d_sh is not None:  # the depth does not depend on SH
             ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
         ctx.scene.ctx.synchronize()
-        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None, None
 
 
 def model_covariance(rot, scale):
@@ -274,7 +291,7 @@ def model_covariance(rot, scale):
     return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], -1)
 
 
-def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0, depth=False):
+def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0, depth=False, density_stats=None):
     """One colour frame of a whole model as a torch tensor rgba[H, W, 4], differentiable with respect to `center` (n, 3),
     `rot` (n, 4; r, x, y, z, used as given), `scale` (n, 3), `opacity` (n,) and, when given, the SH table `sh` ((n, 16, 3)
     or (n, 48)): float32 GPU tensors for a scene of n Gaussians with a built BVH. cov3d is formed here with torch
@@ -292,7 +309,10 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
     depth=True: returns (rgba, depth), depth[H, W] the expected view depth of Scene.render_depth (premultiplied, like the
     colour), both differentiable. The forward is Scene.render_depth_async; the backward is one splat-depth gradient frame
     (Scene.splat_depth_grad_async) of both upstream gradients and the depth chain (Scene.model_grad_async(depth=True)),
-    the rest as above; an output the loss does not use counts as a zero upstream gradient."""
+    the rest as above; an output the loss does not use counts as a zero upstream gradient.
+    density_stats: an (n, 2) float32 GPU tensor [sum, count], or None. When given, the backward adds this view's
+    densification statistic to it (gsrt.density_stats_add of the splat rows it has just computed, on the plain path and the
+    depth path alike); the caller zeroes it. None changes nothing."""
     n = scene.n
     for name, t, shape in (("center", center, (n, 3)), ("rot", rot, (n, 4)), ("scale", scale, (n, 3)),
                            ("opacity", opacity, (n,))):
@@ -304,5 +324,82 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
     with torch.no_grad():
         rad = 3.0 * scale.max(dim=1, keepdim=True).values
         aabbs = torch.cat([center - rad, center + rad], 1)
+    if density_stats is not None and (density_stats.dtype != torch.float32 or not density_stats.is_cuda or
+                                      tuple(density_stats.shape) != (n, 2) or not density_stats.is_contiguous()):
+        raise ValueError("render_model: density_stats must be a contiguous (n, 2) float32 tensor on the GPU")
     fn = _RenderModelDepth if depth else _RenderModel
-    return fn.apply(center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k)
+    return fn.apply(center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k, density_stats)
+
+
+def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features=None):
+    """Adaptive density control of a model on the device (gsrt.densify, gsrt_densify_async): clone, split, prune or keep
+    every Gaussian by the rule of gsrt.h and return the new model (center', rot', scale', opacity', sh', features',
+    origin) as torch tensors of n_out rows, in input order; sh' / features' are None when sh / features are. ctx: the
+    gsrt.Context; center (n, 3), rot (n, 4), scale (n, 3), opacity (n,), sh (n, 16, 3) / (n, 48) or None, features
+    (n, C) or None, stats (n, 2) (render_model's density_stats), noise (n, 2, 3) (e.g. torch.randn: the library has no
+    random numbers): float32 GPU tensors; params: gsrt.densify_params(...). The outputs are allocated at 2 n rows, which
+    always suffices, and returned as trimmed views. origin (int32) holds g for Gaussian g itself and -1 - g for a row
+    newly made from g: remap_state carries optimiser state across. Gradients do not flow through this call.
+
+    The whole loop, with Adam moments m and v per parameter tensor:
+
+        stats = torch.zeros((n, 2), device="cuda")
+        for step in range(steps):
+            rgba = render_model(scene, ubo, center, rot, scale, opacity, sh, density_stats=stats)   # 1: render,
+            loss(rgba).backward()                                                                   #    backward
+            optimiser.step()
+            if step % k == k - 1:
+                with torch.no_grad():
+                    new = densify(ctx, center, rot, scale, opacity, sh, stats, torch.randn(n, 2, 3, device="cuda"),
+                                  gsrt.densify_params(0.0002, split_scale, 0.005))                  # 2: densify
+                    origin = new[-1]
+                    m, v = remap_state(m, origin), remap_state(v, origin)                           # 3: optimiser state
+                    center, rot, scale, opacity, sh = (t.clone().requires_grad_() for t in new[:5])
+                    n = center.shape[0]
+                    scene.close()
+                    scene = gsrt.Scene.from_model_device(ctx, n, center.data_ptr(), rot.data_ptr(), scale.data_ptr(),
+                                                         opacity.data_ptr(), sh.data_ptr())         # 4: the new scene
+                    scene.build_bvh()
+                    stats = torch.zeros((n, 2), device="cuda")                                      # 5: zero the stats
+    """
+    n = int(center.shape[0])
+    dev = center.device
+    tensors = [("center", center, (n, 3)), ("rot", rot, (n, 4)), ("scale", scale, (n, 3)), ("opacity", opacity, (n,)),
+               ("stats", stats, (n, 2)), ("noise", noise, (n, 2, 3))]
+    if sh is not None:
+        if tuple(sh.shape) not in ((n, 16, 3), (n, 48)):
+            raise ValueError("densify: sh must be an (n, 16, 3) or (n, 48) tensor")
+        tensors.append(("sh", sh, tuple(sh.shape)))
+    fc = 0
+    if features is not None:
+        fc = int(features.shape[1]) if features.dim() == 2 else -1
+        tensors.append(("features", features, (n, fc)))
+    for name, t, shape in tensors:
+        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
+            raise ValueError(f"densify: {name} must be a {shape} float32 tensor on the GPU")
+    src = {name: t.detach().contiguous() for name, t, _ in tensors}
+    cap = 2 * n
+    new = lambda *shape: torch.empty((cap,) + shape, dtype=torch.float32, device=dev)  # noqa: E731
+    out = [new(3), new(4), new(3), new(), None if sh is None else new(*sh.shape[1:]),
+           None if features is None else new(fc)]
+    origin = torch.empty((cap,), dtype=torch.int32, device=dev)
+    n_out = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+    torch.cuda.current_stream(dev).synchronize()
+    _densify(ctx, ptr(src["center"]), ptr(src["rot"]), ptr(src["scale"]), ptr(src["opacity"]), ptr(src.get("sh")),
+             ptr(src["stats"]), ptr(src["noise"]), params, ptr(src.get("features")), n=n, feature_channels=fc,
+             out=[ptr(t) for t in out], origin=origin.data_ptr(), cap=cap, d_n_out=n_out.data_ptr())
+    ctx.synchronize()
+    rows = int(n_out.item())
+    return tuple(None if t is None else t[:rows] for t in out) + (origin[:rows],)
+
+
+def remap_state(t, origin):
+    """Rows of `t` (per-Gaussian optimiser state, e.g. an Adam moment, (n, ...)) carried across a densify: row i of the
+    result is t[origin[i]] where origin[i] >= 0 (the Gaussian itself) and zeros where origin[i] < 0 (newly made: a fresh
+    state)."""
+    origin = origin.to(torch.int64)
+    kept = origin >= 0
+    out = torch.zeros((origin.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    out[kept] = t[origin[kept]]
+    return out

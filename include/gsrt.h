@@ -126,7 +126,10 @@ int gsrt_slot_streams(const gsrt_ctx* ctx);
 gsrt_status gsrt_scene_from_params(gsrt_ctx* ctx, const gsrt_gauss_param* params, const gsrt_aabb* aabbs,
                                    uint32_t n, const float* sh, gsrt_scene** out);
 /* Model::CreateGauss + Gauss::init_cov3d/init_radius (Model.cpp:550-564, Sphere.hpp:108-165), computed
- * on the device. rot_rxyz is the reference's vec4(r, x, y, z). */
+ * on the device. rot_rxyz is the reference's vec4(r, x, y, z). Each of the five arrays is a host or a device pointer, on
+ * its own (a device sh is transposed on the device, as gsrt_scene_set_sh does): a model that lives on the device, such as
+ * gsrt_densify's output, becomes a scene without a host round trip. A device source must hold its data when the call
+ * is made; the call returns when it has been read. */
 gsrt_status gsrt_scene_from_model(gsrt_ctx* ctx, const float* center, const float* rot_rxyz, const float* scale,
                                   const float* opacity, const float* sh, uint32_t n, gsrt_scene** out);
 /* download the device-side GaussParam / AABB arrays (either may be NULL) */
@@ -494,6 +497,95 @@ gsrt_status gsrt_splat_depth_grad_to_model(gsrt_scene* scene, const gsrt_ubo* ub
 /* the same, enqueued on gsrt_stream(); device pointers only */
 gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* scene, const gsrt_ubo* ubo, const float* d_grad_splat,
                                                  float* d_grad_center, float* d_grad_cov, int accumulate);
+/* ---- adaptive density control: clone, split and prune a model on the device ----------------------
+ * The model is the gsrt_scene_from_model arrays; the calls below work on arrays, not on a scene: a scene's size is fixed,
+ * so after gsrt_densify the caller creates a new scene from the new arrays (gsrt_scene_from_model takes device pointers)
+ * and builds its BVH. The library has no random numbers: a split's samples come from the caller's noise, so a result is
+ * a pure function of its inputs. Not provided: screen-radius pruning, an opacity reset, resizing a scene in place. */
+typedef struct gsrt_model_arrays {   /* the gsrt_scene_from_model convention */
+    float* center;    /* n x 3 */
+    float* rot_rxyz;  /* n x 4, used as given */
+    float* scale;     /* n x 3 */
+    float* opacity;   /* n */
+    float* sh;        /* n x 48 [gauss][coef][rgb], nullable */
+    float* features;  /* n x feature_channels, nullable */
+    uint32_t feature_channels; /* 0..GSRT_MAX_FEATURES; 0 exactly when features is NULL */
+} gsrt_model_arrays;
+
+typedef struct gsrt_densify_params {
+    float grad_threshold; /* densify when the mean view-space gradient norm is >= this */
+    float split_scale;    /* a densified Gaussian whose largest scale is > this is split, otherwise cloned */
+    float min_opacity;    /* prune unless opacity >= this (so a NaN opacity is pruned) */
+    float max_scale;      /* prune when the largest scale is > this; <= 0 switches the test off */
+    float shrink;         /* a split child's scales are the parent's / shrink (3DGS: 1.6); must be > 0 */
+    uint32_t reserved[3]; /* zero, otherwise GSRT_E_ARG */
+} gsrt_densify_params;
+
+/* The densification statistic of one view, added to stats. grad_splat: the n rows of 8 floats of gsrt_render_splat_grad or
+ * gsrt_render_splat_depth_grad for a frame of width x height pixels; stats: n x 2 floats [sum, count], which the caller
+ * zeroes and this call always adds to. Per Gaussian g, in float32, in exactly this order:
+ *     gx = row[0] * (0.5f * (float)width),  gy = row[1] * (0.5f * (float)height)
+ *     norm = sqrtf(gx * gx + gy * gy)            (products and sum rounded one by one, a correctly rounded root)
+ *     seen = any of row[0..5] != 0.0f            (a -0 is not seen, a NaN is)
+ *     if seen: stats[g][0] += norm, stats[g][1] += 1; otherwise both words stay bit for bit as they were.
+ * The scaling is that of 3DGS's viewspace_point_tensor.grad (the gradient with respect to the NDC position: a pixel is
+ * 2 / width of NDC), so published thresholds such as 0.0002 carry over. "Seen" means that a ray's blend reached the
+ * Gaussian with a gradient: the ray tracer's notion of visibility (a Gaussian behind an opaque one, or one no ray's
+ * alpha cut lets through, is not seen), not the rasteriser's "inside the frustum". One lane per Gaussian and no atomics:
+ * the result is deterministic.
+ * grad_splat and stats are both host pointers or both device pointers (16-byte aligned rows on the device, as
+ * hipMalloc and torch give them). The call runs on gsrt_stream(), behind the gradient frame that wrote the rows, and
+ * blocks until stats is complete.
+ * GSRT_E_ARG: a NULL ctx or pointer; one host and one device pointer; width or height 0; n > GSRT_MAX_GAUSSIANS. */
+gsrt_status gsrt_density_stats_add(gsrt_ctx* ctx, uint32_t n, uint32_t width, uint32_t height, const float* grad_splat,
+                                   float* stats);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_density_stats_add_async(gsrt_ctx* ctx, uint32_t n, uint32_t width, uint32_t height,
+                                         const float* d_grad_splat, float* d_stats);
+/* gsrt_densify's decision and row count alone: n_out = the rows gsrt_densify would write for these scales (n x 3),
+ * opacities (n), stats (n x 2) and params, so that a caller can size the output arrays exactly. Each array is a host or a
+ * device pointer, on its own. Blocks. GSRT_E_ARG: a NULL pointer (the arrays may be NULL when n is 0), bad params (a
+ * non-zero reserved word, shrink not > 0), n > GSRT_MAX_GAUSSIANS. */
+gsrt_status gsrt_densify_count(gsrt_ctx* ctx, uint32_t n, const float* scale, const float* opacity, const float* stats,
+                               const gsrt_densify_params* params, uint32_t* n_out);
+/* Clone, split, prune or keep every Gaussian of `in` (n of them) and write the new model to `out` in one ordered
+ * compaction pass. Per Gaussian g, in float32:
+ *     m     = the largest of the three scales (m = s0; if (s1 > m) m = s1; if (s2 > m) m = s2, as the scene build)
+ *     mean  = stats[g][1] > 0 ? stats[g][0] / stats[g][1] : 0            (stats: gsrt_density_stats_add's)
+ *     prune = !(opacity >= min_opacity) || (max_scale > 0 && m > max_scale)
+ *     dens  = !prune && mean >= grad_threshold
+ *     split = dens && m > split_scale,   clone = dens && !split
+ * g takes c_g output rows: 0 when pruned, 1 when kept, 2 when cloned or split. Its rows start at o_g = the sum of c_h
+ * over h < g: the output's order is the input's, and n_out = the sum of all c_g.
+ *     keep:   row o_g is g, every field bit for bit;                       origin[o_g] = g
+ *     clone:  rows o_g and o_g + 1 are both g, every field bit for bit;     origin = g, -1 - g
+ *     split:  rows o_g + k, k = 0 and 1, are the children;                  origin = -1 - g for both
+ * A split child k: z = noise[g][k][0..3], v_i = scale_i * z_i, x_j = (v_0 R[0][j] + v_1 R[1][j]) + v_2 R[2][j] with R the
+ * rotation matrix of the scene build (row k, column j; its entries formed with the build's own expressions from rot_rxyz as
+ * given), so that x has the covariance (S R)^T (S R) for unit normal z: the scene's own Sigma. centre'_j = centre_j + x_j,
+ * scale'_i = scale_i / shrink; rotation, opacity, the SH row and the feature row are copied bit for bit. Every operation is
+ * rounded on its own (no fused multiply-add), the division correctly.
+ * noise: n x 2 x 3 floats of the caller's (standard normal draws for 3DGS's split); only a split Gaussian's are read.
+ * origin: int32[cap]; a row holds g when it is Gaussian g itself (its optimiser state carries over) and -1 - g when it
+ * was newly made from g (a fresh optimiser state).
+ * cap: the rows `out` and origin have room for; 2 n always suffices. n_out is always written. When n_out > cap or
+ * n_out > GSRT_MAX_GAUSSIANS nothing else is written: GSRT_E_ARG, and gsrt_last_error names the count needed.
+ * in and out must agree on which of sh and features are present and on feature_channels; an out array that is the
+ * matching in array is GSRT_E_ARG (the pass is not in place). All arrays (in, stats, noise, out, origin) are host pointers
+ * or all are device pointers (sh on the device 16-byte aligned); n_out is a host pointer. The call runs on gsrt_stream()
+ * and blocks until `out` is complete.
+ * GSRT_E_ARG also: a NULL ctx, in, out, params or n_out; a NULL input array with n > 0 or output array with cap > 0; bad
+ * params; feature_channels above GSRT_MAX_FEATURES or not matching features; n > GSRT_MAX_GAUSSIANS. */
+gsrt_status gsrt_densify(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats, const float* noise,
+                         const gsrt_densify_params* params, const gsrt_model_arrays* out, int32_t* origin, uint32_t cap,
+                         uint32_t* n_out);
+/* the same, enqueued on gsrt_stream() without a host synchronisation; device pointers only, d_n_out (one uint32)
+ * included: when it reads more than cap (or than GSRT_MAX_GAUSSIANS) after the stream has run, nothing else was written,
+ * which is for the caller to check. (A call for a larger n than any before it on this ctx allocates its workspace first.) */
+gsrt_status gsrt_densify_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* d_stats,
+                               const float* d_noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
+                               int32_t* d_origin, uint32_t cap, uint32_t* d_n_out);
+
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into
