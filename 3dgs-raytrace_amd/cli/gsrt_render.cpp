@@ -26,6 +26,11 @@
 // the same table out; without --splat-grad it is a usage error.
 // Their usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, a gradient run listed before
 // it, one option without the others, C outside 1..16.
+// --loss-target FILE [--loss-lambda L] [--loss-channels 3|4] [--loss-grad-out FILE]: after the frame, its photometric
+// loss against the target image (gsrt_image_loss: raw float32, W*H*channels, 3 channels and lambda 0.2 by default); prints
+// "loss L l1 A ssim S mse M" and writes the loss's gradient with respect to the frame as raw float32 W*H*4, the file
+// --splat-grad, --sh-grad and --opacity-grad read. Usage errors: a gradient run (it renders no frame), the other
+// --loss options without --loss-target, channels not 3 or 4, lambda outside [0, 1].
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +57,10 @@ struct Options {
     std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out, splat_grad, splat_grad_out, depth_grad;
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
+    std::string loss_target, loss_grad_out;
+    float loss_lambda = 0.2f;
+    uint32_t loss_channels = 3;
+    bool loss_options_given = false;  // --loss-lambda, --loss-channels or --loss-grad-out
 };
 
 // A gradient run, --NAME FILE with --NAME-out FILE: the upstream gradient image (raw float32, W*H*image_channels) in, the
@@ -94,7 +103,8 @@ bool given(const Options& o, const GradOption& g) { return !(o.*g.in).empty() ||
                  "                   [--feature-grad FILE --feature-channels C --feature-grad-out FILE]\n"
                  "                   [--sh-grad FILE --sh-grad-out FILE]\n"
                  "                   [--opacity-grad FILE --opacity-grad-out FILE]\n"
-                 "                   [--splat-grad FILE --splat-grad-out FILE] [--depth-grad FILE]\n");
+                 "                   [--splat-grad FILE --splat-grad-out FILE] [--depth-grad FILE]\n"
+                 "                   [--loss-target FILE [--loss-lambda L] [--loss-channels 3|4] [--loss-grad-out FILE]]\n");
     std::exit(2);
 }
 
@@ -148,6 +158,10 @@ Options parse(int argc, char** argv) {
         else if (a == "--splat-grad-out") o.splat_grad_out = val();
         else if (a == "--depth-grad") o.depth_grad = val();
         else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
+        else if (a == "--loss-target") o.loss_target = val();
+        else if (a == "--loss-lambda") { o.loss_lambda = std::strtof(val(), nullptr); o.loss_options_given = true; }
+        else if (a == "--loss-channels") { o.loss_channels = to_u32(val(), "--loss-channels"); o.loss_options_given = true; }
+        else if (a == "--loss-grad-out") { o.loss_grad_out = val(); o.loss_options_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -173,6 +187,13 @@ Options parse(int argc, char** argv) {
         clash(!o.depth.empty(), "--depth");
         clash(!o.features.empty() || !o.features_out.empty(), "--features");
         for (const GradOption* older = kGradOptions; older != g; ++older) clash(given(o, *older), older->name);
+    }
+    if (o.loss_target.empty() && o.loss_options_given) usage("--loss-lambda, --loss-channels and --loss-grad-out go with --loss-target");
+    if (!o.loss_target.empty()) {
+        if (o.loss_channels != 3 && o.loss_channels != 4) usage("--loss-channels must be 3 or 4");
+        if (!(o.loss_lambda >= 0.0f && o.loss_lambda <= 1.0f)) usage("--loss-lambda must be in [0, 1]");
+        for (const GradOption& g : kGradOptions)
+            if (given(o, g)) usage((std::string("--loss-target cannot be combined with ") + g.name + " (a gradient run renders no frame)").c_str());
     }
     // (with --feature-grad, --feature-channels is that pair's)
     if (!given(o, kGradOptions[0]) && (!o.features.empty() || !o.features_out.empty() || o.feature_channels_given)) {
@@ -336,6 +357,31 @@ int main(int argc, char** argv) {
             std::printf("rays %llu candidates %llu blended %llu terminated %llu rounds %llu tiles %llu\n",
                         (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2],
                         (unsigned long long)st[3], (unsigned long long)st[4], (unsigned long long)st[6]);
+    }
+    if (!rc && !o.loss_target.empty()) {
+        // the target: W * H * channels raw float32; the gradient: W * H * 4 raw float32, what --splat-grad reads
+        const size_t px = (size_t)o.width * o.height;
+        std::vector<float> target(px * o.loss_channels), gimg(o.loss_grad_out.empty() ? 0 : px * 4);
+        FILE* f = std::fopen(o.loss_target.c_str(), "rb");
+        const bool whole = f && std::fread(target.data(), sizeof(float), target.size(), f) == target.size() &&
+                           std::fgetc(f) == EOF;
+        if (f) std::fclose(f);
+        if (!whole) {
+            std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels x %u)\n", o.loss_target.c_str(),
+                         target.size(), o.loss_channels);
+            rc = 1;
+        }
+        float sc[4] = {0, 0, 0, 0};
+        if (!rc)
+            rc = check(gsrt_image_loss(ctx, o.width, o.height, rgba.data(), target.data(), o.loss_channels, o.loss_lambda, sc,
+                                       gimg.empty() ? nullptr : gimg.data()), ctx, "image_loss");
+        if (!rc) std::printf("loss %.9g l1 %.9g ssim %.9g mse %.9g\n", sc[0], sc[1], sc[2], sc[3]);
+        if (!rc && !gimg.empty()) {
+            f = std::fopen(o.loss_grad_out.c_str(), "wb");
+            const bool ok = f && std::fwrite(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size();
+            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.loss_grad_out.c_str());
+            if (!rc) std::printf("wrote %s\n", o.loss_grad_out.c_str());
+        }
     }
     if (!rc && o.benchmark) {
         const uint32_t frames = o.frames ? o.frames : 1;

@@ -253,6 +253,7 @@ void gsrt_destroy(gsrt_ctx* ctx) {
     (void)hipFree(ctx->d_grad_in);
     (void)hipFree(ctx->d_grad_out);
     (void)hipFree(ctx->d_densify_ws);
+    (void)hipFree(ctx->d_loss_ws);
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_tile_counter);
     (void)hipFree(ctx->d_lut);
@@ -1443,6 +1444,103 @@ gsrt_status gsrt_densify(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n,
             s = fail(ctx, GSRT_E_DEVICE, "gsrt_densify: download failed");
     return finish_blocking(ctx, s, {{rows ? origin : nullptr, d_origin, sizeof(int32_t) * rows,
                                      "gsrt_densify: origin download failed"}}, &tmpv);
+}
+
+// ---- photometric loss (gsrt_image_loss.hip) -----------------------------------------------------------------------
+// On the render stream: behind the frame that wrote rgba and ahead of the gradient frame that reads grad_image. The call
+// works on images, not on a scene, so no scene array is read and no update ordering is involved.
+gsrt_status gsrt_image_loss_window(float out[11]) {
+    if (!out) return GSRT_E_ARG;
+    gsrt::image_loss_window(out);
+    return GSRT_OK;
+}
+
+// what both forms of gsrt_image_loss refuse before anything is queued or written
+static gsrt_status check_image_loss_args(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba,
+                                         const float* target, uint32_t target_channels, float lambda, const float* out,
+                                         const float* grad_image) {
+    if (!ctx) return GSRT_E_ARG;
+    const std::string name = "gsrt_image_loss: ";
+    if (!rgba || !target || !out) return fail(ctx, GSRT_E_ARG, name + "rgba, target or out is NULL");
+    if (width == 0 || height == 0 || width > 32768 || height > 32768)
+        return fail(ctx, GSRT_E_ARG, name + "width and height must be 1..32768");
+    if (target_channels != 3 && target_channels != 4) return fail(ctx, GSRT_E_ARG, name + "target_channels must be 3 or 4");
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(ctx, GSRT_E_ARG, name + "lambda must be in [0, 1]");
+    if (grad_image) {
+        const size_t px = (size_t)width * height;
+        const auto overlaps = [&](const float* p, size_t floats) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(grad_image), b = reinterpret_cast<uintptr_t>(p);
+            return a < b + sizeof(float) * floats && b < a + sizeof(float) * 4 * px;
+        };
+        if (overlaps(rgba, 4 * px) || overlaps(target, target_channels * px))
+            return fail(ctx, GSRT_E_ARG, name + "grad_image overlaps rgba or target");
+    }
+    return GSRT_OK;
+}
+
+// the call's kernels on the render stream; every pointer is a device pointer (d_out nullptr: the workspace's four
+// floats, whose address *d_out_used receives) and the arguments are checked
+static gsrt_status image_loss_enqueue(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_rgba,
+                                      const float* d_target, uint32_t target_channels, float lambda, float* d_out,
+                                      float* d_grad, float** d_out_used = nullptr) {
+    const uintptr_t wide = reinterpret_cast<uintptr_t>(d_rgba) | reinterpret_cast<uintptr_t>(d_grad) |
+                           (target_channels == 4 ? reinterpret_cast<uintptr_t>(d_target) : 0);
+    if (wide % 16u)
+        return fail(ctx, GSRT_E_ARG, "gsrt_image_loss: rgba, grad_image and a 4-channel target must be 16-byte aligned on the device");
+    const size_t px = (size_t)width * height, tiles = gsrt::image_loss_tiles(width, height);
+    const size_t need = 3 * tiles + 2 + (d_grad ? (9 * px + 1) / 2 : 0);
+    if (!ctx->d_loss_ws || ctx->loss_ws_doubles < need) {
+        GSRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a queued call may still use the smaller one
+        if (gsrt_status s = grow(ctx, &ctx->d_loss_ws, &ctx->loss_ws_doubles, need); s != GSRT_OK) return s;
+    }
+    float* const ws_out = reinterpret_cast<float*>(ctx->d_loss_ws + 3 * tiles);
+    if (d_out_used) *d_out_used = d_out ? d_out : ws_out;
+    gsrt::launch_image_loss(ctx->stream, width, height, d_rgba, d_target, target_channels, lambda, ctx->d_loss_ws,
+                            ws_out + 4, d_out ? d_out : ws_out, d_grad);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_image_loss_async(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_rgba,
+                                  const float* d_target, uint32_t target_channels, float lambda, float* d_out,
+                                  float* d_grad_image) {
+    gsrt_status s = check_image_loss_args(ctx, width, height, d_rgba, d_target, target_channels, lambda, d_out, d_grad_image);
+    if (s != GSRT_OK) return s;
+    (void)hipSetDevice(ctx->device);
+    return image_loss_enqueue(ctx, width, height, d_rgba, d_target, target_channels, lambda, d_out, d_grad_image);
+}
+
+gsrt_status gsrt_image_loss(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const float* target,
+                            uint32_t target_channels, float lambda, float out[4], float* grad_image) {
+    gsrt_status s = check_image_loss_args(ctx, width, height, rgba, target, target_channels, lambda, out, grad_image);
+    if (s != GSRT_OK) return s;
+    (void)hipSetDevice(ctx->device);
+    const bool dev = is_device_ptr(rgba);
+    if (dev != is_device_ptr(target) || (grad_image && dev != is_device_ptr(grad_image)))
+        return fail(ctx, GSRT_E_ARG, "gsrt_image_loss: rgba, target and grad_image must all be host pointers or all be device pointers");
+    if (is_device_ptr(out)) return fail(ctx, GSRT_E_ARG, "gsrt_image_loss: out is a host pointer");
+    const size_t px = (size_t)width * height;
+    float* d_out = nullptr;
+    if (dev) {
+        s = image_loss_enqueue(ctx, width, height, rgba, target, target_channels, lambda, nullptr, grad_image, &d_out);
+        return finish_blocking(ctx, s, {{out, d_out, sizeof(float) * 4, "gsrt_image_loss: scalar download failed"}});
+    }
+    // host images: one device block, rgba | target | gradient
+    Staging tmp;
+    GSRT_HIP(ctx, hipMalloc(&tmp.base, Staging::unit(sizeof(float) * 4 * px) + Staging::unit(sizeof(float) * target_channels * px) +
+                                           (grad_image ? Staging::unit(sizeof(float) * 4 * px) : 0)));
+    void* const tmpv = tmp.base;
+    float* const d_rgba = tmp.take<float>(4 * px);
+    float* const d_target = tmp.take<float>(target_channels * px);
+    float* const d_grad = grad_image ? tmp.take<float>(4 * px) : nullptr;
+    if (hipMemcpyAsync(d_rgba, rgba, sizeof(float) * 4 * px, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(d_target, target, sizeof(float) * target_channels * px, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        s = fail(ctx, GSRT_E_DEVICE, "gsrt_image_loss: upload failed");
+    if (s == GSRT_OK)
+        s = image_loss_enqueue(ctx, width, height, d_rgba, d_target, target_channels, lambda, nullptr, d_grad, &d_out);
+    return finish_blocking(ctx, s, {{out, d_out, sizeof(float) * 4, "gsrt_image_loss: scalar download failed"},
+                                    {grad_image, d_grad, sizeof(float) * 4 * px, "gsrt_image_loss: gradient download failed"}},
+                           &tmpv);
 }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,

@@ -170,6 +170,10 @@ struct gsrt_ctx {
     // blocking call's n_out; grown on demand, used in stream order on `stream`
     uint32_t* d_densify_ws = nullptr;
     size_t densify_ws_words = 0;
+    // gsrt_image_loss: per tile three partial sums (doubles), then four floats for a blocking call's scalars, then, for a
+    // call with a gradient, the nine derivative planes of W x H floats; grown on demand, used in stream order on `stream`
+    double* d_loss_ws = nullptr;
+    size_t loss_ws_doubles = 0;
     unsigned long long* d_counters = nullptr;  // kCounters words: [0..7] stats, [kErrWord] sticky error word
     uint32_t* d_tile_counter = nullptr;
     uint32_t last_w = 0, last_h = 0;
@@ -470,6 +474,14 @@ void launch_densify_count(hipStream_t s, uint32_t n, const gsrt_densify_params& 
 void launch_densify_write(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const gsrt_model_arrays& in,
                           const float* stats, const float* noise, const gsrt_model_arrays& out, int32_t* origin,
                           uint32_t cap, const uint32_t* block_base, const uint32_t* d_n_out);
+// the photometric loss (gsrt_image_loss.hip). image_loss_tiles: the tiles of a frame, each with three doubles in
+// `partial`. launch_image_loss: the statistics pass, the scalars {loss, l1, ssim, mse} into out and, when grad is not
+// nullptr, the gradient pass through maps (9 x width x height floats); every pointer a device pointer, rgba and grad
+// (and a 4-channel target) 16-byte aligned. image_loss_window: the 11 window weights (host only).
+uint32_t image_loss_tiles(uint32_t width, uint32_t height);
+void launch_image_loss(hipStream_t s, uint32_t width, uint32_t height, const float* rgba, const float* target,
+                       uint32_t target_channels, float lambda, double* partial, float* maps, float* out, float* grad);
+void image_loss_window(float out[11]);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into
 inline float* framebuffer_of(gsrt_ctx* ctx) { return ctx->fb_view ? ctx->fb_view : ctx->d_fb; }
 // the prep stream must not overtake what is on ctx->stream now (scene upload/update, BVH build/refit)

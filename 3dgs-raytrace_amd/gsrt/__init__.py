@@ -75,6 +75,7 @@ EXPORTS = [
     "gsrt_debug_frame_refusal_kind", "gsrt_render_splat_depth_grad", "gsrt_render_splat_depth_grad_async",
     "gsrt_splat_depth_grad_to_model", "gsrt_splat_depth_grad_to_model_async", "gsrt_debug_frame_refusal_any",
     "gsrt_density_stats_add", "gsrt_density_stats_add_async", "gsrt_densify_count", "gsrt_densify", "gsrt_densify_async",
+    "gsrt_image_loss", "gsrt_image_loss_async", "gsrt_image_loss_window",
 ]
 
 
@@ -208,6 +209,9 @@ def _load():
         "gsrt_densify_count": ([P, u32, P, P, P, P, P], i32),
         "gsrt_densify": ([P, P, u32, P, P, P, P, P, u32, P], i32),
         "gsrt_densify_async": ([P, P, u32, P, P, P, P, P, u32, P], i32),
+        "gsrt_image_loss": ([P, u32, u32, P, P, u32, f32, P, P], i32),
+        "gsrt_image_loss_async": ([P, u32, u32, P, P, u32, f32, P, P], i32),
+        "gsrt_image_loss_window": ([P], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -632,6 +636,48 @@ def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features
     if o[4] is not None:
         o[4] = o[4].reshape((k,) + tuple(sh_shape))
     return o[0], o[1], o[2], o[3], o[4], o[5], org[:k]
+
+
+def image_loss_window() -> np.ndarray:
+    """the 11 weights of image_loss's 1-D Gaussian window (sigma 1.5, sum 1) as float32 (gsrt_image_loss_window)"""
+    out = np.zeros(11, np.float32)
+    _check(lib.gsrt_image_loss_window(_p(out)))
+    return out
+
+
+def image_loss(ctx, rgba, target, lam=0.2, want_grad=True, *, width=None, height=None, target_channels=None, d_out=0,
+               d_grad=0, asynchronous=False):
+    """The photometric loss of a frame against a target image in one fused call (gsrt_image_loss; the formulas are in
+    gsrt.h): loss = (1 - lam) l1 + lam (1 - ssim) with 3DGS's SSIM (11 x 11 Gaussian window, zero padding), and its
+    gradient with respect to the frame.
+    numpy arrays: rgba (H, W, 4) as Scene.render returns it, target (H, W, 3) or (H, W, 4). Returns (dict(loss=, l1=,
+    ssim=, mse=), grad): grad is d loss / d rgba as (H, W, 4) float32 with a zero alpha slot, the grad_image that
+    Scene.splat_grad, Scene.sh_grad and Scene.opacity_grad take, or None with want_grad=False.
+    device addresses (int): width, height and target_channels are needed. With d_grad, the address of H x W x 4 floats,
+    the gradient is written there (0: no gradient; want_grad is not read). Blocks and returns the dict. With d_out, the
+    address of 4 floats, the scalars {loss, l1, ssim, mse} are written there instead and None is returned; then
+    asynchronous=True only enqueues the call on ctx.stream (gsrt_image_loss_async) without waiting."""
+    if isinstance(rgba, int) or isinstance(target, int):
+        if width is None or height is None or target_channels is None:
+            raise GsrtError(E_ARG, "image_loss: device addresses need width, height and target_channels")
+        if asynchronous or d_out:
+            _check(lib.gsrt_image_loss_async(ctx.handle, width, height, _addr(rgba), _addr(target), target_channels, lam,
+                                             _addr(d_out), _addr(d_grad)), ctx)
+            if not asynchronous:
+                ctx.synchronize()
+            return None
+        out = np.zeros(4, np.float32)
+        _check(lib.gsrt_image_loss(ctx.handle, width, height, _addr(rgba), _addr(target), target_channels, lam, _p(out),
+                                   _addr(d_grad)), ctx)
+        return dict(loss=float(out[0]), l1=float(out[1]), ssim=float(out[2]), mse=float(out[3]))
+    x = np.ascontiguousarray(rgba, dtype=np.float32)
+    y = np.ascontiguousarray(target, dtype=np.float32)
+    if x.ndim != 3 or x.shape[2] != 4 or y.ndim != 3 or y.shape[:2] != x.shape[:2] or y.shape[2] not in (3, 4):
+        raise GsrtError(E_ARG, "image_loss: rgba is an (H, W, 4) array and target an (H, W, 3) or (H, W, 4) one")
+    out = np.zeros(4, np.float32)
+    grad = np.zeros(x.shape, np.float32) if want_grad else None
+    _check(lib.gsrt_image_loss(ctx.handle, x.shape[1], x.shape[0], _p(x), _p(y), y.shape[2], lam, _p(out), _p(grad)), ctx)
+    return dict(loss=float(out[0]), l1=float(out[1]), ssim=float(out[2]), mse=float(out[3])), grad
 
 
 # ---------------------------------------------------------------- context / scene

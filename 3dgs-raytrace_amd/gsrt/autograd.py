@@ -21,6 +21,17 @@ and adaptive density control between steps: render_model(..., density_stats=t) a
 in its backward, densify clones, splits and prunes the model on the device, remap_state carries optimiser state across
 (the whole loop: densify's docstring).
 
+and the loss itself: photometric_loss is 3DGS's (1 - lam) L1 + lam (1 - SSIM) of a frame against a target image in one
+fused call (gsrt.image_loss), so that a training step stays in the library's kernels from the frame to the gradients:
+
+    from gsrt.autograd import render_model, photometric_loss, image_metrics
+    for step in range(steps):
+        rgba = render_model(scene, ubo, center, rot, scale, opacity, sh, density_stats=stats)
+        loss = photometric_loss(ctx, rgba, target, lam=0.2)   # target: (H, W, 3) or (H, W, 4) float32 GPU tensor
+        loss.backward()                                       # d loss / d rgba goes straight into the gradient frames
+        optimiser.step()
+    image_metrics(ctx, rgba.detach(), target)                 # dict(loss=, l1=, ssim=, mse=, psnr=), no gradient
+
 torch is imported here only; `import gsrt` never needs it.
 
 Synchronisation is plain and blocking: the current torch stream is synchronised before the library reads a tensor, and
@@ -29,7 +40,9 @@ Context.synchronize() returns before torch reads what the library wrote. The lib
 """
 import torch
 
-from . import MODE_COR, density_stats_add
+import math
+
+from . import MODE_COR, density_stats_add, image_loss
 from . import densify as _densify
 
 
@@ -403,3 +416,55 @@ def remap_state(t, origin):
     out = torch.zeros((origin.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
     out[kept] = t[origin[kept]]
     return out
+
+
+def _check_images(name, rgba, target):
+    if rgba.dtype != torch.float32 or not rgba.is_cuda or rgba.dim() != 3 or rgba.shape[2] != 4:
+        raise ValueError(f"{name}: rgba must be an (H, W, 4) float32 tensor on the GPU")
+    if (target.dtype != torch.float32 or target.device != rgba.device or target.dim() != 3 or
+            tuple(target.shape[:2]) != tuple(rgba.shape[:2]) or target.shape[2] not in (3, 4)):
+        raise ValueError(f"{name}: target must be an (H, W, 3) or (H, W, 4) float32 tensor on rgba's device")
+
+
+class _PhotometricLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgba, target, gctx, lam):
+        x, y = rgba.detach().contiguous(), target.detach().contiguous()
+        H, W = int(x.shape[0]), int(x.shape[1])
+        out = torch.empty((4,), dtype=torch.float32, device=x.device)
+        grad = torch.empty((H, W, 4), dtype=torch.float32, device=x.device)
+        torch.cuda.current_stream(x.device).synchronize()
+        image_loss(gctx, x.data_ptr(), y.data_ptr(), lam, width=W, height=H, target_channels=int(y.shape[2]),
+                   d_out=out.data_ptr(), d_grad=grad.data_ptr(), asynchronous=True)
+        gctx.synchronize()
+        ctx.save_for_backward(grad)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (kept,) = ctx.saved_tensors
+        return grad_output * kept, None, None, None
+
+
+def photometric_loss(ctx, rgba, target, lam=0.2):
+    """3DGS's photometric loss (1 - lam) l1 + lam (1 - ssim) of a frame `rgba` ((H, W, 4) float32 GPU tensor, e.g.
+    render_model's; alpha is not read) against `target` ((H, W, 3) or (H, W, 4) float32 GPU tensor), as a 0-dim tensor
+    that is differentiable with respect to `rgba`. ctx: the gsrt.Context. The forward is one fused call
+    (gsrt.image_loss, gsrt_image_loss_async; the formulas are in gsrt.h) that also computes d loss / d rgba and keeps it;
+    the backward returns the upstream scalar times the kept gradient and nothing for `target`. The alpha slot of the
+    gradient is zero. Blocking synchronisation on both sides: torch's current stream before the library call,
+    Context.synchronize() after it."""
+    _check_images("photometric_loss", rgba, target)
+    return _PhotometricLoss.apply(rgba, target, ctx, float(lam))
+
+
+def image_metrics(ctx, rgba, target, lam=0.2):
+    """The scalars of photometric_loss without a gradient, for evaluation: dict(loss=, l1=, ssim=, mse=, psnr=) of
+    Python floats, psnr = -10 log10(mse) for images in [0, 1] (inf when mse is 0). The gradient pass is skipped."""
+    _check_images("image_metrics", rgba, target)
+    x, y = rgba.detach().contiguous(), target.detach().contiguous()
+    torch.cuda.current_stream(x.device).synchronize()
+    m = image_loss(ctx, x.data_ptr(), y.data_ptr(), lam, width=int(x.shape[1]), height=int(x.shape[0]),
+                   target_channels=int(y.shape[2]))
+    m["psnr"] = -10.0 * math.log10(m["mse"]) if m["mse"] > 0.0 else math.inf
+    return m

@@ -586,6 +586,47 @@ gsrt_status gsrt_densify_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint3
                                const float* d_noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
                                int32_t* d_origin, uint32_t cap, uint32_t* d_n_out);
 
+/* ---- photometric loss: L1 + D-SSIM of a frame against a target image, with its gradient ---------
+ * The loss of 3DGS's training step in one fused call: rgba is a frame as the renderer leaves it (float[H][W][4], used as
+ * it is, no clamp; alpha is not read), target a float[H][W][target_channels] image with 3 or 4 channels (a fourth is not
+ * read). Over the N = 3 H W colour values x of rgba and y of target:
+ *     l1   = mean |x - y|,   mse = mean (x - y)^2   (so that PSNR = -10 log10(mse) comes free)
+ *     ssim = mean of map, 3DGS's SSIM per channel: with conv the 11 x 11 Gaussian window (sigma 1.5; the product of two
+ *            entries of gsrt_image_loss_window's table) over the image padded with 5 zeros on every side (conv2d(padding=5):
+ *            border pixels see zeros, the window is not renormalised),
+ *                mu1 = conv(x), mu2 = conv(y), s1 = conv(x x) - mu1^2, s2 = conv(y y) - mu2^2, s12 = conv(x y) - mu1 mu2,
+ *                map = ((2 mu1 mu2 + C1) (2 s12 + C2)) / ((mu1^2 + mu2^2 + C1) (s1 + s2 + C2)),  C1 = 0.01^2, C2 = 0.03^2
+ *     loss = (1 - lambda) l1 + lambda (1 - ssim),   lambda in [0, 1] (3DGS: 0.2)
+ * out = {loss, l1, ssim, mse}. The per-pixel terms are float32 (every operation rounded on its own except the window
+ * sums, which are fused multiply-adds, rows first, then columns); they are summed in double in a fixed order and each
+ * scalar is rounded to float once.
+ * grad_image (nullable): float[H][W][4] = d loss / d rgba, in the layout and meaning of the grad_image of
+ * gsrt_render_splat_grad, gsrt_render_sh_grad and gsrt_render_opacity_grad, which take it as it is: per colour value
+ *     (1 - lambda) / N * sign(x - y)  -  lambda / N * d (sum of map) / d x
+ * with sign(0) = 0 (torch's convention; a NaN difference stays a NaN), the second term the exact derivative of the
+ * formula above (zero padding included), and +0 in the alpha slot. The scale is that of the mean: a caller who weights
+ * the loss multiplies the gradient by the same weight. Every pixel is a gather over its own 11 x 11 neighbourhood and
+ * nothing is added atomically: the same inputs give the same bits, scalars and gradient alike. Without grad_image the
+ * scalars are the same bits and the gradient pass is skipped.
+ * rgba, target and grad_image are all host pointers or all device pointers (on the device rgba, grad_image and a
+ * 4-channel target 16-byte aligned, as hipMalloc and torch give them); out is a host pointer. The call runs on
+ * gsrt_stream(), behind the frame that wrote rgba (gsrt_framebuffer's pointer is a valid rgba), and blocks until out and
+ * grad_image are complete. Any width, height >= 1 works, images smaller than the window included.
+ * GSRT_E_ARG, with nothing written: a NULL ctx, rgba, target or out; width or height 0 or above 32768 (the renderer's
+ * limit); target_channels not 3 or 4; lambda outside [0, 1] or NaN; host and device pointers mixed; grad_image
+ * overlapping rgba or target. */
+gsrt_status gsrt_image_loss(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const float* target,
+                            uint32_t target_channels, float lambda, float out[4], float* grad_image);
+/* the same, enqueued on gsrt_stream() without a host synchronisation: it queues behind the frame that wrote d_rgba and
+ * ahead of the gradient frame that reads d_grad_image. Device pointers only, d_out (4 floats) included. (A call for a
+ * larger frame than any before it on this ctx allocates its workspace first.) */
+gsrt_status gsrt_image_loss_async(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_rgba,
+                                  const float* d_target, uint32_t target_channels, float lambda, float* d_out,
+                                  float* d_grad_image);
+/* the 1-D window of gsrt_image_loss: exp(-(i - 5)^2 / (2 * 1.5^2)), i = 0..10, normalised to sum 1 in double and each
+ * rounded to float once (a constant table; no device or ctx needed) */
+gsrt_status gsrt_image_loss_window(float out[11]);
+
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into
