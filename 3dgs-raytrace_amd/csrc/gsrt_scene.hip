@@ -121,7 +121,8 @@ void launch_project(hipStream_t st, uint32_t n, uint32_t mode, const gsrt_ubo& u
 //   dL/dT = 2 W T Sigma = 2 W [u0; u1], T0 = j02 MVz + j00 MVx, T1 = j12 MVz + j11 MVy with
 //   j00 = fx id, j02 = (fx t0) id^2, j11 = fy id, j12 = (fy t1) id^2, id = 1 / depth = -1 / t2,
 //   ppx = (ph0 / ph3 + 1) W / 2, ppy likewise, ph = P t with the general P, t = MV (c, 1),
-// and the centre's gradient is MV^T dL/dt. An invalid splat (depth <= 0 or det <= 0) gets +0. No atomics.
+// and the centre's gradient is MV^T dL/dt. An invalid splat (depth <= 0 or det <= 0) gets +0, and so does a valid one
+// whose row is all +0 (no ray reached it): a zero is written as +0. No atomics.
 // The longest chain of rounded operations from the inputs to an output (the tests' N) ends in a centre entry by way of
 // the conic: t (4), id (1), id^2 (1), j02 (1), T0 (1), u0 (3), v00 (4), det (1), 1 / det (1), A (1), Q G (2), W (2),
 // dL/dT0 (2), dL/dj02 (3), dL/d(id) (4), dL/dt2 (1), + the ppx, ppy part (1), MV^T dL/dt (4): 37.
@@ -216,10 +217,12 @@ __global__ __launch_bounds__(256) void k_splat_grad_to_model(uint32_t n, const g
     }
     float* oc = grad_center + 3 * (size_t)i;
     float* ov = grad_cov + 6 * (size_t)i;
+    // + 0.0f: a zero result is written as +0 whatever the signs of its terms. A valid Gaussian that no ray reached has a
+    // row of +0, W = -Q G Q of it is -0, and sums of products with it come out as -0 wherever every term is negative.
 #pragma unroll
-    for (int k = 0; k < 3; ++k) oc[k] = accumulate ? oc[k] + dc[k] : dc[k];
+    for (int k = 0; k < 3; ++k) oc[k] = accumulate ? oc[k] + dc[k] : dc[k] + 0.0f;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) ov[k] = accumulate ? ov[k] + dS[k] : dS[k];
+    for (int k = 0; k < 6; ++k) ov[k] = accumulate ? ov[k] + dS[k] : dS[k] + 0.0f;
 }
 
 void launch_splat_grad_to_model(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params,

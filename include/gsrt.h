@@ -443,8 +443,9 @@ gsrt_status gsrt_render_splat_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo,
  * are read, a borrowed array included (gsrt_scene_attach). One lane per Gaussian recomputes the projection's float32
  * intermediates: V = T Sigma T^T + 0.3 I with the 0.3 a constant, Q = V^-1, dL/dV = -Q [[dA, dB/2], [dB/2, dC]] Q; the
  * centre receives its part through (ppx, ppy), with the general projection matrix, and through T's dependence on the
- * view-space position. A Gaussian the projection marks invalid (depth <= 0 or det <= 0) gets +0. Nothing flows through
- * the depth key, the AABB or the footprint. No atomics: the result is deterministic.
+ * view-space position. A Gaussian the projection marks invalid (depth <= 0 or det <= 0) gets +0, and with accumulate == 0
+ * so does every entry that comes out as zero, those of a Gaussian whose row is all +0 (no ray reached it) among them.
+ * Nothing flows through the depth key, the AABB or the footprint. No atomics: the result is deterministic.
  * accumulate == 0: both tables are written. accumulate != 0: added to; device tables only. All three tables are host or
  * device pointers (ordinary device memory), each on its own.
  * GSRT_E_ARG: a NULL pointer; a host table with accumulate; a scene with a mesh. GSRT_E_STATE: before gsrt_build_bvh, as

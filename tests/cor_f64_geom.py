@@ -5,6 +5,8 @@ Two steps, as the library takes them (include/gsrt.h, gsrt_render_splat_grad and
                    of g = (A dx^2 + 2 B dx dy + C dy^2) / 2, dx = px - ppx, dy = py - ppy; it walks the hit lists of
                    cor_f64 (_tiles, _hits, _walk: imported, not copied) and forms dL/d alpha_i as cor_f64.gradients does;
   model_chain:     those five numbers back through the projection to the centre and the six cov3d entries.
+And the step torch takes in gsrt.autograd.render_model, by hand:
+  param_chain:     the six cov3d entries back to the rotation (a quaternion, used as given) and the scales.
 project() restates the projection from (centre, cov3d) with its own formulas; a test holds it to cor_f64.Splats.
 
 Everything is numpy float64. Nothing here shares a value or an operation order with the HIP kernels.
@@ -197,4 +199,87 @@ def model_chain(ubo, center, cov, rows):
     out.M2_center, out.M2_cov = _chain(p, rows, True)
     out.valid = p.valid
     out.kappa = np.where(p.valid, p.V[:, 0, 0] * p.V[:, 1, 1] / np.where(p.valid, p.det, 1.0), 0.0)
+    return out
+
+
+def _rotation(rot):
+    """R (n, 3, 3) as [n, k, i] (row k, column i), the quaternion polynomial of cor_f64.covariance's Sigma_ij = sum_k s_k^2
+    R_ki R_kj with q = (r, x, y, z) as given; Rabs, the same polynomial with every product by its absolute value and every
+    difference as a sum; dR[c], the derivative of every entry with respect to q_c, written out entry by entry."""
+    q = np.asarray(rot, np.float64)
+    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    o = np.zeros_like(r)
+
+    def mat(rows):
+        return np.stack([np.stack(row, -1) for row in rows], -2)
+
+    R = mat([[1 - 2 * (y * y + z * z), 2 * (x * y + r * z), 2 * (x * z - r * y)],
+             [2 * (x * y - r * z), 1 - 2 * (x * x + z * z), 2 * (y * z + r * x)],
+             [2 * (x * z + r * y), 2 * (y * z - r * x), 1 - 2 * (x * x + y * y)]])
+    a = np.abs
+    Rabs = mat([[1 + 2 * (y * y + z * z), 2 * (a(x * y) + a(r * z)), 2 * (a(x * z) + a(r * y))],
+                [2 * (a(x * y) + a(r * z)), 1 + 2 * (x * x + z * z), 2 * (a(y * z) + a(r * x))],
+                [2 * (a(x * z) + a(r * y)), 2 * (a(y * z) + a(r * x)), 1 + 2 * (x * x + y * y)]])
+    dR = [mat([[o, 2 * z, -2 * y], [-2 * z, o, 2 * x], [2 * y, -2 * x, o]]),               # d / dr
+          mat([[o, 2 * y, 2 * z], [2 * y, -4 * x, 2 * r], [2 * z, -2 * r, -4 * x]]),       # d / dx
+          mat([[-4 * y, 2 * x, -2 * r], [2 * x, o, 2 * z], [2 * r, 2 * z, -4 * y]]),       # d / dy
+          mat([[-4 * z, 2 * r, 2 * x], [-2 * r, -4 * z, 2 * y], [2 * x, 2 * y, o]])]       # d / dz
+    return R, Rabs, dR
+
+
+def covariance_magnitude(rot, scale):
+    """(n, 6) in cov3d order: sum_k s_k^2 Rabs_ki Rabs_kj, the sum of the absolute values of the products that
+    cor_f64.covariance's Sigma_ij = sum_k s_k^2 R_ki R_kj sums, R's own polynomial taken apart (Rabs of _rotation)"""
+    s = np.asarray(scale, np.float64)
+    Rabs = _rotation(rot)[1]
+    return cov6(np.einsum("nk,nki,nkj->nij", s * s, Rabs, Rabs))
+
+
+def scale_chain(r, s, dcov, mcov):
+    """dL/d(scale) from dL/d(cov3d) by hand: Sigma_ij = sum_k s_k^2 R_ki R_kj (cor_f64.covariance), so dSigma_ij / ds_k =
+    2 s_k R_ki R_kj; a cov3d off-diagonal gradient already counts both places. Second result: the sum of absolute products,
+    with R's entries as they are (param_chain's M_scale takes R's own terms apart as well)."""
+    R = _rotation(r)[0]
+    # R's convention checked against covariance itself
+    np.testing.assert_allclose(np.einsum("nk,nki,nkj->nij", s * s, R, R), F.covariance(r, s), rtol=1e-12, atol=1e-18)
+    g, m = np.zeros_like(s), np.zeros_like(s)
+    for e, (i, j) in enumerate(COV_IJ):
+        term = 2 * s * R[:, :, i] * R[:, :, j]  # (n, k)
+        g += dcov[:, e, None] * term
+        m += mcov[:, e, None] * np.abs(term)
+    return g, m
+
+
+class ParamChain:
+    """What param_chain returns: scale (n, 3), rot (n, 4), M_scale, M_rot (the same shapes)"""
+
+
+def param_chain(rot, scale, dcov, mcov):
+    """cov3d backwards to the parameters in float64: dcov (n, 6) = dL/d(cov3d) to dL/d(scale) (n, 3) and dL/d(rot) (n, 4),
+    rot = (r, x, y, z) taken as given, not normalised (R is a polynomial in it, and the gradient has a radial part).
+    From Sigma_ij = sum_k s_k^2 R_ki R_kj, cov3d slot e = Sigma_ij for (i, j) = COV_IJ[e] (an off-diagonal slot is one
+    variable, so dcov[e] is taken once):
+        dL/ds_k  = sum_e dcov_e 2 s_k R_ki R_kj
+        dL/dR_ka = sum_e dcov_e s_k^2 ([a == i] R_kj + [a == j] R_ki)
+        dL/dq_c  = sum_ka dL/dR_ka dR_ka/dq_c
+    M_scale, M_rot: the same sums fed mcov (the magnitudes of dcov, e.g. model_chain's M2_cov) with every factor by its
+    absolute value and every difference as a sum, R's own polynomial included (Rabs), as _chain(..., absolute=True) forms
+    M2 for the projection."""
+    s = np.asarray(scale, np.float64)
+    dcov, mcov = np.asarray(dcov, np.float64), np.asarray(mcov, np.float64)
+    R, Rabs, dR = _rotation(rot)
+    out = ParamChain()
+    out.scale, out.M_scale = np.zeros_like(s), np.zeros_like(s)
+    gR, mR = np.zeros_like(R), np.zeros_like(R)
+    s2 = s * s
+    for e, (i, j) in enumerate(COV_IJ):
+        d, m = dcov[:, e, None], mcov[:, e, None]
+        out.scale += d * (2 * s * R[:, :, i] * R[:, :, j])
+        out.M_scale += m * (2 * np.abs(s) * Rabs[:, :, i] * Rabs[:, :, j])
+        gR[:, :, i] += d * s2 * R[:, :, j]
+        gR[:, :, j] += d * s2 * R[:, :, i]
+        mR[:, :, i] += m * s2 * Rabs[:, :, j]
+        mR[:, :, j] += m * s2 * Rabs[:, :, i]
+    out.rot = np.stack([(gR * dR[c]).sum((1, 2)) for c in range(4)], -1)
+    out.M_rot = np.stack([(mR * np.abs(dR[c])).sum((1, 2)) for c in range(4)], -1)
     return out

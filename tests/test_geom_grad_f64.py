@@ -3,7 +3,9 @@ comparison, tests/test_geom_grad_gpu.py, holds the splat gradient frame and the 
 
 project() against cor_f64.Splats; model_chain() against central differences of project(); the two steps together against
 central differences of <G, cor_f64.render> in centres and scales; slot 5 against cor_f64.gradients' opacity gradient; and
-the conditioning kappa_g the GPU chain test's bound relies on.
+the conditioning kappa_g the GPU chain test's bound relies on; param_chain (cov3d back to the quaternion and the scales)
+against central differences of cor_f64.covariance, and its power against the faults the glue of
+gsrt.autograd.render_model could have (tests/test_model_grad_gpu.py holds every gradient of render_model to it).
 """
 import numpy as np
 import pytest
@@ -73,24 +75,6 @@ def test_model_chain_matches_central_differences():
     assert not got.center[~v].any() and not got.cov[~v].any()
 
 
-def _scale_chain(r, s, dcov, mcov):
-    """dL/d(scale) from dL/d(cov3d) by hand: Sigma_ij = sum_k s_k^2 R_ki R_kj (cor_f64.covariance), so dSigma_ij / ds_k =
-    2 s_k R_ki R_kj; a cov3d off-diagonal gradient already counts both places. Second result: the sum of absolute products."""
-    q = np.asarray(r, np.float64)
-    rr, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-    R = np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y + rr * z), 2 * (x * z - rr * y)], -1),
-                  np.stack([2 * (x * y - rr * z), 1 - 2 * (x * x + z * z), 2 * (y * z + rr * x)], -1),
-                  np.stack([2 * (x * z + rr * y), 2 * (y * z - rr * x), 1 - 2 * (x * x + y * y)], -1)], -2)  # [n, k, i]
-    # R's convention checked against covariance itself
-    np.testing.assert_allclose(np.einsum("nk,nki,nkj->nij", s * s, R, R), F.covariance(r, s), rtol=1e-12, atol=1e-18)
-    g, m = np.zeros_like(s), np.zeros_like(s)
-    for e, (i, j) in enumerate(Q.COV_IJ):
-        term = 2 * s * R[:, :, i] * R[:, :, j]  # (n, k)
-        g += dcov[:, e, None] * term
-        m += mcov[:, e, None] * np.abs(term)
-    return g, m
-
-
 def test_whole_gradient_matches_central_differences():
     """d<G, rgba>/d(centre) and /d(scale) by central differences of F.render for the eight Gaussians with the largest M
     (slots 0..4 summed), 18x18 at 1 spp, G zero on the float32-sensitive pixels. An entry's step starts at 1e-5 and is
@@ -106,7 +90,7 @@ def test_whole_gradient_matches_central_differences():
     cov = Q.cov6(F.covariance(r, s))
     ch = Q.model_chain(ubo, c, cov, sg.rows)
     mm = Q.model_chain(ubo, c, cov, sg.M)
-    gs, ms = _scale_chain(r, s, ch.cov, mm.M2_cov)
+    gs, ms = Q.scale_chain(r, s, ch.cov, mm.M2_cov)
     picked = np.argsort(-sg.M[:, :5].sum(1))[:8]
     assert (sg.M[picked, :5].sum(1) > 0).all() and ch.valid[picked].all()
     worst = 0.0
@@ -131,6 +115,121 @@ def test_whole_gradient_matches_central_differences():
             worst = max(worst, abs(fd - want) / M)
             assert abs(fd - want) <= 1e-6 * M, (int(g), what, k, h, fd, want, M)
     print(f"whole gradient against central differences: worst error / M = {worst:.3g}")
+
+
+# ---- the parameter chain, cov3d -> (rot, scale), and what tests/test_model_grad_gpu.py allows gsrt.autograd.render_model
+EPS = 2.0 ** -24
+GPU_CHAIN_OPS = 37  # tests/test_geom_grad_gpu.py's CHAIN_OPS (k_splat_grad_to_model); test_model_grad_gpu.py asserts it
+KAPPA = 1.7  # the scene's largest kappa_g (test_scene_is_well_conditioned prints it; the GPU tests' bounds use it)
+# The longest chain of rounded float32 operations in torch's backward of gsrt.autograd.model_covariance as it is written,
+# from (rot, scale, the upstream gradient) to an output, a product counting one more than its two factors together:
+#   R_ki 3 (two products at once, their sum, 1 - 2 (.); the doubling is exact), M = s R 4;
+#   dL/dM_ki: einsum's backward, one matrix product per operand: M 4, the product 5, three terms 7, both operands' 8;
+#   scale: sum_i dL/dM_ki R_ki: 8 + 3, the product 12, three terms 14;
+#   rot:   dL/dR_ki = s_k dL/dM_ki 9, times the other factor of a quaternion product (exact input; doublings exact) 10,
+#          and x (y, z alike) stands in ten such products (x y, x z and r x twice each, x x twice, both factors each
+#          time), which autograd adds one after the other: 9 more, 19. r stands in six: 15.
+N_TORCH = {"scale": 14, "rot": 19}
+
+
+def model_tol(chain_ops=GPU_CHAIN_OPS):
+    """render_model's cov3d and centre gradients against float64, in units of M2: one GPU splat gradient frame against
+    float64 (the 1e-3 M the row tests hold; the chain is linear in the rows, so M2 of M carries it), and the chain
+    kernel's bound plus as much again for float32 parameters that differ from the reference's in their last bits:
+    test_render_model_backward's arithmetic with one frame instead of two."""
+    return S.TOL + 2 * chain_ops * (1 + KAPPA) * EPS
+
+
+def _fd_param_chain(r, s, dcov):
+    """central differences of L = sum_g <dcov_g, cov6(F.covariance(r, s))_g>, one coordinate of every Gaussian at once (a
+    Gaussian's cov3d depends on its own seven numbers only): (n, 3) for the scales, (n, 4) for the quaternion. L is a
+    quadratic in each s_k, so its central difference is exact at any step and h = 1e-3 max_k s_k keeps the rounding of the
+    difference (eps |L| / h) small against the smallest scale's M; in a quaternion entry L is a quartic: h = 1e-5."""
+    def L(rr, ss):
+        return (dcov * Q.cov6(F.covariance(rr, ss))).sum(1)
+
+    gs, gq = np.zeros_like(s), np.zeros_like(r)
+    hs = 1e-3 * s.max(1)
+    for k in range(3):
+        d = np.zeros_like(s)
+        d[:, k] = hs
+        gs[:, k] = (L(r, s + d) - L(r, s - d)) / (2 * hs)
+    for k in range(4):
+        d = np.zeros_like(r)
+        d[:, k] = 1e-5
+        gq[:, k] = (L(r + d, s) - L(r - d, s)) / 2e-5
+    return gs, gq
+
+
+@pytest.mark.parametrize("quats", ["unit", "scaled"])
+def test_param_chain_matches_central_differences(quats):
+    """param_chain against central differences of <dcov, cov6(F.covariance(r, s))> for random dcov, on the scene's own
+    rotations and scales and with every quaternion scaled by a factor in [0.5, 1.5] (the radial part of the gradient, which
+    a normalising parametrisation would not have). Bound: 1e-6 M, as test_model_chain_matches_central_differences."""
+    _, r, s, _, _ = _model()
+    rng = np.random.default_rng(53)
+    if quats == "scaled":
+        r = r * rng.uniform(0.5, 1.5, (S.N, 1))
+    dcov = rng.uniform(-1.0, 1.0, (S.N, 6))
+    got = Q.param_chain(r, s, dcov, np.abs(dcov))
+    gs, gq = _fd_param_chain(r, s, dcov)
+    ws = float((np.abs(gs - got.scale) / got.M_scale).max())
+    wq = float((np.abs(gq - got.rot) / got.M_rot).max())
+    print(f"param_chain ({quats} quaternions) against central differences: worst error / M = {ws:.3g} (scale), {wq:.3g} (rot)")
+    assert (got.M_scale > 0).all() and (got.M_rot > 0).all()
+    assert ws <= 1e-6 and wq <= 1e-6
+    assert (np.abs(got.scale) <= got.M_scale * (1 + 1e-12)).all() and (np.abs(got.rot) <= got.M_rot * (1 + 1e-12)).all()
+    # the scale part is the chain test_whole_gradient_matches_central_differences uses; its M takes R's entries whole
+    g2, m2 = Q.scale_chain(r, s, dcov, np.abs(dcov))
+    np.testing.assert_allclose(got.scale, g2, rtol=1e-12, atol=0)
+    assert (m2 <= got.M_scale * (1 + 1e-12)).all()
+    if quats == "scaled":  # the radial part is there: q . dL/dq = 2 <dL/dR, R - I> for R = I + a quadratic in q
+        radial = (r * got.rot).sum(1)
+        assert (np.abs(radial) > 1e-3 * (np.abs(r) * got.M_rot).sum(1)).sum() > S.N // 2
+
+
+def wrong_param_chains(r, s, dcov, mcov):
+    """the reference chain fed the faults the glue of render_model could have: name -> (scale, rot)"""
+    conj = r * np.array([1.0, -1.0, -1.0, -1.0])
+    off = np.array([1.0, 0.5, 0.5, 1.0, 0.5, 1.0])
+    out = {}
+    for name, d in (("slots xz and yy swapped", dcov[:, [0, 1, 3, 2, 4, 5]]), ("off-diagonals halved", dcov * off),
+                    ("off-diagonals doubled", dcov / off)):
+        w = Q.param_chain(r, s, d, mcov)
+        out[name] = (w.scale, w.rot)
+    w = Q.param_chain(conj, s, dcov, mcov)  # R of the conjugate is R transposed
+    out["R transposed"] = (w.scale, w.rot * np.array([1.0, -1.0, -1.0, -1.0]))
+    true = Q.param_chain(r, s, dcov, mcov)
+    q2 = (r * r).sum(1, keepdims=True)
+    out["radial part dropped"] = (true.scale, true.rot - r * (r * true.rot).sum(1, keepdims=True) / q2)
+    return out
+
+
+def test_param_chain_power():
+    """In the manner of test_grad_f64.test_power: the float64 chain of CASES[0] (G as the GPU tests form it) fed each fault
+    of wrong_param_chains differs from the true one by more than ten times test_model_grad_gpu.py's bound, (model_tol() +
+    N_TORCH 2^-24) M, on a reached entry of scale.grad or rot.grad. Factors measured (error / bound, scale and rot): slots
+    swapped 129 and 85; off-diagonals halved 35 and 27; doubled 70 and 53; R transposed 154 and 83; radial part dropped 0
+    (it does not touch the scales) and 134: none needs another seed or case."""
+    case = S.CASES[0]
+    c, r, s, o, sh = _model()
+    ubo = S.camera(*case)
+    G = S.upstream(case, 4, 201 + case[3])  # test_grad_f64_gpu.reference's
+    sg = Q.splat_gradients(ubo, c, r, s, o, sh, G_rgba=G)
+    cov = Q.cov6(F.covariance(r, s))
+    ch, mm = Q.model_chain(ubo, c, cov, sg.rows), Q.model_chain(ubo, c, cov, sg.M)
+    true = Q.param_chain(r, s, ch.cov, mm.M2_cov)
+    bs = (model_tol() + N_TORCH["scale"] * EPS) * true.M_scale
+    bq = (model_tol() + N_TORCH["rot"] * EPS) * true.M_rot
+    reached_s, reached_q = true.M_scale > 0, true.M_rot > 0
+    assert reached_s.sum() > reached_s.size // 4 and reached_q.sum() > reached_q.size // 4
+    for name, (ws, wq) in wrong_param_chains(r, s, ch.cov, mm.M2_cov).items():
+        fs = float((np.abs(ws - true.scale)[reached_s] / bs[reached_s]).max())
+        fq = float((np.abs(wq - true.rot)[reached_q] / bq[reached_q]).max())
+        print(f"param chain with {name}: worst error / bound = {fs:.3g} (scale), {fq:.3g} (rot)")
+        assert max(fs, fq) >= 10.0, name
+        if name != "radial part dropped":
+            assert fs >= 10.0 and fq >= 10.0, name
 
 
 @pytest.mark.parametrize("with_sh", [True, False])

@@ -4,7 +4,8 @@ in tests/test_image_loss_ref.py.
 
 Shapes (W x H), for a kernel with tiles of 32 x 16 pixels and a 5-pixel halo: 1 x 1; 5 x 7 (the window overhangs on every
 side); 11 x 11; 16 x 16; 17 x 33 (three tile rows, the last with one row); 70 x 37 (three tile columns and rows: halos
-cross two tile borders each way); 1 x 70 and 70 x 1; 64 x 64 (whole tiles only).
+cross two tile borders each way); 1 x 70 and 70 x 1; 64 x 64 (whole tiles only); and MANY_TILES, past one trip of the
+scalar reduction's loop, up to the accepted limits of 32768 each way.
 
 Inputs: smooth fields in [0, 1] plus noise, the target the frame plus a perturbation, and, by fractions of the image so
 that every shape has them: a block where target == frame exactly (sign(0)), a flat block of two constants (the variances
@@ -30,6 +31,10 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1), (5, 7), (11, 11), (16, 16), (17, 33), (70, 37), (1, 70), (70, 1), (64, 64)]
 LAMBDAS = [0.0, 0.2, 1.0]
+# W x H of more than 256 tiles, so that a lane of k_loss_scalars adds a second partial sum (lam 0.2 only): 1 x 4097 is 257
+# tiles (lane 0 alone takes two), 530 x 260 is 17 x 17 = 289, ragged both ways, and the accepted limits, 32768 x 1 (1024
+# tiles) and 1 x 32768 (2048)
+MANY_TILES = [(1, 4097), (530, 260), (32768, 1), (1, 32768)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,9 +83,9 @@ def scalars(d):
     return np.array([d["loss"], d["l1"], d["ssim"], d["mse"]], np.float32)
 
 
-@pytest.mark.parametrize("lam", LAMBDAS)
-@pytest.mark.parametrize("channels", [3, 4])
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape,channels,lam", [(s, c, lam) for lam in LAMBDAS for c in (3, 4) for s in SHAPES] +
+                         [(s, c, 0.2) for c in (3, 4) for s in MANY_TILES],
+                         ids=lambda v: f"{v[0]}x{v[1]}" if isinstance(v, tuple) else str(v))
 def test_matches_reference(ctx, shape, channels, lam):
     W, H = shape
     rgba, target, same = images(W, H, channels)
@@ -143,6 +148,47 @@ def test_device_pointers_match_host_pointers(ctx, channels):
     ctx.synchronize()
     assert np.array_equal(bits(out.cpu().numpy()), bits(scalars(want)))
     assert np.array_equal(bits(g.cpu().numpy()), bits(gwant))
+
+
+def test_workspace_regrows(ctx):
+    """A context's loss workspace grows on demand (a stream synchronise first, then the derivative maps lie at another
+    offset): on contexts of their own, a small frame with a gradient, a larger one without (fits), the same with one
+    (regrown), a still larger one (regrown), the small one again. Once through the blocking call and once through
+    gsrt_image_loss_async on device tensors with no synchronise between the calls; every result has the bits of the shared
+    context's result for that shape."""
+    import torch
+
+    order = [((5, 7), True), ((70, 37), False), ((70, 37), True), ((530, 260), True), ((5, 7), True)]
+    want = {shape: gsrt.image_loss(ctx, *images(*shape, 3)[:2], 0.2) for shape, _ in order}
+    own = gsrt.Context(0)
+    try:
+        for (W, H), with_grad in order:
+            rgba, target, _ = images(W, H, 3)
+            out, grad = gsrt.image_loss(own, rgba, target, 0.2, want_grad=with_grad)
+            assert np.array_equal(bits(scalars(out)), bits(scalars(want[W, H][0]))), (W, H, with_grad)
+            assert (grad is None) == (not with_grad)
+            assert grad is None or np.array_equal(bits(grad), bits(want[W, H][1])), (W, H)
+    finally:
+        own.close()
+    own = gsrt.Context(0)
+    try:
+        calls = []
+        for (W, H), with_grad in order:
+            rgba, target, _ = images(W, H, 3)
+            calls.append((W, H, torch.from_numpy(rgba.copy()).to("cuda:0"), torch.from_numpy(target.copy()).to("cuda:0"),
+                          torch.full((4,), 7.0, dtype=torch.float32, device="cuda:0"),
+                          torch.full((H, W, 4), 7.0, dtype=torch.float32, device="cuda:0") if with_grad else None))
+        torch.cuda.synchronize()
+        for W, H, x, y, out, grad in calls:
+            assert gsrt.image_loss(own, x.data_ptr(), y.data_ptr(), 0.2, width=W, height=H, target_channels=3,
+                                   d_out=out.data_ptr(), d_grad=grad.data_ptr() if grad is not None else 0,
+                                   asynchronous=True) is None
+        own.synchronize()
+        for W, H, _, _, out, grad in calls:
+            assert np.array_equal(bits(out.cpu().numpy()), bits(scalars(want[W, H][0]))), (W, H)
+            assert grad is None or np.array_equal(bits(grad.cpu().numpy()), bits(want[W, H][1])), (W, H)
+    finally:
+        own.close()
 
 
 def test_refusals_leave_outputs_untouched(ctx):
