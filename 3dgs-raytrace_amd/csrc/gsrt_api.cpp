@@ -2,9 +2,11 @@
 #include <algorithm>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <new>
 
@@ -1541,6 +1543,295 @@ gsrt_status gsrt_image_loss(gsrt_ctx* ctx, uint32_t width, uint32_t height, cons
     return finish_blocking(ctx, s, {{out, d_out, sizeof(float) * 4, "gsrt_image_loss: scalar download failed"},
                                     {grad_image, d_grad, sizeof(float) * 4 * px, "gsrt_image_loss: gradient download failed"}},
                            &tmpv);
+}
+
+// ---- the optimiser step (gsrt_model_step.hip) -----------------------------------------------------------------------
+// On the render stream, behind the gradient calls that filled the tables. The calls work on model arrays, not on a scene.
+static const char* check_adam(const gsrt_adam_params* A) {
+    if (!A) return "adam is NULL";
+    if (A->step == 0) return "adam.step must be >= 1";
+    if (!(A->beta1 >= 0.0f && A->beta1 < 1.0f) || !(A->beta2 >= 0.0f && A->beta2 < 1.0f)) return "adam.beta1 and beta2 must be in [0, 1)";
+    if (!(A->eps > 0.0f)) return "adam.eps must be > 0";
+    for (float lr : {A->lr_center, A->lr_rot, A->lr_scale, A->lr_opacity, A->lr_sh_dc, A->lr_sh_rest, A->lr_features})
+        if (!(lr >= 0.0f)) return "a learning rate is negative or NaN";
+    if (A->reserved[0] | A->reserved[1] | A->reserved[2] | A->reserved[3]) return "adam.reserved must be zero";
+    if (A->flags & ~GSRT_ADAM_SPARSE) return "an unknown flag in adam.flags";
+    return nullptr;
+}
+
+static void adam_scalars(const gsrt_adam_params& A, gsrt::AdamScalars& K) {
+    const double t = (double)A.step, b1 = (double)A.beta1, b2 = (double)A.beta2;
+    const double c1 = 1.0 - std::pow(b1, t);
+    const float lr[7] = {A.lr_center, A.lr_rot, A.lr_scale, A.lr_opacity, A.lr_sh_dc, A.lr_sh_rest, A.lr_features};
+    K.beta1 = A.beta1;
+    K.beta2 = A.beta2;
+    K.a1 = (float)(1.0 - b1);
+    K.a2 = (float)(1.0 - b2);
+    K.c2 = (float)std::sqrt(1.0 - std::pow(b2, t));
+    K.eps = A.eps;
+    K.frozen = 0;
+    for (int i = 0; i < 7; ++i) {
+        K.ss[i] = (float)((double)lr[i] / c1);
+        if (lr[i] == 0.0f) K.frozen |= 1u << i;
+    }
+    K.flags = A.flags;
+}
+
+gsrt_status gsrt_adam_scalars(const gsrt_adam_params* adam, float out[GSRT_ADAM_SCALARS]) {
+    if (!out || check_adam(adam)) return GSRT_E_ARG;
+    gsrt::AdamScalars K;
+    adam_scalars(*adam, K);
+    out[0] = K.a1;
+    out[1] = K.a2;
+    out[2] = K.c2;
+    for (int i = 0; i < 7; ++i) out[3 + i] = K.ss[i];
+    return GSRT_OK;
+}
+
+// One array of a model call: where its pointer stands (in the call's own copies of the structs), its size, and whether
+// the call reads and writes it. The list drives the NULL, overlap and side checks and the host form's staging.
+struct StepArray {
+    float** slot;
+    size_t bytes;
+    bool in, out;
+};
+
+static void model_set_arrays(std::vector<StepArray>& list, gsrt_model_arrays& a, size_t n, bool in, bool out) {
+    ModelField f[6];
+    const uint32_t nf = model_fields(a, f);
+    for (uint32_t i = 0; i < nf; ++i) list.push_back({&(a.*f[i].member), sizeof(float) * f[i].floats * n, in, out});
+}
+
+// structs that must agree on sh, features and the channel count (a nullptr entry is an absent optional struct)
+static const char* check_model_sets(std::initializer_list<const gsrt_model_arrays*> sets, const gsrt_model_arrays& first) {
+    for (const gsrt_model_arrays* a : sets) {
+        if (!a) continue;
+        if (a->feature_channels > GSRT_MAX_FEATURES || (a->features == nullptr) != (a->feature_channels == 0))
+            return "features need 1..GSRT_MAX_FEATURES channels, NULL exactly with 0 channels";
+        if ((a->sh == nullptr) != (first.sh == nullptr) || a->feature_channels != first.feature_channels)
+            return "the structs must agree on sh, features and feature_channels";
+    }
+    return nullptr;
+}
+
+// NULL arrays (n > 0), overlaps of a written array with any other (same: pairs of slots that may be one array), and the
+// side: 0 host, 1 device, -1 refused
+static int check_step_arrays(gsrt_ctx* ctx, const std::string& name, const std::vector<StepArray>& list, size_t n,
+                             std::initializer_list<std::pair<float**, float**>> same) {
+    if (!n) return 1;
+    for (const StepArray& a : list)
+        if (!*a.slot) return fail(ctx, GSRT_E_ARG, name + "a NULL array"), -1;
+    for (size_t i = 0; i < list.size(); ++i)
+        for (size_t j = i + 1; j < list.size(); ++j) {
+            if (!list[i].out && !list[j].out) continue;
+            const uintptr_t a = reinterpret_cast<uintptr_t>(*list[i].slot), b = reinterpret_cast<uintptr_t>(*list[j].slot);
+            if (!(a < b + list[j].bytes && b < a + list[i].bytes)) continue;
+            bool allowed = false;
+            for (const auto& p : same)
+                if (a == b && ((p.first == list[i].slot && p.second == list[j].slot) ||
+                               (p.first == list[j].slot && p.second == list[i].slot)))
+                    allowed = true;
+            if (!allowed) return fail(ctx, GSRT_E_ARG, name + "an output array overlaps another array of the call"), -1;
+        }
+    size_t on_dev = 0;
+    for (const StepArray& a : list)
+        if (is_device_ptr(*a.slot)) ++on_dev;
+    if (on_dev && on_dev != list.size())
+        return fail(ctx, GSRT_E_ARG, name + "the arrays must all be host pointers or all be device pointers"), -1;
+    return on_dev ? 1 : 0;
+}
+
+// The host form: every array gets a region of one device block (slots that hold the same host array share one), inputs
+// are uploaded, `run` enqueues the kernels on the slots' device pointers, outputs are downloaded, the stream is drained.
+static gsrt_status run_staged(gsrt_ctx* ctx, const std::string& name, std::vector<StepArray>& list,
+                              const std::function<gsrt_status()>& run) {
+    size_t bytes = 0;
+    for (const StepArray& a : list) bytes += Staging::unit(a.bytes);
+    Staging tmp;
+    GSRT_HIP(ctx, hipMalloc(&tmp.base, bytes ? bytes : 16));
+    void* const tmpv = tmp.base;
+    gsrt_status s = GSRT_OK;
+    std::vector<float*> host(list.size()), dev(list.size());
+    for (size_t i = 0; i < list.size(); ++i) {
+        host[i] = *list[i].slot;
+        dev[i] = nullptr;
+        for (size_t j = 0; j < i; ++j)
+            if (host[j] == host[i]) dev[i] = dev[j];
+        if (!dev[i]) {
+            dev[i] = tmp.take<float>(list[i].bytes / sizeof(float));
+            if (list[i].in && s == GSRT_OK && list[i].bytes &&
+                hipMemcpyAsync(dev[i], host[i], list[i].bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+                s = fail(ctx, GSRT_E_DEVICE, name + "upload failed");
+        }
+        *list[i].slot = dev[i];
+    }
+    if (s == GSRT_OK) s = run();
+    for (size_t i = 0; i < list.size(); ++i)
+        if (list[i].out && s == GSRT_OK && list[i].bytes &&
+            hipMemcpyAsync(host[i], dev[i], list[i].bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, name + "download failed");
+    return finish_blocking(ctx, s, {}, &tmpv);
+}
+
+// gsrt_model_step (adam != nullptr) and gsrt_model_activate (everything about m, v, grads absent) in one body
+static gsrt_status model_step_any(gsrt_ctx* ctx, const char* fn, bool blocking, uint32_t n, const gsrt_model_arrays* raw,
+                                  const gsrt_model_arrays* m, const gsrt_model_arrays* v, const gsrt_model_grads* grads,
+                                  const gsrt_adam_params* adam, bool step, const gsrt_model_arrays* act,
+                                  gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out, float* grad_raw) {
+    if (!ctx) return GSRT_E_ARG;
+    const std::string name = std::string(fn) + ": ";
+    if (!raw || (step && (!m || !v || !grads || !adam))) return fail(ctx, GSRT_E_ARG, name + "a NULL struct");
+    if (step)
+        if (const char* why = check_adam(adam)) return fail(ctx, GSRT_E_ARG, name + why);
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, name + "n above GSRT_MAX_GAUSSIANS");
+    if (const char* why = check_model_sets({raw, step ? m : nullptr, step ? v : nullptr, act}, *raw))
+        return fail(ctx, GSRT_E_ARG, name + why);
+    if (step && ((grads->sh == nullptr) != (raw->sh == nullptr) || (grads->features == nullptr) != (raw->features == nullptr)))
+        return fail(ctx, GSRT_E_ARG, name + "grads.sh / grads.features are NULL exactly when the model has none");
+    (void)hipSetDevice(ctx->device);
+    gsrt_model_arrays r = *raw, mm = step ? *m : gsrt_model_arrays{}, vv = step ? *v : gsrt_model_arrays{};
+    gsrt_model_arrays aa = act ? *act : gsrt_model_arrays{};
+    gsrt_model_grads gg = step ? *grads : gsrt_model_grads{};
+    float* p_out = reinterpret_cast<float*>(params_out);
+    float* b_out = reinterpret_cast<float*>(aabbs_out);
+    std::vector<StepArray> list;
+    model_set_arrays(list, r, n, true, step);
+    if (step) {
+        model_set_arrays(list, mm, n, true, true);
+        model_set_arrays(list, vv, n, true, true);
+        const auto in = [&](const float*& p, size_t floats) {
+            list.push_back({const_cast<float**>(&p), sizeof(float) * floats * n, true, false});
+        };
+        in(gg.center, 3);
+        in(gg.cov, 6);
+        in(gg.splat, 8);
+        if (r.sh) in(gg.sh, 48);
+        if (r.features) in(gg.features, r.feature_channels);
+    }
+    if (act) {
+        // act.sh / act.features given as NULL with a model that has them is refused above; every present array is written
+        if (n && (!aa.center || !aa.rot_rxyz || !aa.scale || !aa.opacity)) return fail(ctx, GSRT_E_ARG, name + "a NULL array");
+        model_set_arrays(list, aa, n, false, true);
+    }
+    if (p_out) list.push_back({&p_out, sizeof(gsrt_gauss_param) * (size_t)n, false, true});
+    if (b_out) list.push_back({&b_out, sizeof(gsrt_aabb) * (size_t)n, false, true});
+    if (step && grad_raw) list.push_back({&grad_raw, sizeof(float) * 11 * (size_t)n, false, true});
+    if (n && (!r.center || !r.rot_rxyz || !r.scale || !r.opacity ||
+              (step && (!mm.center || !mm.rot_rxyz || !mm.scale || !mm.opacity || !vv.center || !vv.rot_rxyz || !vv.scale ||
+                        !vv.opacity || !gg.center || !gg.cov || !gg.splat))))
+        return fail(ctx, GSRT_E_ARG, name + "a NULL array");
+    const int side = check_step_arrays(ctx, name, list, n, {{&aa.sh, &r.sh}, {&aa.features, &r.features}});
+    if (side < 0) return GSRT_E_ARG;
+    if (!blocking && side == 0 && n) return fail(ctx, GSRT_E_ARG, name + "the async form takes device pointers only");
+    gsrt::AdamScalars K{};
+    if (step) adam_scalars(*adam, K);
+    const auto run = [&]() -> gsrt_status {
+        gsrt::launch_model_step(ctx->stream, n, step ? &K : nullptr, r, &mm, &vv, &gg, aa,
+                                reinterpret_cast<gsrt_gauss_param*>(p_out), reinterpret_cast<gsrt_aabb*>(b_out), grad_raw);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, GSRT_E_DEVICE, name + "launch failed");
+        return GSRT_OK;
+    };
+    if (!n) return GSRT_OK;
+    if (side == 1) {
+        const gsrt_status s = run();
+        return blocking ? finish_blocking(ctx, s, {}) : s;
+    }
+    return run_staged(ctx, name, list, run);
+}
+
+gsrt_status gsrt_model_step(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* m,
+                            const gsrt_model_arrays* v, const gsrt_model_grads* grads, const gsrt_adam_params* adam,
+                            const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
+                            float* grad_raw) {
+    return model_step_any(ctx, "gsrt_model_step", true, n, raw, m, v, grads, adam, true, act, params_out, aabbs_out, grad_raw);
+}
+gsrt_status gsrt_model_step_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* m,
+                                  const gsrt_model_arrays* v, const gsrt_model_grads* grads, const gsrt_adam_params* adam,
+                                  const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
+                                  float* grad_raw) {
+    return model_step_any(ctx, "gsrt_model_step", false, n, raw, m, v, grads, adam, true, act, params_out, aabbs_out, grad_raw);
+}
+gsrt_status gsrt_model_activate(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* act,
+                                gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out) {
+    return model_step_any(ctx, "gsrt_model_activate", true, n, raw, nullptr, nullptr, nullptr, nullptr, false, act, params_out,
+                          aabbs_out, nullptr);
+}
+gsrt_status gsrt_model_activate_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* act,
+                                      gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out) {
+    return model_step_any(ctx, "gsrt_model_activate", false, n, raw, nullptr, nullptr, nullptr, nullptr, false, act, params_out,
+                          aabbs_out, nullptr);
+}
+
+static gsrt_status model_deactivate_any(gsrt_ctx* ctx, bool blocking, uint32_t n, const gsrt_model_arrays* act,
+                                        const gsrt_model_arrays* raw) {
+    if (!ctx) return GSRT_E_ARG;
+    const std::string name = "gsrt_model_deactivate: ";
+    if (!act || !raw) return fail(ctx, GSRT_E_ARG, name + "a NULL struct");
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, name + "n above GSRT_MAX_GAUSSIANS");
+    if (const char* why = check_model_sets({act, raw}, *act)) return fail(ctx, GSRT_E_ARG, name + why);
+    (void)hipSetDevice(ctx->device);
+    gsrt_model_arrays a = *act, r = *raw;
+    if (n && (!a.center || !a.rot_rxyz || !a.scale || !a.opacity || !r.center || !r.rot_rxyz || !r.scale || !r.opacity))
+        return fail(ctx, GSRT_E_ARG, name + "a NULL array");
+    std::vector<StepArray> list;
+    model_set_arrays(list, a, n, true, false);
+    model_set_arrays(list, r, n, false, true);
+    const int side = check_step_arrays(ctx, name, list, n, {{&a.sh, &r.sh}, {&a.features, &r.features}});
+    if (side < 0) return GSRT_E_ARG;
+    if (!blocking && side == 0 && n) return fail(ctx, GSRT_E_ARG, name + "the async form takes device pointers only");
+    const auto run = [&]() -> gsrt_status {
+        gsrt::launch_model_deactivate(ctx->stream, n, a, r);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, GSRT_E_DEVICE, name + "launch failed");
+        return GSRT_OK;
+    };
+    if (!n) return GSRT_OK;
+    if (side == 1) {
+        const gsrt_status s = run();
+        return blocking ? finish_blocking(ctx, s, {}) : s;
+    }
+    return run_staged(ctx, name, list, run);
+}
+gsrt_status gsrt_model_deactivate(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* act, const gsrt_model_arrays* raw) {
+    return model_deactivate_any(ctx, true, n, act, raw);
+}
+gsrt_status gsrt_model_deactivate_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* act,
+                                        const gsrt_model_arrays* raw) {
+    return model_deactivate_any(ctx, false, n, act, raw);
+}
+
+static gsrt_status opacity_reset_any(gsrt_ctx* ctx, bool blocking, uint32_t n, float* logit, float* m, float* v,
+                                     float max_opacity) {
+    if (!ctx) return GSRT_E_ARG;
+    const std::string name = "gsrt_model_opacity_reset: ";
+    if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return fail(ctx, GSRT_E_ARG, name + "max_opacity must be in (0, 1)");
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, name + "n above GSRT_MAX_GAUSSIANS");
+    (void)hipSetDevice(ctx->device);
+    std::vector<StepArray> list = {{&logit, sizeof(float) * (size_t)n, true, true},
+                                   {&m, sizeof(float) * (size_t)n, false, true},
+                                   {&v, sizeof(float) * (size_t)n, false, true}};
+    const int side = check_step_arrays(ctx, name, list, n, {});
+    if (side < 0) return GSRT_E_ARG;
+    if (!blocking && side == 0 && n) return fail(ctx, GSRT_E_ARG, name + "the async form takes device pointers only");
+    const float limit = (float)std::log((double)max_opacity / (1.0 - (double)max_opacity));
+    const auto run = [&]() -> gsrt_status {
+        gsrt::launch_opacity_reset(ctx->stream, n, limit, logit, m, v);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, GSRT_E_DEVICE, name + "launch failed");
+        return GSRT_OK;
+    };
+    if (!n) return GSRT_OK;
+    if (side == 1) {
+        const gsrt_status s = run();
+        return blocking ? finish_blocking(ctx, s, {}) : s;
+    }
+    return run_staged(ctx, name, list, run);
+}
+gsrt_status gsrt_model_opacity_reset(gsrt_ctx* ctx, uint32_t n, float* logit_opacity, float* m_opacity, float* v_opacity,
+                                     float max_opacity) {
+    return opacity_reset_any(ctx, true, n, logit_opacity, m_opacity, v_opacity, max_opacity);
+}
+gsrt_status gsrt_model_opacity_reset_async(gsrt_ctx* ctx, uint32_t n, float* d_logit_opacity, float* d_m_opacity,
+                                           float* d_v_opacity, float max_opacity) {
+    return opacity_reset_any(ctx, false, n, d_logit_opacity, d_m_opacity, d_v_opacity, max_opacity);
 }
 
 gsrt_status gsrt_render(gsrt_scene* sc, const gsrt_ubo* ubo, uint32_t mode, uint32_t k, float* rgba_out,

@@ -482,6 +482,21 @@ uint32_t image_loss_tiles(uint32_t width, uint32_t height);
 void launch_image_loss(hipStream_t s, uint32_t width, uint32_t height, const float* rgba, const float* target,
                        uint32_t target_channels, float lambda, double* partial, float* maps, float* out, float* grad);
 void image_loss_window(float out[11]);
+// the optimiser step (gsrt_model_step.hip). AdamScalars: what the kernels take of a gsrt_adam_params: gsrt_adam_scalars'
+// floats (ss per group: centre, rot, log scale, logit, SH coefficient 0, SH rest, features), bit i of frozen set when
+// group i's lr is 0, the flags. launch_model_step: K == nullptr is the activation alone (m, v, G unused); every pointer a
+// device pointer, act's members, params, aabbs and grad_raw nullable. The SH / feature rows are stepped in place and
+// copied to act's where that is another array.
+struct AdamScalars {
+    float beta1, beta2, a1, a2, c2, eps;
+    float ss[7];
+    uint32_t frozen, flags;
+};
+void launch_model_step(hipStream_t s, uint32_t n, const AdamScalars* K, const gsrt_model_arrays& raw,
+                       const gsrt_model_arrays* m, const gsrt_model_arrays* v, const gsrt_model_grads* G,
+                       const gsrt_model_arrays& act, gsrt_gauss_param* params, gsrt_aabb* aabbs, float* grad_raw);
+void launch_model_deactivate(hipStream_t s, uint32_t n, const gsrt_model_arrays& act, const gsrt_model_arrays& raw);
+void launch_opacity_reset(hipStream_t s, uint32_t n, float limit, float* logit, float* m, float* v);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into
 inline float* framebuffer_of(gsrt_ctx* ctx) { return ctx->fb_view ? ctx->fb_view : ctx->d_fb; }
 // the prep stream must not overtake what is on ctx->stream now (scene upload/update, BVH build/refit)

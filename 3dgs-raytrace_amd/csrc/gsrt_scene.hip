@@ -5,13 +5,14 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "gsrt_cov3d.hpp"
 #include "gsrt_internal.hpp"
 #include "gsrt_project.hpp"
 
 namespace gsrt {
 
 // Gauss::init_cov3d / init_radius / BoundingBox (RayTracingInVulkan/src/Assets/Sphere.hpp:108-165),
-// packed as Scene.cpp:125-136 does. glm mat3 products are summed left to right.
+// packed as Scene.cpp:125-136 does: cov3d_pack (gsrt_cov3d.hpp) per Gaussian.
 __global__ __launch_bounds__(256) void k_cov3d(uint32_t n, const float* __restrict__ center,
                                                const float* __restrict__ rot, const float* __restrict__ scale,
                                                const float* __restrict__ opacity, gsrt_gauss_param* __restrict__ params,
@@ -20,40 +21,11 @@ __global__ __launch_bounds__(256) void k_cov3d(uint32_t n, const float* __restri
     if (i >= n) return;
     const float r = rot[4 * i + 0], x = rot[4 * i + 1], y = rot[4 * i + 2], z = rot[4 * i + 3];
     const float s0 = scale[3 * i + 0], s1 = scale[3 * i + 1], s2 = scale[3 * i + 2];
-    // R[c][row], glm::mat3 column-major constructor (Sphere.hpp:143-147)
-    float R[9] = {1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
-                  2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
-                  2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y)};
-    const float S[9] = {s0, 0.f, 0.f, 0.f, s1, 0.f, 0.f, 0.f, s2};
-    float M[9];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            M[c * 3 + k] = (S[0 * 3 + k] * R[c * 3 + 0] + S[1 * 3 + k] * R[c * 3 + 1]) + S[2 * 3 + k] * R[c * 3 + 2];
-    // Sigma = transpose(M) * M: Sigma[c][k] = (Mt[0][k]*M[c][0] + Mt[1][k]*M[c][1]) + Mt[2][k]*M[c][2], Mt[a][k] = M[k][a]
-    float Sig[9];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            Sig[c * 3 + k] = (M[k * 3 + 0] * M[c * 3 + 0] + M[k * 3 + 1] * M[c * 3 + 1]) + M[k * 3 + 2] * M[c * 3 + 2];
+    const float c[3] = {center[3 * i + 0], center[3 * i + 1], center[3 * i + 2]};
     gsrt_gauss_param g;
-    g.center_opacity[0] = center[3 * i + 0];
-    g.center_opacity[1] = center[3 * i + 1];
-    g.center_opacity[2] = center[3 * i + 2];
-    g.center_opacity[3] = opacity[i];
-    g.cov3d[0] = Sig[0]; g.cov3d[1] = Sig[1]; g.cov3d[2] = Sig[2];
-    g.cov3d[3] = Sig[4]; g.cov3d[4] = Sig[5]; g.cov3d[5] = Sig[8];
-    g.pad[0] = 0.f; g.pad[1] = 0.f;
-    params[i] = g;
-    float mx = s0;
-    if (s1 > mx) mx = s1;
-    if (s2 > mx) mx = s2;
-    const float rad = (float)(3.0 * (double)mx);  // Sphere.hpp:164, double product stored as float
     gsrt_aabb a;
-    a.min_x = g.center_opacity[0] - rad; a.min_y = g.center_opacity[1] - rad; a.min_z = g.center_opacity[2] - rad;
-    a.max_x = g.center_opacity[0] + rad; a.max_y = g.center_opacity[1] + rad; a.max_z = g.center_opacity[2] + rad;
+    cov3d_pack(c, r, x, y, z, s0, s1, s2, opacity[i], g, a);  // gsrt_cov3d.hpp: shared with the model step
+    params[i] = g;
     aabbs[i] = a;
 }
 

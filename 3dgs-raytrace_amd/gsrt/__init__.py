@@ -76,6 +76,8 @@ EXPORTS = [
     "gsrt_splat_depth_grad_to_model", "gsrt_splat_depth_grad_to_model_async", "gsrt_debug_frame_refusal_any",
     "gsrt_density_stats_add", "gsrt_density_stats_add_async", "gsrt_densify_count", "gsrt_densify", "gsrt_densify_async",
     "gsrt_image_loss", "gsrt_image_loss_async", "gsrt_image_loss_window",
+    "gsrt_adam_scalars", "gsrt_model_step", "gsrt_model_step_async", "gsrt_model_activate", "gsrt_model_activate_async",
+    "gsrt_model_deactivate", "gsrt_model_deactivate_async", "gsrt_model_opacity_reset", "gsrt_model_opacity_reset_async",
 ]
 
 
@@ -212,6 +214,15 @@ def _load():
         "gsrt_image_loss": ([P, u32, u32, P, P, u32, f32, P, P], i32),
         "gsrt_image_loss_async": ([P, u32, u32, P, P, u32, f32, P, P], i32),
         "gsrt_image_loss_window": ([P], i32),
+        "gsrt_adam_scalars": ([P, P], i32),
+        "gsrt_model_step": ([P, u32, P, P, P, P, P, P, P, P, P], i32),
+        "gsrt_model_step_async": ([P, u32, P, P, P, P, P, P, P, P, P], i32),
+        "gsrt_model_activate": ([P, u32, P, P, P, P], i32),
+        "gsrt_model_activate_async": ([P, u32, P, P, P, P], i32),
+        "gsrt_model_deactivate": ([P, u32, P, P], i32),
+        "gsrt_model_deactivate_async": ([P, u32, P, P], i32),
+        "gsrt_model_opacity_reset": ([P, u32, P, P, P, f32], i32),
+        "gsrt_model_opacity_reset_async": ([P, u32, P, P, P, f32], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -678,6 +689,203 @@ def image_loss(ctx, rgba, target, lam=0.2, want_grad=True, *, width=None, height
     grad = np.zeros(x.shape, np.float32) if want_grad else None
     _check(lib.gsrt_image_loss(ctx.handle, x.shape[1], x.shape[0], _p(x), _p(y), y.shape[2], lam, _p(out), _p(grad)), ctx)
     return dict(loss=float(out[0]), l1=float(out[1]), ssim=float(out[2]), mse=float(out[3])), grad
+
+
+# ---------------------------------------------------------------- the optimiser step
+
+ADAM_SPARSE = 1  # GSRT_ADAM_SPARSE
+ADAM_SCALARS = 10  # GSRT_ADAM_SCALARS
+
+
+class AdamParams(ctypes.Structure):
+    """gsrt_adam_params"""
+    _fields_ = [("lr_center", ctypes.c_float), ("lr_rot", ctypes.c_float), ("lr_scale", ctypes.c_float),
+                ("lr_opacity", ctypes.c_float), ("lr_sh_dc", ctypes.c_float), ("lr_sh_rest", ctypes.c_float),
+                ("lr_features", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("eps", ctypes.c_float), ("step", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+class ModelGrads(ctypes.Structure):
+    """gsrt_model_grads: addresses of the gradient tables as the library's backward writes them (0 / None: absent)"""
+    _fields_ = [("center", ctypes.c_void_p), ("cov", ctypes.c_void_p), ("splat", ctypes.c_void_p),
+                ("sh", ctypes.c_void_p), ("features", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(AdamParams) == 64 and ctypes.sizeof(ModelGrads) == 40
+
+
+def adam_params(lr_center=1.6e-4, lr_rot=1e-3, lr_scale=5e-3, lr_opacity=5e-2, lr_sh_dc=2.5e-3, lr_sh_rest=1.25e-4,
+                lr_features=0.0, beta1=0.9, beta2=0.999, eps=1e-15, step=1, sparse=False) -> AdamParams:
+    """a gsrt_adam_params; the defaults are 3DGS's rates (the caller schedules them: change lr_* and step per call). A
+    rate of exactly 0 freezes its group; sparse: Gaussians no ray reached with a gradient keep raw, m and v (ADAM_SPARSE)"""
+    return AdamParams(lr_center, lr_rot, lr_scale, lr_opacity, lr_sh_dc, lr_sh_rest, lr_features, beta1, beta2, eps, step,
+                      ADAM_SPARSE if sparse else 0)
+
+
+def adam_scalars(adam) -> np.ndarray:
+    """the float32 scalars model_step's kernels use (gsrt_adam_scalars; no device needed): [1 - beta1, 1 - beta2,
+    sqrt(1 - beta2^t), then lr / (1 - beta1^t) for center, rot, scale, opacity, sh_dc, sh_rest, features]"""
+    out = np.zeros(ADAM_SCALARS, np.float32)
+    _check(lib.gsrt_adam_scalars(ctypes.byref(adam), _p(out)))
+    return out
+
+
+_MODEL_SHAPES = ((3,), (4,), (3,), (), (48,), None)  # per Gaussian: center, rot, scale, opacity, sh, features (n, C)
+
+
+def _model_set(what, arrays, n, writable):
+    """(center, rot, scale, opacity, sh or None, features or None) as a ModelArrays. numpy arrays are passed by address
+    (float32, C-contiguous; copies of other inputs are made only for arrays the call reads); ints are device addresses.
+    Returns (struct, n, channels, keep-alive list, on the device?)."""
+    arrays = tuple(arrays) + (None,) * (6 - len(arrays))
+    dev = isinstance(arrays[0], int)
+    keep, addr, fc = [], [], 0
+    for a, shape in zip(arrays, _MODEL_SHAPES):
+        if a is None or (isinstance(a, int) and a == 0):
+            addr.append(None)
+            continue
+        if isinstance(a, int) != dev:
+            raise GsrtError(E_ARG, f"{what}: numpy arrays or device addresses, not both")
+        if dev:
+            addr.append(a)
+            continue
+        if writable:
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable):
+                raise GsrtError(E_ARG, f"{what}: arrays changed in place are writable C-contiguous float32 arrays")
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+        if n is None:
+            n = a.shape[0] if a.ndim else 1
+        if shape is None:
+            fc = a.size // n if n else (a.shape[1] if a.ndim == 2 else 0)
+        want = n * (fc if shape is None else int(np.prod(shape, dtype=np.int64)))
+        if a.size != want:
+            raise GsrtError(E_ARG, f"{what}: an array of {a.size} floats where n = {n} needs {want}")
+        keep.append(a)
+        addr.append(a.ctypes.data)
+    return addr, n, fc, keep, dev
+
+
+def _new_model(n, src_addr, fc, sh_shape=(48,)):
+    o = [np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32),
+         None if src_addr[4] is None else np.zeros((n,) + tuple(sh_shape), np.float32),
+         None if src_addr[5] is None else np.zeros((n, fc), np.float32)]
+    return o
+
+
+def model_step(ctx, raw, m, v, grads, adam, *, n=None, feature_channels=0, act=None, params_out=None, aabbs_out=None,
+               grad_raw=None, want_act=True, want_grad_raw=False, asynchronous=False):
+    """One optimiser step on the raw model (gsrt_model_step; the formulas are in gsrt.h): the gradient tables chained to the
+    raw parameters, Adam, and the next frame's arrays. raw, m, v: (center (n, 3), rot (n, 4) unnormalised, log scale
+    (n, 3), logit opacity (n,), sh (n, 48) / (n, 16, 3) or None, features (n, C) or None), the moments in the same layout,
+    all updated in place. grads: (center (n, 3), cov (n, 6), splat (n, 8), sh or None, features or None) as Scene.model_grad,
+    Scene.splat_grad, Scene.sh_grad and Scene.feature_grad return them. adam: an AdamParams (adam_params).
+    numpy arrays: raw, m, v are writable C-contiguous float32 arrays. Returns dict(act=(center, rot, scale, opacity, sh,
+    features) or None (want_act=False), params= (n, 12), aabbs= (n, 6) (as Scene.download returns them, for Scene.update), grad_raw= (n, 11)
+    or None): act is the activated model, sh / features in it the stepped arrays themselves.
+    device addresses (int; 0 or None when absent): n (and feature_channels) are needed; act = six addresses or None,
+    params_out, aabbs_out, grad_raw addresses or None. Blocks and returns None; asynchronous=True only enqueues the call
+    on ctx.stream (gsrt_model_step_async): synchronise before Scene.update / Scene.attach read params_out / aabbs_out."""
+    r_addr, n, fc, k1, dev = _model_set("model_step: raw", raw, n, True)
+    m_addr, _, fcm, k2, dev_m = _model_set("model_step: m", m, n, True)
+    v_addr, _, fcv, k3, dev_v = _model_set("model_step: v", v, n, True)
+    if n is None:
+        raise GsrtError(E_ARG, "model_step: device addresses need n")
+    grads = tuple(grads) + (None,) * (5 - len(grads))
+    keep, g_addr = [], []
+    for a, width in zip(grads, (3, 6, 8, 48, fc if not dev else feature_channels)):
+        if a is None or (isinstance(a, int) and a == 0):
+            g_addr.append(None)
+        elif isinstance(a, int):
+            g_addr.append(a)
+        else:
+            keep.append(_f32(a, (n, width)))
+            g_addr.append(keep[-1].ctypes.data)
+    if dev:
+        fc = fcm = fcv = feature_channels
+    s_raw, s_m, s_v = ModelArrays(*r_addr, fc), ModelArrays(*m_addr, fcm), ModelArrays(*v_addr, fcv)
+    s_g = ModelGrads(*g_addr)
+    if dev:
+        s_act = None if act is None else ModelArrays(*[x or None for x in act], fc)
+        fn = lib.gsrt_model_step_async if asynchronous else lib.gsrt_model_step
+        _check(fn(ctx.handle, n, ctypes.byref(s_raw), ctypes.byref(s_m), ctypes.byref(s_v), ctypes.byref(s_g),
+                  ctypes.byref(adam), None if s_act is None else ctypes.byref(s_act), _addr(params_out), _addr(aabbs_out),
+                  _addr(grad_raw)), ctx)
+        return None
+    out = _new_model(n, r_addr, fc) if want_act else None
+    if out is not None:
+        out[4], out[5] = (None if r_addr[4] is None else raw[4]), (None if r_addr[5] is None else raw[5])
+        s_act = ModelArrays(*[None if a is None else a.ctypes.data for a in out], fc)
+    params, aabbs = np.zeros((n, 12), np.float32), np.zeros((n, 6), np.float32)
+    graw = np.zeros((n, 11), np.float32) if want_grad_raw else None
+    _check(lib.gsrt_model_step(ctx.handle, n, ctypes.byref(s_raw), ctypes.byref(s_m), ctypes.byref(s_v), ctypes.byref(s_g),
+                               ctypes.byref(adam), None if out is None else ctypes.byref(s_act), _p(params), _p(aabbs),
+                               _p(graw)), ctx)
+    return dict(act=None if out is None else tuple(out), params=params, aabbs=aabbs, grad_raw=graw)
+
+
+def model_activate(ctx, raw, *, n=None, feature_channels=0, act=None, params_out=None, aabbs_out=None, asynchronous=False):
+    """The activation and packing of model_step alone (gsrt_model_activate), for step 0 and after a densify: raw =
+    (center, rot, log scale, logit opacity, sh or None, features or None). numpy arrays: returns dict(act=(center, rot,
+    scale, opacity, sh, features), params=, aabbs=); sh / features in act are copies. device addresses: n (and
+    feature_channels) needed, act = six addresses or None, params_out / aabbs_out addresses or None; returns None."""
+    r_addr, n, fc, keep, dev = _model_set("model_activate: raw", raw, n, False)
+    if n is None:
+        raise GsrtError(E_ARG, "model_activate: device addresses need n")
+    if dev:
+        fc = feature_channels
+        s_raw = ModelArrays(*r_addr, fc)
+        s_act = None if act is None else ModelArrays(*[x or None for x in act], fc)
+        fn = lib.gsrt_model_activate_async if asynchronous else lib.gsrt_model_activate
+        _check(fn(ctx.handle, n, ctypes.byref(s_raw), None if s_act is None else ctypes.byref(s_act), _addr(params_out),
+                  _addr(aabbs_out)), ctx)
+        return None
+    s_raw = ModelArrays(*r_addr, fc)
+    out = _new_model(n, r_addr, fc)
+    s_act = ModelArrays(*[None if a is None else a.ctypes.data for a in out], fc)
+    params, aabbs = np.zeros((n, 12), np.float32), np.zeros((n, 6), np.float32)
+    _check(lib.gsrt_model_activate(ctx.handle, n, ctypes.byref(s_raw), ctypes.byref(s_act), _p(params), _p(aabbs)), ctx)
+    return dict(act=tuple(out), params=params, aabbs=aabbs)
+
+
+def model_deactivate(ctx, act, *, n=None, feature_channels=0, raw=None, asynchronous=False):
+    """Activated to raw (gsrt_model_deactivate): what ply_read or densify return becomes the model model_step optimises;
+    log scale = log(s), logit = log(o / (1 - o)), the rest copied. numpy arrays: returns (center, rot, log scale, logit,
+    sh or None, features or None). device addresses: n (and feature_channels) and raw = six addresses are needed."""
+    a_addr, n, fc, keep, dev = _model_set("model_deactivate: act", act, n, False)
+    if n is None:
+        raise GsrtError(E_ARG, "model_deactivate: device addresses need n")
+    if dev:
+        if raw is None:
+            raise GsrtError(E_ARG, "model_deactivate: device addresses need raw")
+        s_act, s_raw = ModelArrays(*a_addr, feature_channels), ModelArrays(*[x or None for x in raw], feature_channels)
+        fn = lib.gsrt_model_deactivate_async if asynchronous else lib.gsrt_model_deactivate
+        _check(fn(ctx.handle, n, ctypes.byref(s_act), ctypes.byref(s_raw)), ctx)
+        return None
+    out = _new_model(n, a_addr, fc)
+    s_act = ModelArrays(*a_addr, fc)
+    s_raw = ModelArrays(*[None if a is None else a.ctypes.data for a in out], fc)
+    _check(lib.gsrt_model_deactivate(ctx.handle, n, ctypes.byref(s_act), ctypes.byref(s_raw)), ctx)
+    return tuple(out)
+
+
+def model_opacity_reset(ctx, logit, m, v, max_opacity=0.01, *, n=None, asynchronous=False):
+    """3DGS's opacity reset on the raw model (gsrt_model_opacity_reset): logit = min(logit, log(max_opacity / (1 -
+    max_opacity))) in place, both Adam moments of the opacities set to 0. Three writable float32 numpy arrays of n, or
+    three device addresses with n given (asynchronous=True: enqueued on ctx.stream only)."""
+    if isinstance(logit, int):
+        if n is None:
+            raise GsrtError(E_ARG, "model_opacity_reset: device addresses need n")
+        fn = lib.gsrt_model_opacity_reset_async if asynchronous else lib.gsrt_model_opacity_reset
+        _check(fn(ctx.handle, n, _addr(logit), _addr(m), _addr(v), max_opacity), ctx)
+        return None
+    for a in (logit, m, v):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable and
+                a.size == logit.size):
+            raise GsrtError(E_ARG, "model_opacity_reset: three writable C-contiguous float32 arrays of one size")
+    _check(lib.gsrt_model_opacity_reset(ctx.handle, logit.size, _p(logit), _p(m), _p(v), max_opacity), ctx)
+    return None
 
 
 # ---------------------------------------------------------------- context / scene

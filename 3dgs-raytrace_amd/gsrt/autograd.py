@@ -32,6 +32,10 @@ fused call (gsrt.image_loss), so that a training step stays in the library's ker
         optimiser.step()
     image_metrics(ctx, rgba.detach(), target)                 # dict(loss=, l1=, ssim=, mse=, psnr=), no gradient
 
+and the optimiser: model_step chains the gradient tables to the raw parameters (unnormalised quaternion, log scale, logit
+opacity), takes the Adam step and writes the next frame's scene arrays in one fused call (gsrt.model_step), so that a whole
+training loop needs neither torch.autograd nor torch.optim (the loop: model_step's docstring).
+
 torch is imported here only; `import gsrt` never needs it.
 
 Synchronisation is plain and blocking: the current torch stream is synchronised before the library reads a tensor, and
@@ -44,6 +48,7 @@ import math
 
 from . import MODE_COR, density_stats_add, image_loss
 from . import densify as _densify
+from . import model_step as _model_step
 
 
 class _RenderFeatures(torch.autograd.Function):
@@ -468,3 +473,75 @@ def image_metrics(ctx, rgba, target, lam=0.2):
                    target_channels=int(y.shape[2]))
     m["psnr"] = -10.0 * math.log10(m["mse"]) if m["mse"] > 0.0 else math.inf
     return m
+
+
+def _model_tensors(name, tensors, n, dev, fc=None):
+    """(center, rot, scale, opacity, sh or None, features or None) checked: contiguous float32 tensors on `dev`"""
+    tensors = tuple(tensors) + (None,) * (6 - len(tensors))
+    shapes = [((n, 3),), ((n, 4),), ((n, 3),), ((n,),), ((n, 48), (n, 16, 3)), None]
+    for t, ok, what in zip(tensors, shapes, ("center", "rot", "scale", "opacity", "sh", "features")):
+        if t is None:
+            continue
+        good = tuple(t.shape) in ok if ok else (t.dim() == 2 and t.shape[0] == n and (fc is None or t.shape[1] == fc))
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or not good:
+            raise ValueError(f"model_step: {name}.{what} must be a contiguous float32 tensor of n rows on the model's device")
+    return tensors
+
+
+def model_step(ctx, raw, m, v, grads, adam, want_act=True, want_grad_raw=False):
+    """One optimiser step of the raw model in the library's own kernels (gsrt.model_step, gsrt_model_step_async; the
+    formulas are in gsrt.h). ctx: the gsrt.Context. raw, m, v: (center (n, 3), rot (n, 4) unnormalised, log scale (n, 3),
+    logit opacity (n,), sh (n, 16, 3) / (n, 48) or None, features (n, C) or None), the two Adam moments in the same layout:
+    contiguous float32 GPU tensors, all updated in place. grads: (center (n, 3), cov (n, 6), splat (n, 8), sh or None,
+    features or None), the tables as Scene.model_grad_async, Scene.splat_grad_async, Scene.sh_grad_async and
+    Scene.feature_grad_async write them. adam: gsrt.adam_params(..., step=t), t counting from 1.
+    Returns dict(act=(center, rot, scale, opacity, sh, features) or None, params=(n, 12), aabbs=(n, 6), grad_raw=(n, 11) or
+    None): the activated model (sh / features in it are raw's own tensors), the scene arrays for Scene.update, and the
+    chained gradient the step used. Blocking synchronisation on both sides: torch's current stream before the call,
+    Context.synchronize() after it. Gradients do not flow through this call.
+
+    The whole loop, without torch.autograd or torch.optim (n Gaussians, a W x H target; new = torch.empty on the GPU):
+
+        raw = [t.contiguous() for t in gsrt.model_deactivate(...)]       # or from a .ply: center, rot, log scale, logit, sh
+        m, v = [torch.zeros_like(t) for t in raw], [torch.zeros_like(t) for t in raw]
+        rgba, gimg, rows = new(H, W, 4), new(H, W, 4), new(n, 8)
+        d_c, d_cov, d_sh, out4 = new(n, 3), new(n, 6), new(n, 48), new(4)
+        for t in range(1, steps + 1):
+            scene.render_async(ubo, d_rgba=rgba.data_ptr())                                     # Scene.render_async
+            gsrt.image_loss(ctx, rgba.data_ptr(), target.data_ptr(), 0.2, width=W, height=H, target_channels=3,
+                            d_out=out4.data_ptr(), d_grad=gimg.data_ptr(), asynchronous=True)   # image_loss
+            scene.splat_grad_async(ubo, gimg.data_ptr(), rows.data_ptr())                       # splat_grad_async
+            scene.model_grad_async(ubo, rows.data_ptr(), d_c.data_ptr(), d_cov.data_ptr())      # model_grad_async
+            scene.sh_grad_async(ubo, gimg.data_ptr(), d_sh.data_ptr())                          # sh_grad_async
+            gsrt.density_stats_add(ctx, rows.data_ptr(), stats.data_ptr(), W, H, n=n, asynchronous=True)
+            out = model_step(ctx, raw, m, v, (d_c, d_cov, rows, d_sh), gsrt.adam_params(step=t, sparse=True))  # model_step
+            scene.update(params=out["params"].data_ptr(), aabbs=out["aabbs"].data_ptr())        # Scene.update
+            scene.refit_bvh()                                                                   #  + refit_bvh
+            scene.set_sh(raw[4].data_ptr())                                                     #  + set_sh
+
+    Every call of the loop body queues on the library's streams; only model_step waits (it returns tensors). Scene.update
+    reads out["params"] / out["aabbs"] on the library's update stream: keep `out` alive until the next model_step has
+    returned (or call ctx.synchronize()), so that torch does not hand their memory out again before they are read. Every few
+    hundred steps: densify(ctx, *out["act"][:5], stats, noise, params) on the activated model, remap_state on every tensor
+    of m and v with its origin, gsrt.model_deactivate of the new model (device addresses) for the new raw tensors, and a
+    new scene from the new activated arrays (Scene.from_model_device, build_bvh), as in densify's docstring; every few
+    thousand, gsrt.model_opacity_reset(ctx, raw[3].data_ptr(), m[3].data_ptr(), v[3].data_ptr(), 0.01, n=n)."""
+    n, dev = int(raw[0].shape[0]), raw[0].device
+    raw = _model_tensors("raw", raw, n, dev)
+    fc = 0 if raw[5] is None else int(raw[5].shape[1])
+    m, v = _model_tensors("m", m, n, dev, fc), _model_tensors("v", v, n, dev, fc)
+    grads = tuple(grads) + (None,) * (5 - len(grads))
+    for t, width, what in zip(grads, (3, 6, 8, 48, fc), ("center", "cov", "splat", "sh", "features")):
+        if t is not None and (t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() != n * width):
+            raise ValueError(f"model_step: grads.{what} must be a contiguous float32 tensor of n x {width} on the model's device")
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+    act = (new(n, 3), new(n, 4), new(n, 3), new(n), raw[4], raw[5]) if want_act else None
+    params, aabbs = new(n, 12), new(n, 6)
+    graw = new(n, 11) if want_grad_raw else None
+    ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+    torch.cuda.current_stream(dev).synchronize()
+    _model_step(ctx, [ptr(t) for t in raw], [ptr(t) for t in m], [ptr(t) for t in v], [ptr(t) for t in grads], adam, n=n,
+                feature_channels=fc, act=None if act is None else [ptr(t) for t in act], params_out=params.data_ptr(),
+                aabbs_out=aabbs.data_ptr(), grad_raw=ptr(graw), asynchronous=True)
+    ctx.synchronize()
+    return dict(act=act, params=params, aabbs=aabbs, grad_raw=graw)

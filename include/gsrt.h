@@ -502,7 +502,8 @@ gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* scene, const gsrt_u
  * The model is the gsrt_scene_from_model arrays; the calls below work on arrays, not on a scene: a scene's size is fixed,
  * so after gsrt_densify the caller creates a new scene from the new arrays (gsrt_scene_from_model takes device pointers)
  * and builds its BVH. The library has no random numbers: a split's samples come from the caller's noise, so a result is
- * a pure function of its inputs. Not provided: screen-radius pruning, an opacity reset, resizing a scene in place. */
+ * a pure function of its inputs. Not provided: screen-radius pruning, resizing a scene in place (an opacity reset:
+ * gsrt_model_opacity_reset below). */
 typedef struct gsrt_model_arrays {   /* the gsrt_scene_from_model convention */
     float* center;    /* n x 3 */
     float* rot_rxyz;  /* n x 4, used as given */
@@ -627,6 +628,105 @@ gsrt_status gsrt_image_loss_async(gsrt_ctx* ctx, uint32_t width, uint32_t height
 /* the 1-D window of gsrt_image_loss: exp(-(i - 5)^2 / (2 * 1.5^2)), i = 0..10, normalised to sum 1 in double and each
  * rounded to float once (a constant table; no device or ctx needed) */
 gsrt_status gsrt_image_loss_window(float out[11]);
+
+/* ---- the optimiser step on the device: fused Adam over the raw model ------------------------------
+ * With these calls this header alone describes a 3DGS training loop: gsrt_render, gsrt_image_loss, gsrt_render_splat_grad,
+ * gsrt_splat_grad_to_model, gsrt_render_sh_grad, gsrt_model_step, gsrt_scene_update + gsrt_refit_bvh + gsrt_scene_set_sh
+ * (INTEGRATION.md gives it in C). What is optimised, and what a .ply holds, is the raw model: a gsrt_model_arrays whose
+ * rot_rxyz is an unnormalised quaternion, whose scale is the log scale and whose opacity is the logit; centre, sh and
+ * features are stored as they are. The library's own model (gsrt_scene_from_model, gsrt_densify, gsrt_ply_read) is the
+ * activated one. Everything is float32, every operation rounded on its own (no fused multiply-add), divisions and square
+ * roots correctly rounded; no atomics: a result is a pure function of its inputs.
+ * Activation, per Gaussian, of raw (r, x, y, z), log scale l_k and logit t:
+ *     nq = sqrtf(((r r + x x) + y y) + z z),  q = raw_rot / nq (nq == 0 leaves q = raw_rot: the scene build's polynomial
+ *     turns the zero quaternion into R = I),  s_k = expf(l_k),  o = 1 / (1 + expf(-t));
+ * params_out[g] and aabbs_out[g] are, bit for bit, what gsrt_scene_from_model writes for (centre, q, s, o).
+ * Chain, with dcov = grads.cov[g] (cov3d's order; an off-diagonal slot is one variable), R the scene build's rotation
+ * matrix of q (Sigma_ij = sum_k s_k^2 R_ki R_kj) and D the symmetric matrix of dcov (an off-diagonal entry half its slot):
+ *     w_k = D R_k,  d s_k = (2 s_k) (R_k . w_k),  d log_scale_k = d s_k * s_k,
+ *     d R_ka = ((2 s_k) s_k) w_ka,  d q_c = sum_ka d R_ka dR_ka/dq_c,  d raw_rot = (dq - q (q . dq)) / nq, +0 when nq == 0,
+ *     d logit = (grads.splat[g][5] * o) * (1 - o),
+ *     d centre = grads.center[g], d sh and d features the table entries, unchanged.
+ * Adam, per parameter word p with gradient g and its group's rate lr, with gsrt_adam_scalars' a1 = 1 - beta1,
+ * a2 = 1 - beta2, c2 = sqrt(1 - beta2^t), ss = lr / (1 - beta1^t):
+ *     m' = beta1 * m + a1 * g,   v' = beta2 * v + (a2 * g) * g,   p' = p - (ss * m') / (sqrtf(v') / c2 + eps).
+ * The groups: centre, rot, log scale, logit, SH coefficient 0 of each channel (lr_sh_dc), SH coefficients 1..15
+ * (lr_sh_rest), features. A group whose lr is exactly 0 is frozen: its raw, m and v words keep their bits. With
+ * GSRT_ADAM_SPARSE a Gaussian that was not seen keeps every raw, m and v word bit for bit (3DGS's sparse Adam); "seen" is
+ * gsrt_density_stats_add's: any of its splat row's slots 0..5 != 0.0f. Without the flag every Gaussian is stepped.
+ * Not provided: other optimisers, learning-rate schedules (change lr_* per call), weight decay. */
+#define GSRT_ADAM_SPARSE 1u
+typedef struct gsrt_adam_params {
+    float lr_center, lr_rot, lr_scale, lr_opacity, lr_sh_dc, lr_sh_rest, lr_features;
+    float beta1, beta2, eps;      /* 3DGS: 0.9, 0.999, 1e-15 */
+    uint32_t step;                /* t >= 1 */
+    uint32_t flags;               /* GSRT_ADAM_SPARSE */
+    uint32_t reserved[4];         /* zero, otherwise GSRT_E_ARG */
+} gsrt_adam_params;
+
+typedef struct gsrt_model_grads {     /* with respect to the activated model, as the library's backward writes them */
+    const float* center;    /* n x 3: gsrt_splat_grad_to_model's grad_center (or the depth form's) */
+    const float* cov;       /* n x 6: its grad_cov */
+    const float* splat;     /* n x 8: the gradient frame's rows; slot 5 is d/d opacity, slots 0..5 decide "seen" */
+    const float* sh;        /* n x 48 [gauss][coef][rgb]: gsrt_render_sh_grad's table; NULL exactly when the model has no sh */
+    const float* features;  /* n x C: gsrt_render_feature_grad's table; NULL exactly when it has no features */
+} gsrt_model_grads;
+
+/* The float32 scalars the step's kernels use, host only (no ctx, no device): out = {1 - beta1, 1 - beta2,
+ * sqrt(1 - beta2^t), then lr / (1 - beta1^t) for lr_center, lr_rot, lr_scale, lr_opacity, lr_sh_dc, lr_sh_rest,
+ * lr_features}, each formed in double and rounded to float once. GSRT_E_ARG: a NULL pointer; step == 0; beta1 or beta2
+ * outside [0, 1) or NaN; eps not > 0; a negative or NaN learning rate; a non-zero reserved word; an unknown flag. */
+#define GSRT_ADAM_SCALARS 10
+gsrt_status gsrt_adam_scalars(const gsrt_adam_params* adam, float out[GSRT_ADAM_SCALARS]);
+/* One optimiser step of n Gaussians. raw, m (first moments) and v (second moments; the same layout as raw) are updated in
+ * place; grads is read as the library's backward leaves it. Each of the outputs is nullable: act (as a whole, and, when
+ * given, it has every array raw has) receives the activated model in the gsrt_scene_from_model convention, params_out
+ * (n entries) and aabbs_out (n entries) the scene arrays, all three for all n Gaussians, stepped or not, activated from
+ * the updated raw values; grad_raw (n x 11 floats: centre 3, rot 4, log scale 3, logit 1) the chained gradient the step
+ * used, for every Gaussian. act->sh may be raw->sh itself and act->features raw->features itself (they are stored as
+ * they are: nothing is copied then); otherwise the updated rows are copied.
+ * raw, m, v and act must agree on feature_channels and on which of sh and features are present, and grads->sh /
+ * grads->features are NULL exactly when the model has none. All arrays are host pointers, or all are device pointers
+ * (ordinary device memory; whole float4 / float2 accesses are used where the bases are 16- / 8-byte aligned, as hipMalloc
+ * and torch give them, dword accesses otherwise); the host form stages them in a device block of the call's.
+ * The call runs on gsrt_stream(), behind the gradient calls that filled grads; the blocking form returns when everything
+ * is written. After the async form call gsrt_synchronize before handing params_out / aabbs_out to gsrt_scene_update or
+ * gsrt_scene_attach: those read their source on other streams.
+ * GSRT_E_ARG, with nothing written: a NULL ctx, raw, m, v, grads or adam, or a NULL required array with n > 0; host and
+ * device pointers mixed; what gsrt_adam_scalars refuses; sh or features presence, or the channel count (above
+ * GSRT_MAX_FEATURES included), disagreeing between the structs; n > GSRT_MAX_GAUSSIANS; an output array overlapping an
+ * input or another output (raw, m and v, written in place, must not overlap each other or grads either). */
+gsrt_status gsrt_model_step(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* m,
+                            const gsrt_model_arrays* v, const gsrt_model_grads* grads, const gsrt_adam_params* adam,
+                            const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
+                            float* grad_raw);
+/* the same, enqueued on gsrt_stream() without a host synchronisation; device pointers only */
+gsrt_status gsrt_model_step_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* m,
+                                  const gsrt_model_arrays* v, const gsrt_model_grads* grads, const gsrt_adam_params* adam,
+                                  const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
+                                  float* grad_raw);
+/* The activation and packing alone, for step 0 and after a densify: the same arithmetic, the same kernel code path; raw is
+ * only read. act, params_out and aabbs_out as for gsrt_model_step, with its pointer and aliasing rules and refusals. */
+gsrt_status gsrt_model_activate(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* act,
+                                gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out);
+gsrt_status gsrt_model_activate_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* act,
+                                      gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out);
+/* Activated to raw, which turns a gsrt_ply_read result or a gsrt_densify output into the raw form: centre and rot copied
+ * bit for bit (a normalised quaternion is a raw one), log scale = logf(s), logit = logf(o / (1 - o)); sh and features
+ * copied (raw->sh may be act->sh itself, raw->features act->features itself). An opacity of 1 gives +inf, of 0 -inf.
+ * Pointers, presence and aliasing rules and refusals as for gsrt_model_activate, with act the input and raw the output. */
+gsrt_status gsrt_model_deactivate(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* act, const gsrt_model_arrays* raw);
+gsrt_status gsrt_model_deactivate_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* act,
+                                        const gsrt_model_arrays* raw);
+/* 3DGS's opacity reset on the raw model: logit' = min(logit, L), L = (float)log(max_opacity / (1 - max_opacity)) formed in
+ * double (a NaN logit stays a NaN), and both moment arrays of the opacities are set to +0 for every Gaussian. The three
+ * arrays (n floats each) are all host or all device pointers. On gsrt_stream(); the blocking form returns when they are
+ * written. GSRT_E_ARG: a NULL ctx or pointer (with n > 0), mixed pointers, overlapping arrays, max_opacity outside (0, 1)
+ * or NaN, n > GSRT_MAX_GAUSSIANS. */
+gsrt_status gsrt_model_opacity_reset(gsrt_ctx* ctx, uint32_t n, float* logit_opacity, float* m_opacity, float* v_opacity,
+                                     float max_opacity);
+gsrt_status gsrt_model_opacity_reset_async(gsrt_ctx* ctx, uint32_t n, float* d_logit_opacity, float* d_m_opacity,
+                                           float* d_v_opacity, float max_opacity);
 
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
