@@ -23,7 +23,9 @@
 // laid out [gauss][coef][rgb] out), --opacity-grad FILE --opacity-grad-out FILE (gsrt_render_opacity_grad: W*H*4 in, n
 // out), --splat-grad FILE --splat-grad-out FILE (gsrt_render_splat_grad: W*H*4 in, n*8 out; the library refuses --lut).
 // --depth-grad FILE beside the --splat-grad pair (the depth image's gradient, W*H): gsrt_render_splat_depth_grad instead,
-// the same table out; without --splat-grad it is a usage error.
+// the same table out; without --splat-grad it is a usage error. --pose-grad-out FILE beside the --splat-grad pair: the rows
+// chained to the camera (gsrt_pose_grad; with --depth-grad its depth form), the 16 floats of dL/d(model_view) written raw and
+// the twist (gsrt_pose_twist) printed; without --splat-grad it is a usage error.
 // Their usage errors: --mode ref or a REF-default scene, --stats, --depth, --features, a gradient run listed before
 // it, one option without the others, C outside 1..16.
 // --loss-target FILE [--loss-lambda L] [--loss-channels 3|4] [--loss-grad-out FILE]: after the frame, its photometric
@@ -54,7 +56,7 @@ struct Options {
     int device = 0;
     float fov = 0.0f;  // 0: scene default
     std::string camera, out, binary, text, ply, depth, features, features_out, feature_grad, feature_grad_out;
-    std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out, splat_grad, splat_grad_out, depth_grad;
+    std::string sh_grad, sh_grad_out, opacity_grad, opacity_grad_out, splat_grad, splat_grad_out, depth_grad, pose_grad_out;
     uint32_t feature_channels = 0;
     bool feature_channels_given = false;
     std::string loss_target, loss_grad_out;
@@ -104,6 +106,7 @@ bool given(const Options& o, const GradOption& g) { return !(o.*g.in).empty() ||
                  "                   [--sh-grad FILE --sh-grad-out FILE]\n"
                  "                   [--opacity-grad FILE --opacity-grad-out FILE]\n"
                  "                   [--splat-grad FILE --splat-grad-out FILE] [--depth-grad FILE]\n"
+                 "                   [--pose-grad-out FILE]\n"
                  "                   [--loss-target FILE [--loss-lambda L] [--loss-channels 3|4] [--loss-grad-out FILE]]\n");
     std::exit(2);
 }
@@ -157,6 +160,7 @@ Options parse(int argc, char** argv) {
         else if (a == "--splat-grad") o.splat_grad = val();
         else if (a == "--splat-grad-out") o.splat_grad_out = val();
         else if (a == "--depth-grad") o.depth_grad = val();
+        else if (a == "--pose-grad-out") o.pose_grad_out = val();
         else if (a == "--feature-channels") { o.feature_channels = to_u32(val(), "--feature-channels"); o.feature_channels_given = true; }
         else if (a == "--loss-target") o.loss_target = val();
         else if (a == "--loss-lambda") { o.loss_lambda = std::strtof(val(), nullptr); o.loss_options_given = true; }
@@ -172,6 +176,7 @@ Options parse(int argc, char** argv) {
     if (!o.depth.empty() && o.mode != "cor") usage("--depth needs --mode cor (REF frames have no blended depth)");
     if (!o.depth.empty() && o.stats) usage("--depth cannot be combined with --stats");
     if (!o.depth_grad.empty() && o.splat_grad.empty()) usage("--depth-grad goes with --splat-grad and --splat-grad-out");
+    if (!o.pose_grad_out.empty() && o.splat_grad.empty()) usage("--pose-grad-out goes with --splat-grad and --splat-grad-out");
     for (const GradOption* g = std::end(kGradOptions); g-- != kGradOptions;) {  // newest first
         if (!given(o, *g)) continue;
         const std::string n = g->name;
@@ -347,6 +352,19 @@ int main(int argc, char** argv) {
             if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, out.c_str());
         }
         if (!rc) std::printf("wrote %s\n", out.c_str());
+        if (!rc && !o.pose_grad_out.empty()) {  // with --splat-grad (parse): gtab holds the splat rows
+            float gmv[16], twist[6];
+            rc = check(gsrt_pose_grad(scene, &ubo, gtab.data(), gdepth.empty() ? 0 : 1, gmv), ctx, "pose_grad");
+            if (!rc) rc = check(gsrt_pose_twist(ubo.model_view, gmv, twist), ctx, "pose_twist");
+            if (!rc) {
+                f = std::fopen(o.pose_grad_out.c_str(), "wb");
+                const bool ok = f && std::fwrite(gmv, sizeof(float), 16, f) == 16;
+                if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.pose_grad_out.c_str());
+            }
+            if (!rc)
+                std::printf("wrote %s\ntwist dL/dv %.9g %.9g %.9g dL/dw %.9g %.9g %.9g\n", o.pose_grad_out.c_str(), twist[0],
+                            twist[1], twist[2], twist[3], twist[4], twist[5]);
+        }
     } else if (!rc) {
         rc = check(gsrt_render(scene, &ubo, mode, 0, rgba.data(), nullptr), ctx, "render");
     }

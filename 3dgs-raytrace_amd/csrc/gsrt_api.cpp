@@ -256,6 +256,7 @@ void gsrt_destroy(gsrt_ctx* ctx) {
     (void)hipFree(ctx->d_grad_out);
     (void)hipFree(ctx->d_densify_ws);
     (void)hipFree(ctx->d_loss_ws);
+    (void)hipFree(ctx->d_pose_ws);
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_tile_counter);
     (void)hipFree(ctx->d_lut);
@@ -1218,6 +1219,74 @@ gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* sc, const gsrt_ubo*
 gsrt_status gsrt_splat_depth_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* grad_center,
                                            float* grad_cov, int accumulate) {
     return model_grad_blocking(sc, ubo, grad_splat, grad_center, grad_cov, accumulate, true);
+}
+
+// ---- the camera's gradient (gsrt_pose_grad.hip) -------------------------------------------------------------------
+// On the render stream behind the gradient frame that wrote the rows, reading the scene's parameters as the chain above.
+static gsrt_status check_pose_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, const float* rows, const float* out) {
+    if (!sc || !ubo) return GSRT_E_ARG;
+    const char* name = "gsrt_pose_grad: ";
+    if (!rows) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_splat is NULL");
+    if (!out) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "grad_model_view is NULL");
+    if (sc->ntri) return fail(sc->ctx, GSRT_E_ARG, std::string(name) + "not for a scene with a triangle mesh");
+    if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, std::string(name) + "before gsrt_build_bvh");
+    return GSRT_OK;
+}
+
+// the two kernels on the render stream; the arguments are checked and every pointer is a device pointer (d_out nullptr:
+// the workspace's 16 floats, whose address *d_out_used receives)
+static gsrt_status pose_grad_enqueue(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_rows, bool depth, float* d_out,
+                                     float** d_out_used = nullptr) {
+    gsrt_ctx* ctx = sc->ctx;
+    const size_t chunks = gsrt::pose_grad_chunks(sc->n), need = 16 * chunks + 8;
+    if (!ctx->d_pose_ws || ctx->pose_ws_doubles < need) {
+        GSRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a queued call may still use the smaller one
+        if (gsrt_status s = grow(ctx, &ctx->d_pose_ws, &ctx->pose_ws_doubles, need); s != GSRT_OK) return s;
+    }
+    // the result's slot stands at the end of the allocation, wherever this call's partials end
+    float* const ws_out = reinterpret_cast<float*>(ctx->d_pose_ws + (ctx->pose_ws_doubles - 8));
+    if (d_out_used) *d_out_used = d_out ? d_out : ws_out;
+    if (gsrt_status s = gsrt::wait_updates(ctx, ctx->stream); s != GSRT_OK) return s;
+    ctx->serial_pending = true;
+    ctx->serial_reads = true;
+    gsrt::launch_pose_grad(ctx->stream, sc->n, *ubo, sc->d_params, d_rows, depth, ctx->d_pose_ws, d_out ? d_out : ws_out);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_pose_grad_async(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_grad_splat, int depth,
+                                 float* d_grad_model_view) {
+    gsrt_status s = check_pose_grad_args(sc, ubo, d_grad_splat, d_grad_model_view);
+    if (s != GSRT_OK) return s;
+    (void)hipSetDevice(sc->ctx->device);
+    return pose_grad_enqueue(sc, ubo, d_grad_splat, depth != 0, d_grad_model_view);
+}
+
+gsrt_status gsrt_pose_grad(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, int depth,
+                           float grad_model_view[16]) {
+    gsrt_status s = check_pose_grad_args(sc, ubo, grad_splat, grad_model_view);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (is_device_ptr(grad_model_view)) return fail(ctx, GSRT_E_ARG, "gsrt_pose_grad: grad_model_view is a host pointer");
+    const size_t n = sc->n;
+    float* tmp = nullptr;
+    const bool in_dev = is_device_ptr(grad_splat) || !n;
+    if (!in_dev) GSRT_HIP(ctx, hipMalloc(&tmp, sizeof(float) * 8 * n));
+    void* tmpv = tmp;
+    if (!in_dev && hipMemcpyAsync(tmp, grad_splat, sizeof(float) * 8 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        s = fail(ctx, GSRT_E_DEVICE, "splat gradient upload failed");
+    float* d_out = nullptr;
+    if (s == GSRT_OK) s = pose_grad_enqueue(sc, ubo, in_dev ? grad_splat : tmp, depth != 0, nullptr, &d_out);
+    return finish_blocking(ctx, s, {{d_out ? grad_model_view : nullptr, d_out, sizeof(float) * 16,
+                                     "gsrt_pose_grad: download failed"}}, &tmpv);
+}
+
+gsrt_status gsrt_debug_pose_grad_layout(uint32_t out[2]) {
+    if (!out) return GSRT_E_ARG;
+    out[0] = gsrt::kPoseChunk;
+    out[1] = gsrt::kPoseFinalLanes;
+    return GSRT_OK;
 }
 
 // ---- adaptive density control (gsrt_densify.hip) ------------------------------------------------------------------

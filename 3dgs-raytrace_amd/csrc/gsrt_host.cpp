@@ -314,3 +314,82 @@ extern "C" gsrt_status gsrt_synth_cloud(uint32_t kind, uint32_t n, uint32_t seed
     }
     return GSRT_OK;
 }
+
+// ---- camera pose helpers (gsrt_pose_twist, gsrt_ubo_apply_twist): host only, in double, each result rounded once ----
+namespace {
+
+// exp of the twist (v, w) of se(3) as a 4x4 in row-major doubles E[r][c]: R = I + A K + B K^2 (Rodrigues), K = [w]x,
+// translation (I + B K + C K^2) v, A = sin th / th, B = (1 - cos th) / th^2, C = (th - sin th) / th^3, th = |w|; below
+// th = 0.1 by their series in th^2, whose first omitted term is under 1e-17 of the value there
+void twist_exp(const double v[3], const double w[3], double E[4][4]) {
+    const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    double A, B, C;
+    if (t2 < 1e-2) {
+        A = 1.0 - t2 / 6.0 * (1.0 - t2 / 20.0 * (1.0 - t2 / 42.0 * (1.0 - t2 / 72.0)));
+        B = 0.5 * (1.0 - t2 / 12.0 * (1.0 - t2 / 30.0 * (1.0 - t2 / 56.0 * (1.0 - t2 / 90.0))));
+        C = 1.0 / 6.0 * (1.0 - t2 / 20.0 * (1.0 - t2 / 42.0 * (1.0 - t2 / 72.0 * (1.0 - t2 / 110.0))));
+    } else {
+        const double th = std::sqrt(t2);
+        A = std::sin(th) / th;
+        B = (1.0 - std::cos(th)) / t2;
+        C = (th - std::sin(th)) / (t2 * th);
+    }
+    const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
+    double K2[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) K2[r][c] = K[r][0] * K[0][c] + K[r][1] * K[1][c] + K[r][2] * K[2][c];
+    for (int r = 0; r < 3; ++r) {
+        double tr = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            const double eye = r == c ? 1.0 : 0.0;
+            E[r][c] = eye + A * K[r][c] + B * K2[r][c];
+            tr += (eye + B * K[r][c] + C * K2[r][c]) * v[c];
+        }
+        E[r][3] = tr;
+    }
+    E[3][0] = E[3][1] = E[3][2] = 0.0;
+    E[3][3] = 1.0;
+}
+
+}  // namespace
+
+extern "C" gsrt_status gsrt_pose_twist(const float model_view[16], const float grad_model_view[16], float twist[6]) {
+    if (!model_view || !grad_model_view || !twist) return GSRT_E_ARG;
+    // H = G MV^T as 4x4 matrices, entry [r][c] of a column-major array at c * 4 + r
+    double H[4][4];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 4; ++k) s += (double)grad_model_view[k * 4 + i] * (double)model_view[k * 4 + j];
+            H[i][j] = s;
+        }
+    const double t[6] = {H[0][3], H[1][3], H[2][3], H[2][1] - H[1][2], H[0][2] - H[2][0], H[1][0] - H[0][1]};
+    for (int k = 0; k < 6; ++k) twist[k] = (float)t[k];
+    return GSRT_OK;
+}
+
+extern "C" gsrt_status gsrt_ubo_apply_twist(gsrt_ubo* ubo, const float twist[6]) {
+    if (!ubo || !twist) return GSRT_E_ARG;
+    bool zero = true;
+    for (int k = 0; k < 6; ++k) zero = zero && twist[k] == 0.0f;
+    if (zero) return GSRT_OK;  // every bit as it was
+    const double v[3] = {twist[0], twist[1], twist[2]}, w[3] = {twist[3], twist[4], twist[5]};
+    const double nv[3] = {-v[0], -v[1], -v[2]}, nw[3] = {-w[0], -w[1], -w[2]};
+    double E[4][4], Ei[4][4];
+    twist_exp(v, w, E);
+    twist_exp(nv, nw, Ei);
+    float mv[16], inv[16];
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r) {
+            double a = 0.0, b = 0.0;
+            for (int k = 0; k < 4; ++k) {
+                a += E[r][k] * (double)ubo->model_view[c * 4 + k];           // exp(xi^) MV
+                b += (double)ubo->model_view_inverse[k * 4 + r] * Ei[k][c];  // MVinv exp(-xi^)
+            }
+            mv[c * 4 + r] = (float)a;
+            inv[c * 4 + r] = (float)b;
+        }
+    std::memcpy(ubo->model_view, mv, sizeof mv);
+    std::memcpy(ubo->model_view_inverse, inv, sizeof inv);
+    return GSRT_OK;
+}

@@ -174,6 +174,10 @@ struct gsrt_ctx {
     // call with a gradient, the nine derivative planes of W x H floats; grown on demand, used in stream order on `stream`
     double* d_loss_ws = nullptr;
     size_t loss_ws_doubles = 0;
+    // gsrt_pose_grad: per chunk of Gaussians one partial of 16 doubles, then 16 floats for a blocking call's result; grown
+    // on demand, used in stream order on `stream`
+    double* d_pose_ws = nullptr;
+    size_t pose_ws_doubles = 0;
     unsigned long long* d_counters = nullptr;  // kCounters words: [0..7] stats, [kErrWord] sticky error word
     uint32_t* d_tile_counter = nullptr;
     uint32_t last_w = 0, last_h = 0;
@@ -482,6 +486,15 @@ uint32_t image_loss_tiles(uint32_t width, uint32_t height);
 void launch_image_loss(hipStream_t s, uint32_t width, uint32_t height, const float* rgba, const float* target,
                        uint32_t target_channels, float lambda, double* partial, float* maps, float* out, float* grad);
 void image_loss_window(float out[11]);
+// the camera's gradient (gsrt_pose_grad.hip). kPoseChunk: the consecutive Gaussians one workgroup of the first kernel sums
+// into one partial of 16 doubles; kPoseFinalLanes: the lanes of the second kernel's one workgroup, which sums the partials
+// (gsrt_debug_pose_grad_layout reports both). launch_pose_grad: rows (n x 8) chained to the 16 floats of out; partial holds
+// 16 * pose_grad_chunks(n) doubles; every pointer a device pointer.
+constexpr uint32_t kPoseChunk = 2048;
+constexpr uint32_t kPoseFinalLanes = 512;
+uint32_t pose_grad_chunks(uint32_t n);
+void launch_pose_grad(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params, const float* rows,
+                      bool depth, double* partial, float* out);
 // the optimiser step (gsrt_model_step.hip). AdamScalars: what the kernels take of a gsrt_adam_params: gsrt_adam_scalars'
 // floats (ss per group: centre, rot, log scale, logit, SH coefficient 0, SH rest, features), bit i of frozen set when
 // group i's lr is 0, the flags. launch_model_step: K == nullptr is the activation alone (m, v, G unused); every pointer a

@@ -78,6 +78,7 @@ EXPORTS = [
     "gsrt_image_loss", "gsrt_image_loss_async", "gsrt_image_loss_window",
     "gsrt_adam_scalars", "gsrt_model_step", "gsrt_model_step_async", "gsrt_model_activate", "gsrt_model_activate_async",
     "gsrt_model_deactivate", "gsrt_model_deactivate_async", "gsrt_model_opacity_reset", "gsrt_model_opacity_reset_async",
+    "gsrt_pose_grad", "gsrt_pose_grad_async", "gsrt_pose_twist", "gsrt_ubo_apply_twist", "gsrt_debug_pose_grad_layout",
 ]
 
 
@@ -223,6 +224,11 @@ def _load():
         "gsrt_model_deactivate_async": ([P, u32, P, P], i32),
         "gsrt_model_opacity_reset": ([P, u32, P, P, P, f32], i32),
         "gsrt_model_opacity_reset_async": ([P, u32, P, P, P, f32], i32),
+        "gsrt_pose_grad": ([P, P, P, i32, P], i32),
+        "gsrt_pose_grad_async": ([P, P, P, i32, P], i32),
+        "gsrt_pose_twist": ([P, P, P], i32),
+        "gsrt_ubo_apply_twist": ([P, P], i32),
+        "gsrt_debug_pose_grad_layout": ([P], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -289,6 +295,41 @@ def camera_from_modelview(mv, fovy_deg, width, height, focus_distance=1.0, sampl
     _check(lib.gsrt_camera_from_modelview(_p(m), fovy_deg, width, height, focus_distance,
                                           samples, bounces, _p(ubo)))
     return ubo
+
+
+def pose_twist(model_view, grad_model_view) -> np.ndarray:
+    """gsrt_pose_twist: the gradient (dL/dv, dL/dw), (6,) float32, in the tangent space of a left perturbation
+    MV' = exp(xi^) MV, from model_view and Scene.pose_grad's result (16 floats each, column-major, or (4, 4) arrays holding
+    the same 16 floats in that order)."""
+    mv, g = np.asarray(model_view, np.float32), np.asarray(grad_model_view, np.float32)
+    if mv.size != 16 or g.size != 16:
+        raise GsrtError(E_ARG, "pose_twist: model_view and grad_model_view hold 16 floats each")
+    mv, g = np.ascontiguousarray(mv).reshape(16), np.ascontiguousarray(g).reshape(16)
+    out = np.zeros(6, np.float32)
+    _check(lib.gsrt_pose_twist(_p(mv), _p(g), _p(out)))
+    return out
+
+
+def ubo_apply_twist(ubo, twist) -> np.ndarray:
+    """gsrt_ubo_apply_twist on a copy of `ubo`: model_view <- exp(xi^) model_view, model_view_inverse <- model_view_inverse
+    exp(-xi^) for the twist xi = (v, w), 6 floats. A zero twist returns an identical copy."""
+    if not isinstance(ubo, np.ndarray) or ubo.dtype != UBO_DTYPE or ubo.size != 1:
+        raise GsrtError(E_ARG, "ubo_apply_twist: ubo is one UBO_DTYPE record")
+    t = np.asarray(twist, np.float32)
+    if t.size != 6:
+        raise GsrtError(E_ARG, "ubo_apply_twist: a twist holds 6 floats")
+    t = np.ascontiguousarray(t).reshape(6)
+    out = ubo.copy()
+    _check(lib.gsrt_ubo_apply_twist(_p(out), _p(t)))
+    return out
+
+
+def pose_grad_layout():
+    """(chunk, lanes) of gsrt_pose_grad's summation (gsrt_debug_pose_grad_layout): the Gaussians per first-stage partial
+    and the second stage's lane count"""
+    out = np.zeros(2, np.uint32)
+    _check(lib.gsrt_debug_pose_grad_layout(_p(out)))
+    return int(out[0]), int(out[1])
 
 
 def camera_from_file(path, fovy_deg, width, height, focus_distance=1.0, samples=1, bounces=16) -> np.ndarray:
@@ -1432,6 +1473,25 @@ class Scene:
         fn = lib.gsrt_splat_depth_grad_to_model_async if depth else lib.gsrt_splat_grad_to_model_async
         _check(fn(self.handle, _p(ubo), ctypes.c_void_p(d_grad_splat or None), ctypes.c_void_p(d_grad_center or None),
                   ctypes.c_void_p(d_grad_cov or None), 1 if accumulate else 0), self.ctx)
+
+    def pose_grad(self, ubo, rows, depth=False):
+        """The camera's gradient (gsrt_pose_grad): rows is the (n, 8) table of splat_grad (depth=True: of splat_depth_grad)
+        for the same ubo and scene parameters, a numpy array or a device address; returns (16,) float32, the partial
+        derivative of the loss with respect to ubo.model_view in its own column-major layout (reshape(4, 4).T is the matrix),
+        with model_view_inverse held fixed. Summed in double in a fixed order: deterministic."""
+        out = np.zeros(16, np.float32)
+        if isinstance(rows, (int, np.integer)):
+            src = ctypes.c_void_p(int(rows) or None)
+        else:
+            rows = _f32(rows, (self.n, 8))
+            src = _p(rows)
+        _check(lib.gsrt_pose_grad(self.handle, _p(ubo), src, 1 if depth else 0, _p(out)), self.ctx)
+        return out
+
+    def pose_grad_async(self, ubo, d_grad_splat: int, d_grad_model_view: int, depth=False):
+        """Enqueue the camera's gradient on ctx.stream: device addresses of n*8 and 16 floats."""
+        _check(lib.gsrt_pose_grad_async(self.handle, _p(ubo), ctypes.c_void_p(d_grad_splat or None), 1 if depth else 0,
+                                        ctypes.c_void_p(d_grad_model_view or None)), self.ctx)
 
     def geometry_grad(self, ubo, grad_image, mode=MODE_COR, k=0, grad_depth=None):
         """One splat gradient frame and the projection's backward: (grad_center (n, 3), grad_cov (n, 6), grad_opacity

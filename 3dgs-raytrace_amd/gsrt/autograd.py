@@ -204,10 +204,38 @@ def _add_density_stats(ctx, rows):
                           asynchronous=True)
 
 
+def _ubo_with_view(ubo, view):
+    """render_model(..., view=V): a copy of `ubo` with V as its model_view (view[r, c] = model_view[c * 4 + r]) and V's
+    inverse, computed in float64 outside the graph, as its model_view_inverse; view=None: `ubo` itself"""
+    if view is None:
+        return ubo
+    with torch.no_grad():
+        V = view.detach().to(torch.float64).cpu()
+        inv = torch.linalg.inv(V)
+    out = ubo.copy()
+    out["model_view"][0] = V.t().contiguous().reshape(16).to(torch.float32).numpy()
+    out["model_view_inverse"][0] = inv.t().contiguous().reshape(16).to(torch.float32).numpy()
+    return out
+
+
+def _queue_pose_grad(ctx, rows, depth):
+    """render_model(..., view=V): the camera's gradient from the splat rows just queued, behind the model chain"""
+    if not (ctx.has_view and ctx.needs_input_grad[5]):
+        return None
+    d_view = torch.empty((16,), dtype=torch.float32, device=rows.device)
+    ctx.scene.pose_grad_async(ctx.ubo, rows.data_ptr(), d_view.data_ptr(), depth=depth)
+    return d_view
+
+
+def _view_grad(d_view):
+    return None if d_view is None else d_view.reshape(4, 4).t().contiguous()  # [c][r] storage to view[r, c]
+
+
 class _RenderModel(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k, density_stats):
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats):
         n = scene.n
+        ubo = _ubo_with_view(ubo, view)
         params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
         params[:, 0:3], params[:, 3], params[:, 4:10] = center.detach(), opacity.detach(), cov3d.detach()
         boxes = aabbs.detach().to(torch.float32).contiguous()
@@ -224,6 +252,7 @@ class _RenderModel(torch.autograd.Function):
         ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
         ctx.sh_shape = None if sh is None else tuple(sh.shape)
         ctx.density_stats = density_stats
+        ctx.has_view = view is not None
         return rgba
 
     @staticmethod
@@ -240,18 +269,20 @@ class _RenderModel(torch.autograd.Function):
         ctx.scene.splat_grad_async(ctx.ubo, g.data_ptr(), rows.data_ptr(), False, ctx.mode, ctx.k)
         _add_density_stats(ctx, rows)
         ctx.scene.model_grad_async(ctx.ubo, rows.data_ptr(), d_c.data_ptr(), d_v.data_ptr(), False)
+        d_view = _queue_pose_grad(ctx, rows, False)
         if d_sh is not None:
             ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
         ctx.scene.ctx.synchronize()
-        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None, None
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, _view_grad(d_view), None, None, None, None, None
 
 
 class _RenderModelDepth(torch.autograd.Function):
     """_RenderModel with the expected depth as a second differentiable output (render_model(..., depth=True))"""
 
     @staticmethod
-    def forward(ctx, center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k, density_stats):
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats):
         n = scene.n
+        ubo = _ubo_with_view(ubo, view)
         params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
         params[:, 0:3], params[:, 3], params[:, 4:10] = center.detach(), opacity.detach(), cov3d.detach()
         boxes = aabbs.detach().to(torch.float32).contiguous()
@@ -270,6 +301,7 @@ class _RenderModelDepth(torch.autograd.Function):
         ctx.sh_shape = None if sh is None else tuple(sh.shape)
         ctx.image = (H, W, center.device)
         ctx.density_stats = density_stats
+        ctx.has_view = view is not None
         return rgba, depth
 
     @staticmethod
@@ -291,10 +323,11 @@ class _RenderModelDepth(torch.autograd.Function):
         ctx.scene.splat_depth_grad_async(ctx.ubo, g.data_ptr(), gd.data_ptr(), rows.data_ptr(), False, ctx.mode, ctx.k)
         _add_density_stats(ctx, rows)
         ctx.scene.model_grad_async(ctx.ubo, rows.data_ptr(), d_c.data_ptr(), d_v.data_ptr(), False, depth=True)
+        d_view = _queue_pose_grad(ctx, rows, True)
         if d_sh is not None:  # the depth does not depend on SH
             ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
         ctx.scene.ctx.synchronize()
-        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, None, None, None, None, None
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, _view_grad(d_view), None, None, None, None, None
 
 
 def model_covariance(rot, scale):
@@ -309,7 +342,8 @@ def model_covariance(rot, scale):
     return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], -1)
 
 
-def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0, depth=False, density_stats=None):
+def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0, depth=False, density_stats=None,
+                 view=None):
     """One colour frame of a whole model as a torch tensor rgba[H, W, 4], differentiable with respect to `center` (n, 3),
     `rot` (n, 4; r, x, y, z, used as given), `scale` (n, 3), `opacity` (n,) and, when given, the SH table `sh` ((n, 16, 3)
     or (n, 48)): float32 GPU tensors for a scene of n Gaussians with a built BVH. cov3d is formed here with torch
@@ -330,7 +364,13 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
     the rest as above; an output the loss does not use counts as a zero upstream gradient.
     density_stats: an (n, 2) float32 GPU tensor [sum, count], or None. When given, the backward adds this view's
     densification statistic to it (gsrt.density_stats_add of the splat rows it has just computed, on the plain path and the
-    depth path alike); the caller zeroes it. None changes nothing."""
+    depth path alike); the caller zeroes it. None changes nothing.
+    view: a (4, 4) float32 GPU tensor, the camera's model-view matrix with view[r, c] = model_view[c * 4 + r], or None. When
+    given, the forward renders with a copy of `ubo` whose model_view is `view` and whose model_view_inverse is its inverse
+    (computed in float64, outside the graph), and the backward adds one Scene.pose_grad_async behind the model chain and
+    returns view.grad: the partial derivative with model_view_inverse held fixed (gsrt.h, gsrt_pose_grad: everything that
+    flows through the projection; the rays' share, the SH basis under a rotation, is not provided), on the plain path and
+    the depth path alike. For a pose on the manifold use gsrt.pose_twist and gsrt.ubo_apply_twist. None changes nothing."""
     n = scene.n
     for name, t, shape in (("center", center, (n, 3)), ("rot", rot, (n, 4)), ("scale", scale, (n, 3)),
                            ("opacity", opacity, (n,))):
@@ -345,8 +385,10 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
     if density_stats is not None and (density_stats.dtype != torch.float32 or not density_stats.is_cuda or
                                       tuple(density_stats.shape) != (n, 2) or not density_stats.is_contiguous()):
         raise ValueError("render_model: density_stats must be a contiguous (n, 2) float32 tensor on the GPU")
+    if view is not None and (view.dtype != torch.float32 or not view.is_cuda or tuple(view.shape) != (4, 4)):
+        raise ValueError("render_model: view must be a (4, 4) float32 tensor on the GPU")
     fn = _RenderModelDepth if depth else _RenderModel
-    return fn.apply(center, cov3d, opacity, sh, aabbs, scene, ubo, mode, k, density_stats)
+    return fn.apply(center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats)
 
 
 def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features=None):

@@ -728,6 +728,49 @@ gsrt_status gsrt_model_opacity_reset(gsrt_ctx* ctx, uint32_t n, float* logit_opa
 gsrt_status gsrt_model_opacity_reset_async(gsrt_ctx* ctx, uint32_t n, float* d_logit_opacity, float* d_m_opacity,
                                            float* d_v_opacity, float max_opacity);
 
+/* ---- camera pose gradients: the backward of a frame to the model-view matrix -----------------------
+ * The training loop above takes the cameras as known. For pose refinement and tracking (noisy COLMAP poses, SLAM,
+ * relocalisation) gsrt_pose_grad chains the splat rows of gsrt_render_splat_grad (depth == 0) or of
+ * gsrt_render_splat_depth_grad (depth != 0) to the camera: grad_model_view receives the partial derivative of the loss with
+ * respect to each of the 16 floats of ubo.model_view, in the ubo's own column-major layout (entry c * 4 + r is row r,
+ * column c), WITH ubo.model_view_inverse HELD FIXED. The renderer uses the two fields for separate things: model_view
+ * feeds the projection (ppx, ppy, the conic, the depth key and the blended depth), model_view_inverse makes the rays
+ * (origin and direction, hence the AABB slab test and the SH basis). The result is everything that flows through the splat
+ * rows. Not differentiated, as for gsrt_render_splat_grad: the hits taken and their order, the AABB test, the cuts and the
+ * stop. For a scene without SH rows, or with constant colour, it is the whole gradient of what is differentiated.
+ * Per valid Gaussian g, gsrt_splat_grad_to_model's float32 quantities are recomputed in the same order: gt[0..3] = dL/dt at
+ * the view-space position t = MV (c, 1), the (ppx, ppy) part through the general projection included (depth != 0:
+ * gt[2] -= row[6]); g0[k] = dL/dT0[k], g1[k] = dL/dT1[k] at the Jacobian rows T0 = j02 MVz + j00 MVx, T1 = j12 MVz + j11 MVy.
+ * Its contribution to grad_model_view[c * 4 + r], with c4 = (centre, 1):
+ *     gt[r] * c4[c]                          for all r, c in 0..3 (the bottom row too: a float of the ubo like the others)
+ *     + g0[c] * j00                          r = 0, c < 3          (T's own dependence on MV's 3x3)
+ *     + g1[c] * j11                          r = 1, c < 3
+ *     + (g0[c] * j02 + g1[c] * j12)          r = 2, c < 3
+ * A Gaussian the projection marks invalid (depth <= 0 or det <= 0) contributes nothing. Each contribution is float32,
+ * every operation rounded on its own. The 16 sums over the Gaussians are taken in double in an order that is a function
+ * of n alone (fixed chunks of consecutive Gaussians, fixed trees; not of the grid, the device or timing), and each sum is
+ * rounded to float once. No atomics: the same inputs give the same bits, as gsrt_image_loss promises for its scalars.
+ * grad_splat (n x 8 floats) is a host or a device pointer; grad_model_view is a host pointer; the call blocks. The scene's
+ * current parameters are read, as by gsrt_splat_grad_to_model. GSRT_E_ARG: a NULL pointer; a scene with a mesh.
+ * GSRT_E_STATE: before gsrt_build_bvh. A refused call leaves grad_model_view as it was.
+ * Not provided: gradients with respect to the projection matrix (intrinsics); the model_view_inverse partial, i.e. the ray
+ * direction's effect on the SH basis (zero under a camera translation, since a pixel's world ray direction does not change;
+ * under a rotation the term that pose-refining 3DGS systems drop as well); batched cameras (one call per view). */
+gsrt_status gsrt_pose_grad(gsrt_scene* scene, const gsrt_ubo* ubo, const float* grad_splat, int depth,
+                           float grad_model_view[16]);
+/* the same, enqueued on gsrt_stream() behind the gradient frame; device pointers only (16 floats of ordinary device memory) */
+gsrt_status gsrt_pose_grad_async(gsrt_scene* scene, const gsrt_ubo* ubo, const float* d_grad_splat, int depth,
+                                 float* d_grad_model_view);
+/* Host-only helpers for optimising a pose on the manifold (no ctx, no device; computed in double, each result rounded to
+ * float once). gsrt_pose_twist: the gradient in the tangent space of a left (camera-frame) perturbation
+ * MV' = exp(xi^) MV, xi = (v, w): with H = G MV^T as 4x4 matrices (G = grad_model_view),
+ *     twist = { H[0][3], H[1][3], H[2][3],  H[2][1] - H[1][2], H[0][2] - H[2][0], H[1][0] - H[0][1] }    dL/dv, dL/dw.
+ * gsrt_ubo_apply_twist: the retraction, model_view <- exp(xi^) model_view and model_view_inverse <- model_view_inverse
+ * exp(-xi^), exp(xi^) = [[R, V v], [0, 1]] by Rodrigues' formula (by its series for |w| < 0.1). Nothing assumes that MV
+ * is rigid. A zero twist leaves every bit of the ubo as it was. GSRT_E_ARG: a NULL pointer. */
+gsrt_status gsrt_pose_twist(const float model_view[16], const float grad_model_view[16], float twist[6]);
+gsrt_status gsrt_ubo_apply_twist(gsrt_ubo* ubo, const float twist[6]);
+
 /* counters of the last render with GSRT_FLAG_STATS: [0] rays, [1] sum candidates |C_r|, [2] sum blended
  * |H_r|, [3] terminated rays, [4] tile collection rounds, [5] narrow-traversal restarts, [6] tiles,
  * [7] max candidates in one tile. Per-ray uint4 {candidates, blended, rounds, terminated} into

@@ -100,6 +100,10 @@ gsrt_status gsrt_render_sharded_emulated_dump8(gsrt_scene* scene, const gsrt_ubo
                                                const uint32_t* bands, uint32_t* codes, gsrt_dump8_escape* esc,
                                                uint32_t cap, uint32_t* n_esc);
 
+/* the summation layout of gsrt_pose_grad (no device): out = {the consecutive Gaussians one workgroup of the first kernel
+ * sums into one partial, the lanes of the second kernel's one workgroup}, so that tests can place n at the seams */
+gsrt_status gsrt_debug_pose_grad_layout(uint32_t out[2]);
+
 /* ---- synthetic inputs (std::mt19937(seed) + uniform_real_distribution<float>) ---- */
 gsrt_status gsrt_synth_cloud(uint32_t kind, uint32_t n, uint32_t seed, int with_sh, float* center,
                              float* rot_rxyz, float* scale, float* opacity, float* sh);
