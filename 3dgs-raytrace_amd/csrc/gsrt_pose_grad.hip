@@ -2,8 +2,8 @@
 // of ubo.model_view, model_view_inverse held fixed. k_splat_grad_to_model's chain (gsrt_scene.hip) ended one step earlier,
 // at the view-space position t = MV (c, 1) and the two Jacobian rows T0, T1, and summed over the Gaussians.
 //
-// Per valid Gaussian, in float32 with k_splat_grad_to_model's own operations in its own order (restated here, so that
-// kernel's outputs stay what they are): gt[0..3] = dL/dt (the (ppx, ppy) part through the general projection included; with
+// Per valid Gaussian, in float32: cor_chain and cor_chain_grad (gsrt_project.hpp), the chain and backward
+// k_splat_grad_to_model runs, give gt[0..3] = dL/dt (the (ppx, ppy) part through the general projection included; with
 // DEPTH, gt[2] -= row[6]), g0[k] = dL/dT0[k], g1[k] = dL/dT1[k]. Its 16 contributions, in the ubo's column-major layout
 // (entry c * 4 + r is row r, column c), with c4 = (centre, 1):
 //     m[c * 4 + r] = gt[r] * c4[c]                                   t_r = sum_c MV[r][c] c4[c]
@@ -11,11 +11,9 @@
 //             r = 1  + g1[c] * j11                                   T1[c] = j12 MV[2][c] + j11 MV[1][c]
 //             r = 2  + (g0[c] * j02 + g1[c] * j12)
 // each rounded on its own. An invalid Gaussian (depth <= 0 or det <= 0) contributes nothing.
-// The longest chain of rounded operations from the inputs to a contribution (the tests' N) ends in entry r = 2, c < 3 by
-// way of the conic: t (4), id (1), id^2 (1), j02 (1), T0 (1), u0 (3), v00 (4), det (1), 1 / det (1), A (1), Q G (2), W (2),
-// dL/dT0 (2), dL/dj02 (3), dL/d(id) (4), dL/dt2 (1), + the ppx, ppy part (1): 33 so far, k_splat_grad_to_model's 37 less
-// its final MV^T dL/dt (4); then gt[2] * c4[c] (1) and + the direct term (1), itself a shorter chain: 35. DEPTH: one more,
-// gt[2] - row[6], before the product: 36.
+// The longest chain of rounded operations from the inputs to a contribution (the tests' N) ends in entry r = 2, c < 3:
+// cor_chain_grad's 33 to gt[2] (DEPTH: 34), then gt[2] * c4[c] (1) and + the direct term (1), itself a shorter chain:
+// 35 (DEPTH: 36).
 //
 // The sums over the Gaussians are taken in double, in an order that is a function of n alone:
 //   k_pose_partial: workgroup b of 256 lanes owns the kPoseChunk consecutive Gaussians from b * kPoseChunk. Lane l adds
@@ -29,6 +27,7 @@
 #include <cstdint>
 
 #include "gsrt_internal.hpp"
+#include "gsrt_project.hpp"
 
 namespace gsrt {
 
@@ -36,85 +35,25 @@ constexpr uint32_t kPoseLanes = 256;
 constexpr uint32_t kPosePerLane = kPoseChunk / kPoseLanes;
 static_assert(kPoseChunk % kPoseLanes == 0 && kPoseFinalLanes % 64 == 0, "whole lanes, whole waves");
 
-// the 16 contributions of one Gaussian (see the header); false, and m untouched, for an invalid one
+// the 16 contributions of one valid Gaussian (see the header), f its chain
 template <bool DEPTH>
-__device__ GSRT_INLINE bool pose_terms(const gsrt_ubo& ubo, const gsrt_gauss_param& g, const float* __restrict__ row,
-                                       float m[16]) {
-    const float4 r0 = make_float4(row[0], row[1], row[2], row[3]);  // dppx, dppy, dA, dB
-    const float gC = row[4];
-    const float* MV = ubo.model_view;
-    const float* P = ubo.projection;
-    const float c4[4] = {g.center_opacity[0], g.center_opacity[1], g.center_opacity[2], 1.0f};
-    float t[4];
-    mul4v(MV, c4, t);
-    const float depth = -t[2];
-    if (!(depth > 0.0f)) return false;
-    float ph[4];
-    mul4v(P, t, ph);
-    const float fx = (cm(P, 0, 0) * (float)ubo.width) * 0.5f;
-    const float fy = (cm(P, 1, 1) * (float)ubo.height) * 0.5f;
-    const float id = 1.0f / depth;
-    const float id2 = id * id;
-    const float fxt0 = fx * t[0], fyt1 = fy * t[1];
-    const float j00 = fx * id, j02 = fxt0 * id2, j11 = fy * id, j12 = fyt1 * id2;
-    float T0[3], T1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        T0[k] = fmaf(j02, cm(MV, k, 2), j00 * cm(MV, k, 0));
-        T1[k] = fmaf(j12, cm(MV, k, 2), j11 * cm(MV, k, 1));
-    }
-    const float* cv = g.cov3d;
-    const float Sg[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
-    float u0[3], u1[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        u0[r] = fmaf(Sg[r * 3 + 2], T0[2], fmaf(Sg[r * 3 + 1], T0[1], Sg[r * 3 + 0] * T0[0]));
-        u1[r] = fmaf(Sg[r * 3 + 2], T1[2], fmaf(Sg[r * 3 + 1], T1[1], Sg[r * 3 + 0] * T1[0]));
-    }
-    const float v00 = fmaf(T0[2], u0[2], fmaf(T0[1], u0[1], T0[0] * u0[0])) + 0.3f;
-    const float v01 = fmaf(T0[2], u1[2], fmaf(T0[1], u1[1], T0[0] * u1[0]));
-    const float v11 = fmaf(T1[2], u1[2], fmaf(T1[1], u1[1], T1[0] * u1[0])) + 0.3f;
-    const float det = fmaf(v00, v11, -(v01 * v01));
-    if (!(det > 0.0f)) return false;
-    const float idet = 1.0f / det;
-    const float A = v11 * idet, B = -v01 * idet, C = v00 * idet;
-    // W = -Q G Q
-    const float gA = r0.z, hB = 0.5f * r0.w;
-    const float m00 = A * gA + B * hB, m01 = A * hB + B * gC, m10 = B * gA + C * hB, m11 = B * hB + C * gC;
-    const float w00 = -(m00 * A + m01 * B), w01 = -(m00 * B + m01 * C), w11 = -(m10 * B + m11 * C);
-    // dL/dT = 2 W [u0; u1], then to the Jacobian's four entries
-    float g0[3], g1[3];
-    float gj00 = 0.0f, gj02 = 0.0f, gj11 = 0.0f, gj12 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        g0[k] = 2.0f * (w00 * u0[k] + w01 * u1[k]);
-        g1[k] = 2.0f * (w01 * u0[k] + w11 * u1[k]);
-        gj00 = k ? gj00 + g0[k] * cm(MV, k, 0) : g0[k] * cm(MV, k, 0);
-        gj02 = k ? gj02 + g0[k] * cm(MV, k, 2) : g0[k] * cm(MV, k, 2);
-        gj11 = k ? gj11 + g1[k] * cm(MV, k, 1) : g1[k] * cm(MV, k, 1);
-        gj12 = k ? gj12 + g1[k] * cm(MV, k, 2) : g1[k] * cm(MV, k, 2);
-    }
-    const float gid = (gj00 * fx + gj11 * fy) + (2.0f * id) * (gj02 * fxt0 + gj12 * fyt1);
-    float gt[4] = {(gj02 * fx) * id2, (gj12 * fy) * id2, gid * id2, 0.0f};
-    // ppx = (ph0 / ph3 + 1) W / 2, ppy likewise
-    const float iw = 1.0f / ph[3];
-    const float gnx = r0.x * (0.5f * (float)ubo.width), gny = r0.y * (0.5f * (float)ubo.height);
-    const float gp0 = gnx * iw, gp1 = gny * iw, gp3 = -((gnx * ph[0] + gny * ph[1]) * (iw * iw));
-#pragma unroll
-    for (int c = 0; c < 4; ++c) gt[c] = gt[c] + ((cm(P, c, 0) * gp0 + cm(P, c, 1) * gp1) + cm(P, c, 3) * gp3);
-    if constexpr (DEPTH) gt[2] = gt[2] - row[6];  // depth = -t2
+__device__ GSRT_INLINE void pose_terms(const gsrt_ubo& ubo, const gsrt_gauss_param& g, const CorChain& f,
+                                       const float* __restrict__ row, float m[16]) {
+    CorChainGrad d;
+    cor_conic_grad(f, row, d);
+    cor_chain_grad<DEPTH>(ubo, f, row, d);
     // t = MV c4, and T's own dependence on MV's 3x3
+    const float c4[4] = {g.center_opacity[0], g.center_opacity[1], g.center_opacity[2], 1.0f};
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) m[c * 4 + r] = gt[r] * c4[c];
+        for (int r = 0; r < 4; ++r) m[c * 4 + r] = d.gt[r] * c4[c];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        m[c * 4 + 0] = m[c * 4 + 0] + g0[c] * j00;
-        m[c * 4 + 1] = m[c * 4 + 1] + g1[c] * j11;
-        m[c * 4 + 2] = m[c * 4 + 2] + (g0[c] * j02 + g1[c] * j12);
+        m[c * 4 + 0] = m[c * 4 + 0] + d.g0[c] * f.j00;
+        m[c * 4 + 1] = m[c * 4 + 1] + d.g1[c] * f.j11;
+        m[c * 4 + 2] = m[c * 4 + 2] + (d.g0[c] * f.j02 + d.g1[c] * f.j12);
     }
-    return true;
 }
 
 // The 16 sums over the workgroup's lanes, in a fixed order: down each wave by the xor butterfly (every lane ends with
@@ -154,8 +93,10 @@ __global__ __launch_bounds__(kPoseLanes) void k_pose_partial(uint32_t n, const g
         const size_t i = base + (size_t)j * kPoseLanes;
         if (i >= n) break;
         const gsrt_gauss_param g = params[i];
-        float m[16];
-        if (pose_terms<DEPTH>(ubo, g, rows + 8 * i, m)) {
+        CorChain f;
+        if (cor_chain(ubo, g, f) == kCorValid) {
+            float m[16];
+            pose_terms<DEPTH>(ubo, g, f, rows + 8 * i, m);
 #pragma unroll
             for (int k = 0; k < 16; ++k) acc[k] += (double)m[k];
         }
@@ -184,10 +125,8 @@ void launch_pose_grad(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt
                       bool depth, double* partial, float* out) {
     const uint32_t chunks = pose_grad_chunks(n);
     if (chunks) {
-        if (depth)
-            hipLaunchKernelGGL(k_pose_partial<true>, dim3(chunks), dim3(kPoseLanes), 0, s, n, ubo, params, rows, partial);
-        else
-            hipLaunchKernelGGL(k_pose_partial<false>, dim3(chunks), dim3(kPoseLanes), 0, s, n, ubo, params, rows, partial);
+        const auto kernel = depth ? k_pose_partial<true> : k_pose_partial<false>;
+        hipLaunchKernelGGL(kernel, dim3(chunks), dim3(kPoseLanes), 0, s, n, ubo, params, rows, partial);
     }
     hipLaunchKernelGGL(k_pose_final, dim3(1), dim3(kPoseFinalLanes), 0, s, chunks, partial, out);  // no chunks: 16 x +0
 }

@@ -1,5 +1,6 @@
 // gsrt_project.hpp -- the per-splat COR/REF projection (device code), shared by k_project (gsrt_scene.hip) and the
-// fused prep kernel k_prep_cor (gsrt_render.hip: frontier blocks + projection blocks in one launch).
+// fused prep kernel k_prep_cor (gsrt_render.hip: frontier blocks + projection blocks in one launch), and the COR chain
+// with its backward, which k_splat_grad_to_model (gsrt_scene.hip) and k_pose_partial (gsrt_pose_grad.hip) run too.
 #pragma once
 
 #include "gsrt_internal.hpp"
@@ -55,53 +56,152 @@ __device__ GSRT_INLINE void project_ref(const gsrt_ubo& u, const gsrt_gauss_para
     s.valid = 1u;
 }
 
-// COR projection: depth = -view z, Jacobian of the actual pixel mapping (fx = P00 W/2, fy = P11 H/2),
-// V += 0.3 I low-pass, conic = V^-1 (COR flags).
-__device__ GSRT_INLINE void project_cor(const gsrt_ubo& u, const gsrt_gauss_param& g, SplatRec& s) {
+// The COR projection's float32 chain from a Gaussian's centre and cov3d to its conic: depth = -view z, Jacobian of the
+// actual pixel mapping (fx = P00 W/2, fy = P11 H/2), V += 0.3 I low-pass, conic = V^-1 (COR flags):
+//   t = MV (c, 1), ph = P t, id = 1 / depth = -1 / t2,
+//   j00 = fx id, j02 = (fx t0) id^2, j11 = fy id, j12 = (fy t1) id^2, T0 = j02 MVz + j00 MVx, T1 = j12 MVz + j11 MVy,
+//   u0 = Sigma T0, u1 = Sigma T1, V = [[T0 u0, T0 u1], [T0 u1, T1 u1]] + 0.3 I, Q = [[A, B], [B, C]] = V^-1.
+// The one statement of it on the device: the projection (project_cor) reads its outputs from it, and its backward
+// (cor_chain_grad) its intermediates, so the roundings the two see are the same ones.
+struct CorChain {
+    float t[4], ph[4];
+    // what follows: only past kCorBehind
+    float fx, fy, id, id2, fxt0, fyt1, j00, j02, j11, j12;
+    float T0[3], T1[3], u0[3], u1[3];
+    float v00, v01, v11, det;
+    float idet, A, B, C;  // only when kCorValid
+};
+// how far the chain got: the centre is not in front of the camera (depth <= 0 or NaN), V is not invertible
+// (det <= 0 or NaN), or all of CorChain is filled
+enum CorReach { kCorBehind, kCorSingular, kCorValid };
+
+__device__ GSRT_INLINE CorReach cor_chain(const gsrt_ubo& u, const gsrt_gauss_param& g, CorChain& f) {
     const float* MV = u.model_view;
     const float* P = u.projection;
     const float c4[4] = {g.center_opacity[0], g.center_opacity[1], g.center_opacity[2], 1.0f};
-    float t[4];
-    mul4v(MV, c4, t);
-    s.valid = 0u;
-    s.depth = -t[2];
-    s.opacity = g.center_opacity[3];
-    s.ppx = s.ppy = s.a = s.b = s.c = 0.0f;
-    if (!(s.depth > 0.0f)) return;
-    float ph[4];
-    mul4v(P, t, ph);
-    const float ndcx = ph[0] / ph[3], ndcy = ph[1] / ph[3];
-    s.ppx = ((ndcx + 1.0f) * (float)u.width) * 0.5f;
-    s.ppy = ((ndcy + 1.0f) * (float)u.height) * 0.5f;
-    const float fx = (cm(P, 0, 0) * (float)u.width) * 0.5f;
-    const float fy = (cm(P, 1, 1) * (float)u.height) * 0.5f;
-    const float id = 1.0f / s.depth;
-    const float id2 = id * id;
-    const float j00 = fx * id, j02 = (fx * t[0]) * id2, j11 = fy * id, j12 = (fy * t[1]) * id2;
-    float T0[3], T1[3];
+    mul4v(MV, c4, f.t);
+    // ahead of the depth test although nothing needs it behind the camera: after the test the compiler sinks it, in a
+    // kernel that uses it only in the backward, to the end of the depth > 0 block, behind the det > 0 block, which then
+    // cannot take the backward in, and a valid Gaussian's row loads issue late (k_pose_partial: 0.8 % slower)
+    mul4v(P, f.t, f.ph);
+    const float depth = -f.t[2];
+    if (!(depth > 0.0f)) return kCorBehind;
+    f.fx = (cm(P, 0, 0) * (float)u.width) * 0.5f;
+    f.fy = (cm(P, 1, 1) * (float)u.height) * 0.5f;
+    f.id = 1.0f / depth;
+    f.id2 = f.id * f.id;
+    f.fxt0 = f.fx * f.t[0];
+    f.fyt1 = f.fy * f.t[1];
+    f.j00 = f.fx * f.id;
+    f.j02 = f.fxt0 * f.id2;
+    f.j11 = f.fy * f.id;
+    f.j12 = f.fyt1 * f.id2;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        T0[k] = fmaf(j02, cm(MV, k, 2), j00 * cm(MV, k, 0));
-        T1[k] = fmaf(j12, cm(MV, k, 2), j11 * cm(MV, k, 1));
+        f.T0[k] = fmaf(f.j02, cm(MV, k, 2), f.j00 * cm(MV, k, 0));
+        f.T1[k] = fmaf(f.j12, cm(MV, k, 2), f.j11 * cm(MV, k, 1));
     }
     const float* cv = g.cov3d;
     const float Sg[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
-    float u0[3], u1[3];
+    const float *T0 = f.T0, *T1 = f.T1, *u0 = f.u0, *u1 = f.u1;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        u0[r] = fmaf(Sg[r * 3 + 2], T0[2], fmaf(Sg[r * 3 + 1], T0[1], Sg[r * 3 + 0] * T0[0]));
-        u1[r] = fmaf(Sg[r * 3 + 2], T1[2], fmaf(Sg[r * 3 + 1], T1[1], Sg[r * 3 + 0] * T1[0]));
+        f.u0[r] = fmaf(Sg[r * 3 + 2], T0[2], fmaf(Sg[r * 3 + 1], T0[1], Sg[r * 3 + 0] * T0[0]));
+        f.u1[r] = fmaf(Sg[r * 3 + 2], T1[2], fmaf(Sg[r * 3 + 1], T1[1], Sg[r * 3 + 0] * T1[0]));
     }
-    const float v00 = fmaf(T0[2], u0[2], fmaf(T0[1], u0[1], T0[0] * u0[0])) + 0.3f;
-    const float v01 = fmaf(T0[2], u1[2], fmaf(T0[1], u1[1], T0[0] * u1[0]));
-    const float v11 = fmaf(T1[2], u1[2], fmaf(T1[1], u1[1], T1[0] * u1[0])) + 0.3f;
-    const float det = fmaf(v00, v11, -(v01 * v01));
-    if (!(det > 0.0f)) return;
-    const float idet = 1.0f / det;
-    s.a = v11 * idet;
-    s.b = -v01 * idet;
-    s.c = v00 * idet;
-    s.valid = 1u;
+    f.v00 = fmaf(T0[2], u0[2], fmaf(T0[1], u0[1], T0[0] * u0[0])) + 0.3f;
+    f.v01 = fmaf(T0[2], u1[2], fmaf(T0[1], u1[1], T0[0] * u1[0]));
+    f.v11 = fmaf(T1[2], u1[2], fmaf(T1[1], u1[1], T1[0] * u1[0])) + 0.3f;
+    f.det = fmaf(f.v00, f.v11, -(f.v01 * f.v01));
+    if (!(f.det > 0.0f)) return kCorSingular;
+    f.idet = 1.0f / f.det;
+    f.A = f.v11 * f.idet;
+    f.B = -f.v01 * f.idet;
+    f.C = f.v00 * f.idet;
+    return kCorValid;
+}
+
+// COR projection: cor_chain's outputs as a splat record. depth and opacity are always written, the pixel position once
+// the centre is in front of the camera, the conic only for a valid splat.
+__device__ GSRT_INLINE void project_cor(const gsrt_ubo& u, const gsrt_gauss_param& g, SplatRec& s) {
+    CorChain f;
+    const CorReach reach = cor_chain(u, g, f);
+    s.valid = reach == kCorValid ? 1u : 0u;
+    s.depth = -f.t[2];
+    s.opacity = g.center_opacity[3];
+    s.ppx = s.ppy = s.a = s.b = s.c = 0.0f;
+    if (reach == kCorBehind) return;
+    const float ndcx = f.ph[0] / f.ph[3], ndcy = f.ph[1] / f.ph[3];
+    s.ppx = ((ndcx + 1.0f) * (float)u.width) * 0.5f;
+    s.ppy = ((ndcy + 1.0f) * (float)u.height) * 0.5f;
+    if (reach != kCorValid) return;
+    s.a = f.A;
+    s.b = f.B;
+    s.c = f.C;
+}
+
+// cor_chain backwards, for a valid Gaussian, in two steps (cor_conic_grad, then cor_chain_grad): a splat row's slots 0..4,
+// dL/d(ppx, ppy, A, B, C) (gsrt_render_splat_grad), to
+//   G = [[dA, dB/2], [dB/2, dC]], W = dL/dV = -Q G Q (symmetric; the 0.3 I is a constant),
+//   g0 = dL/dT0, g1 = dL/dT1: dL/dT = 2 W T Sigma = 2 W [u0; u1], T's dependence on the Jacobian's four entries only,
+//   gt = dL/dt: through j02, j12 (t0, t1), id (t2), and ppx = (ph0 / ph3 + 1) W / 2, ppy likewise, with the general P.
+// DEPTH: the row is gsrt_render_splat_depth_grad's, whose slot 6 holds dL/d(depth), depth = -t2: gt[2] - row[6].
+// The row is read here, so only a valid Gaussian's row is read at all (read ahead of the chain, k_pose_partial loads
+// every row and measured 3 to 6 % slower).
+// The longest chain of rounded operations from a Gaussian's parameters to gt (the head of the tests' N) ends in gt[2] by
+// way of the conic: t (4), id (1), id^2 (1), j02 (1), T0 (1), u0 (3), v00 (4), det (1), 1 / det (1), A (1), Q G (2),
+// W (2), dL/dT0 (2), dL/dj02 (3), dL/d(id) (4), dL/dt2 (1), + the ppx, ppy part (1): 33; DEPTH, - row[6] (1): 34. Each
+// kernel that carries gt further states its own tail.
+struct CorChainGrad {
+    float w00, w01, w11;
+    float g0[3], g1[3];
+    float gt[4];
+};
+
+// the first step, W: a function of its own so that k_splat_grad_to_model can form T^T W T between the two, where it
+// always stood (with it after the whole backward the kernel's instructions are scheduled differently and the call
+// measured slower: profiles/project_chain/timing.jsonl)
+__device__ GSRT_INLINE void cor_conic_grad(const CorChain& f, const float* __restrict__ row, CorChainGrad& d) {
+    const float A = f.A, B = f.B, C = f.C;
+    // W = -Q G Q
+    const float gA = row[2], hB = 0.5f * row[3], gC = row[4];
+    const float m00 = A * gA + B * hB, m01 = A * hB + B * gC, m10 = B * gA + C * hB, m11 = B * hB + C * gC;
+    d.w00 = -(m00 * A + m01 * B);
+    d.w01 = -(m00 * B + m01 * C);
+    d.w11 = -(m10 * B + m11 * C);
+}
+
+// the second step: g0, g1 and gt from d's W
+template <bool DEPTH>
+__device__ GSRT_INLINE void cor_chain_grad(const gsrt_ubo& u, const CorChain& f, const float* __restrict__ row,
+                                           CorChainGrad& d) {
+    const float* MV = u.model_view;
+    const float* P = u.projection;
+    const float w00 = d.w00, w01 = d.w01, w11 = d.w11;
+    // dL/dT = 2 W [u0; u1], then to the Jacobian's four entries
+    float gj00 = 0.0f, gj02 = 0.0f, gj11 = 0.0f, gj12 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float g0 = 2.0f * (w00 * f.u0[k] + w01 * f.u1[k]), g1 = 2.0f * (w01 * f.u0[k] + w11 * f.u1[k]);
+        d.g0[k] = g0;
+        d.g1[k] = g1;
+        gj00 = k ? gj00 + g0 * cm(MV, k, 0) : g0 * cm(MV, k, 0);
+        gj02 = k ? gj02 + g0 * cm(MV, k, 2) : g0 * cm(MV, k, 2);
+        gj11 = k ? gj11 + g1 * cm(MV, k, 1) : g1 * cm(MV, k, 1);
+        gj12 = k ? gj12 + g1 * cm(MV, k, 2) : g1 * cm(MV, k, 2);
+    }
+    const float gid = (gj00 * f.fx + gj11 * f.fy) + (2.0f * f.id) * (gj02 * f.fxt0 + gj12 * f.fyt1);
+    d.gt[0] = (gj02 * f.fx) * f.id2;
+    d.gt[1] = (gj12 * f.fy) * f.id2;
+    d.gt[2] = gid * f.id2;
+    d.gt[3] = 0.0f;
+    // ppx = (ph0 / ph3 + 1) W / 2, ppy likewise
+    const float iw = 1.0f / f.ph[3];
+    const float gnx = row[0] * (0.5f * (float)u.width), gny = row[1] * (0.5f * (float)u.height);
+    const float gp0 = gnx * iw, gp1 = gny * iw, gp3 = -((gnx * f.ph[0] + gny * f.ph[1]) * (iw * iw));
+#pragma unroll
+    for (int c = 0; c < 4; ++c) d.gt[c] = d.gt[c] + ((cm(P, c, 0) * gp0 + cm(P, c, 1) * gp1) + cm(P, c, 3) * gp3);
+    if constexpr (DEPTH) d.gt[2] = d.gt[2] - row[6];  // depth = -t2
 }
 
 // One wave per workgroup and <= 80 VGPRs (6 waves/SIMD): the COR projection of frame f+1 runs on the prep

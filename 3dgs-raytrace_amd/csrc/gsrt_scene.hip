@@ -85,22 +85,19 @@ void launch_project(hipStream_t st, uint32_t n, uint32_t mode, const gsrt_ubo& u
                             depth_unsafe);
 }
 
-// project_cor backwards (gsrt_splat_grad_to_model): one lane per Gaussian takes its splat row (gsrt_render_splat_grad:
-// dL/d(ppx, ppy, A, B, C) in slots 0..4) to dL/d(centre) and dL/d(cov3d). The forward's float32 intermediates are
-// recomputed with project_cor's own operations; then
-//   Q = [[A, B], [B, C]] = V^-1, G = [[dA, dB/2], [dB/2, dC]], W = dL/dV = -Q G Q (symmetric; the 0.3 I is a constant),
+// cor_chain backwards to the model (gsrt_splat_grad_to_model): one lane per Gaussian takes its splat row
+// (gsrt_render_splat_grad: dL/d(ppx, ppy, A, B, C) in slots 0..4) to dL/d(centre) and dL/d(cov3d). cor_chain recomputes the
+// forward's float32 intermediates, cor_conic_grad and cor_chain_grad (gsrt_project.hpp) take the row to W = dL/dV and
+// dL/dt; this kernel's own part:
 //   dL/dSigma = T^T W T (an off-diagonal cov3d entry stands twice in Sigma: twice the matrix entry),
-//   dL/dT = 2 W T Sigma = 2 W [u0; u1], T0 = j02 MVz + j00 MVx, T1 = j12 MVz + j11 MVy with
-//   j00 = fx id, j02 = (fx t0) id^2, j11 = fy id, j12 = (fy t1) id^2, id = 1 / depth = -1 / t2,
-//   ppx = (ph0 / ph3 + 1) W / 2, ppy likewise, ph = P t with the general P, t = MV (c, 1),
-// and the centre's gradient is MV^T dL/dt. An invalid splat (depth <= 0 or det <= 0) gets +0, and so does a valid one
-// whose row is all +0 (no ray reached it): a zero is written as +0. No atomics.
-// The longest chain of rounded operations from the inputs to an output (the tests' N) ends in a centre entry by way of
-// the conic: t (4), id (1), id^2 (1), j02 (1), T0 (1), u0 (3), v00 (4), det (1), 1 / det (1), A (1), Q G (2), W (2),
-// dL/dT0 (2), dL/dj02 (3), dL/d(id) (4), dL/dt2 (1), + the ppx, ppy part (1), MV^T dL/dt (4): 37.
+//   dL/d(centre) = MV^T dL/dt.
+// An invalid splat (depth <= 0 or det <= 0) gets +0, and so does a valid one whose row is all +0 (no ray reached it): a
+// zero is written as +0. No atomics.
+// The longest chain of rounded operations from the inputs to an output (the tests' N) ends in a centre entry:
+// cor_chain_grad's 33 to dL/dt, then MV^T dL/dt (4): 37.
 // DEPTH (the second instantiation, gsrt_splat_depth_grad_to_model): the row is gsrt_render_splat_depth_grad's, whose
-// slot 6 holds dL/d(depth), depth = -t2: one more step, dL/dt2 - row[6] (1), before MV^T dL/dt: 38. Without DEPTH slot 6
-// is never read. Nothing of it reaches cov3d.
+// slot 6 holds dL/d(depth): cor_chain_grad's 34, then the same 4: 38. Without DEPTH slot 6 is never read. Nothing of it
+// reaches cov3d.
 // Not a prep kernel: ordinary priority, 256 lanes a workgroup as the scene build's kernels.
 template <bool DEPTH>
 __global__ __launch_bounds__(256) void k_splat_grad_to_model(uint32_t n, const gsrt_ubo ubo,
@@ -111,81 +108,27 @@ __global__ __launch_bounds__(256) void k_splat_grad_to_model(uint32_t n, const g
     if (i >= n) return;
     const gsrt_gauss_param g = params[i];
     const float* row = rows + 8 * (size_t)i;
-    const float4 r0 = make_float4(row[0], row[1], row[2], row[3]);  // dppx, dppy, dA, dB
-    const float gC = row[4];
     float dc[3] = {0.0f, 0.0f, 0.0f}, dS[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    const float* MV = ubo.model_view;
-    const float* P = ubo.projection;
-    const float c4[4] = {g.center_opacity[0], g.center_opacity[1], g.center_opacity[2], 1.0f};
-    float t[4];
-    mul4v(MV, c4, t);
-    const float depth = -t[2];
-    if (depth > 0.0f) {
-        float ph[4];
-        mul4v(P, t, ph);
-        const float fx = (cm(P, 0, 0) * (float)ubo.width) * 0.5f;
-        const float fy = (cm(P, 1, 1) * (float)ubo.height) * 0.5f;
-        const float id = 1.0f / depth;
-        const float id2 = id * id;
-        const float fxt0 = fx * t[0], fyt1 = fy * t[1];
-        const float j00 = fx * id, j02 = fxt0 * id2, j11 = fy * id, j12 = fyt1 * id2;
-        float T0[3], T1[3];
+    CorChain f;
+    if (cor_chain(ubo, g, f) == kCorValid) {
+        CorChainGrad d;
+        cor_conic_grad(f, row, d);
+        // dL/dSigma = T^T W T, entries in cov3d's order
+        const float *T0 = f.T0, *T1 = f.T1;
+        int e = 0;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T0[k] = fmaf(j02, cm(MV, k, 2), j00 * cm(MV, k, 0));
-            T1[k] = fmaf(j12, cm(MV, k, 2), j11 * cm(MV, k, 1));
-        }
-        const float* cv = g.cov3d;
-        const float Sg[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
-        float u0[3], u1[3];
+        for (int a = 0; a < 3; ++a)
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            u0[r] = fmaf(Sg[r * 3 + 2], T0[2], fmaf(Sg[r * 3 + 1], T0[1], Sg[r * 3 + 0] * T0[0]));
-            u1[r] = fmaf(Sg[r * 3 + 2], T1[2], fmaf(Sg[r * 3 + 1], T1[1], Sg[r * 3 + 0] * T1[0]));
-        }
-        const float v00 = fmaf(T0[2], u0[2], fmaf(T0[1], u0[1], T0[0] * u0[0])) + 0.3f;
-        const float v01 = fmaf(T0[2], u1[2], fmaf(T0[1], u1[1], T0[0] * u1[0]));
-        const float v11 = fmaf(T1[2], u1[2], fmaf(T1[1], u1[1], T1[0] * u1[0])) + 0.3f;
-        const float det = fmaf(v00, v11, -(v01 * v01));
-        if (det > 0.0f) {
-            const float idet = 1.0f / det;
-            const float A = v11 * idet, B = -v01 * idet, C = v00 * idet;
-            // W = -Q G Q
-            const float gA = r0.z, hB = 0.5f * r0.w;
-            const float m00 = A * gA + B * hB, m01 = A * hB + B * gC, m10 = B * gA + C * hB, m11 = B * hB + C * gC;
-            const float w00 = -(m00 * A + m01 * B), w01 = -(m00 * B + m01 * C), w11 = -(m10 * B + m11 * C);
-            // dL/dSigma = T^T W T, entries in cov3d's order
-            int e = 0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = a; b < 3; ++b) {
-                    const float s = (w00 * (T0[a] * T0[b]) + w01 * (T0[a] * T1[b] + T1[a] * T0[b])) + w11 * (T1[a] * T1[b]);
-                    dS[e++] = a == b ? s : 2.0f * s;
-                }
-            // dL/dT = 2 W [u0; u1], then to the Jacobian's four entries
-            float gj00 = 0.0f, gj02 = 0.0f, gj11 = 0.0f, gj12 = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float g0 = 2.0f * (w00 * u0[k] + w01 * u1[k]), g1 = 2.0f * (w01 * u0[k] + w11 * u1[k]);
-                gj00 = k ? gj00 + g0 * cm(MV, k, 0) : g0 * cm(MV, k, 0);
-                gj02 = k ? gj02 + g0 * cm(MV, k, 2) : g0 * cm(MV, k, 2);
-                gj11 = k ? gj11 + g1 * cm(MV, k, 1) : g1 * cm(MV, k, 1);
-                gj12 = k ? gj12 + g1 * cm(MV, k, 2) : g1 * cm(MV, k, 2);
+            for (int b = a; b < 3; ++b) {
+                const float s = (d.w00 * (T0[a] * T0[b]) + d.w01 * (T0[a] * T1[b] + T1[a] * T0[b])) + d.w11 * (T1[a] * T1[b]);
+                dS[e++] = a == b ? s : 2.0f * s;
             }
-            const float gid = (gj00 * fx + gj11 * fy) + (2.0f * id) * (gj02 * fxt0 + gj12 * fyt1);
-            float gt[4] = {(gj02 * fx) * id2, (gj12 * fy) * id2, gid * id2, 0.0f};
-            // ppx = (ph0 / ph3 + 1) W / 2, ppy likewise
-            const float iw = 1.0f / ph[3];
-            const float gnx = r0.x * (0.5f * (float)ubo.width), gny = r0.y * (0.5f * (float)ubo.height);
-            const float gp0 = gnx * iw, gp1 = gny * iw, gp3 = -((gnx * ph[0] + gny * ph[1]) * (iw * iw));
+        cor_chain_grad<DEPTH>(ubo, f, row, d);
+        const float* MV = ubo.model_view;
+        const float* gt = d.gt;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) gt[c] = gt[c] + ((cm(P, c, 0) * gp0 + cm(P, c, 1) * gp1) + cm(P, c, 3) * gp3);
-            if constexpr (DEPTH) gt[2] = gt[2] - row[6];  // depth = -t2
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                dc[k] = ((cm(MV, k, 0) * gt[0] + cm(MV, k, 1) * gt[1]) + cm(MV, k, 2) * gt[2]) + cm(MV, k, 3) * gt[3];
-        }
+        for (int k = 0; k < 3; ++k)
+            dc[k] = ((cm(MV, k, 0) * gt[0] + cm(MV, k, 1) * gt[1]) + cm(MV, k, 2) * gt[2]) + cm(MV, k, 3) * gt[3];
     }
     float* oc = grad_center + 3 * (size_t)i;
     float* ov = grad_cov + 6 * (size_t)i;
@@ -200,12 +143,9 @@ __global__ __launch_bounds__(256) void k_splat_grad_to_model(uint32_t n, const g
 void launch_splat_grad_to_model(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params,
                                 const float* rows, float* grad_center, float* grad_cov, bool accumulate, bool depth) {
     if (!n) return;
-    if (depth)
-        hipLaunchKernelGGL(k_splat_grad_to_model<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, ubo, params, rows,
-                           grad_center, grad_cov, accumulate ? 1u : 0u);
-    else
-        hipLaunchKernelGGL(k_splat_grad_to_model<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, ubo, params, rows,
-                           grad_center, grad_cov, accumulate ? 1u : 0u);
+    const auto kernel = depth ? k_splat_grad_to_model<true> : k_splat_grad_to_model<false>;
+    hipLaunchKernelGGL(kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, ubo, params, rows, grad_center, grad_cov,
+                       accumulate ? 1u : 0u);
 }
 
 // Scene-update copies (gsrt_scene_update / refit / stream_pages from device sources) beside the previous frames'

@@ -22,9 +22,9 @@ pytestmark = pytest.mark.gpu
 
 CASES = TG.CASES
 # the longest chain of rounded float32 operations from the kernel's inputs to one of its outputs, counted in
-# k_splat_grad_to_model as it is written (its header lists the steps): t 4, 1 / depth 1, its square 1, j02 1, T0 1, u0 3,
-# v00 4, det 1, 1 / det 1, A 1, Q G 2, W 2, dL/dT0 2, dL/dj02 3, dL/d(1 / depth) 4, dL/dt2 1, + the ppx, ppy part 1,
-# MV^T dL/dt 4
+# k_splat_grad_to_model as it is written (cor_chain_grad's header in gsrt_project.hpp lists the steps to dL/dt): t 4,
+# 1 / depth 1, its square 1, j02 1, T0 1, u0 3, v00 4, det 1, 1 / det 1, A 1, Q G 2, W 2, dL/dT0 2, dL/dj02 3,
+# dL/d(1 / depth) 4, dL/dt2 1, + the ppx, ppy part 1, MV^T dL/dt 4
 CHAIN_OPS = 37
 EPS = 2.0 ** -24
 _REF = {}

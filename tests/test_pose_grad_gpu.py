@@ -18,6 +18,7 @@ import pytest
 
 import cor_f64_pose as PQ
 import gsrt
+import oracle as O
 import pose_cases as PC
 import test_depth_grad_f64 as SD
 import test_depth_grad_gpu as TD
@@ -125,6 +126,30 @@ def test_nonaffine_view_and_general_projection(ctx, depth):
     G, B, valid = PC.reference(ubo, params, rows, depth)
     assert valid.sum() > 500 and (B > 0).all() and np.abs(G[3]).min() > 0
     hold("pose-grad non-affine depth" if depth else "pose-grad non-affine", 777, got, G, B)
+
+
+@pytest.mark.parametrize("depth", [False, True], ids=["plain", "depth"])
+def test_translation_column_is_the_centre_gradient_bit_for_bit(ctx, depth):
+    """gsrt_pose_grad and gsrt_splat_grad_to_model carry one dL/dt (cor_chain_grad): for a single Gaussian under a view
+    whose 3x3 is the identity, the gradient's translation column equals the centre's gradient exactly. Column 3 of the pose
+    contribution is gt[r] * 1 with no direct term, and the double sum of one term rounds back to the same float; the centre's
+    MV^T gt is ((1 gt[k] + 0) + 0) + 0 gt[3]. Compared as floats (a zero's sign would not matter), and every value
+    non-zero: 16 seeded Gaussians with random rows under a general projection."""
+    P = PC.nonaffine_camera()["projection"][0]
+    rng = np.random.default_rng(1601)
+    for seed in range(16):
+        mv = O.translate(*rng.uniform(-2.0, 2.0, 3))
+        ubo = PC.camera(mv, P)
+        assert ubo["model_view"][0].tobytes() == mv.tobytes() and (ubo["projection"][0] != 0).sum() >= 12
+        params, aabbs, rows, behind = PC.synthetic(1, 500 + seed, ubo)
+        assert not behind.any() and rows[0, :7].all()
+        sc = built(ctx, params, aabbs)
+        try:
+            pose = sc.pose_grad(ubo, rows, depth=depth)
+            centre, _ = sc.model_grad(ubo, rows, depth=depth)
+        finally:
+            sc.close()
+        assert pose[12:15].all() and (pose[12:15] == centre[0]).all(), (seed, pose[12:16], centre[0])
 
 
 def test_deterministic_across_calls_and_workspace_regrowth():
