@@ -33,12 +33,19 @@
 // "loss L l1 A ssim S mse M" and writes the loss's gradient with respect to the frame as raw float32 W*H*4, the file
 // --splat-grad, --sh-grad and --opacity-grad read. Usage errors: a gradient run (it renders no frame), the other
 // --loss options without --loss-target, channels not 3 or 4, lambda outside [0, 1].
+// --loss-mask FILE (W*H weights), --loss-background r,g,b, --loss-depth-target FILE (W*H depths; with --depth, whose frame
+// supplies the premultiplied depth) [--loss-depth-weight w (1 by default)] [--loss-depth-grad-out FILE], all beside
+// --loss-target: the loss is gsrt_frame_loss's instead, the line printed gains "depth_l1 D depth_samples K", and the two
+// gradients written are what --splat-grad and --depth-grad read. Usage errors: any of them without --loss-target, a
+// background that is not three numbers, --loss-depth-target without --depth, the depth weight or gradient without
+// --loss-depth-target, --loss-depth-grad-out without --loss-grad-out.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/gsrt_test.h"  // gsrt_synth_cloud: the synthetic clouds of --benchmark
@@ -63,6 +70,9 @@ struct Options {
     float loss_lambda = 0.2f;
     uint32_t loss_channels = 3;
     bool loss_options_given = false;  // --loss-lambda, --loss-channels or --loss-grad-out
+    std::string loss_mask, loss_depth_target, loss_depth_grad_out;  // any of these five: gsrt_frame_loss
+    float loss_background[3] = {0.0f, 0.0f, 0.0f}, loss_depth_weight = 1.0f;
+    bool loss_background_given = false, loss_depth_weight_given = false;
 };
 
 // A gradient run, --NAME FILE with --NAME-out FILE: the upstream gradient image (raw float32, W*H*image_channels) in, the
@@ -107,7 +117,9 @@ bool given(const Options& o, const GradOption& g) { return !(o.*g.in).empty() ||
                  "                   [--opacity-grad FILE --opacity-grad-out FILE]\n"
                  "                   [--splat-grad FILE --splat-grad-out FILE] [--depth-grad FILE]\n"
                  "                   [--pose-grad-out FILE]\n"
-                 "                   [--loss-target FILE [--loss-lambda L] [--loss-channels 3|4] [--loss-grad-out FILE]]\n");
+                 "                   [--loss-target FILE [--loss-lambda L] [--loss-channels 3|4] [--loss-grad-out FILE]\n"
+                 "                    [--loss-mask FILE] [--loss-background r,g,b]\n"
+                 "                    [--loss-depth-target FILE [--loss-depth-weight w] [--loss-depth-grad-out FILE]]]\n");
     std::exit(2);
 }
 
@@ -166,6 +178,16 @@ Options parse(int argc, char** argv) {
         else if (a == "--loss-lambda") { o.loss_lambda = std::strtof(val(), nullptr); o.loss_options_given = true; }
         else if (a == "--loss-channels") { o.loss_channels = to_u32(val(), "--loss-channels"); o.loss_options_given = true; }
         else if (a == "--loss-grad-out") { o.loss_grad_out = val(); o.loss_options_given = true; }
+        else if (a == "--loss-mask") { o.loss_mask = val(); o.loss_options_given = true; }
+        else if (a == "--loss-background") {
+            float* b = o.loss_background;
+            char tail = 0;
+            if (std::sscanf(val(), "%f,%f,%f%c", b, b + 1, b + 2, &tail) != 3) usage("--loss-background takes r,g,b");
+            o.loss_background_given = o.loss_options_given = true;
+        }
+        else if (a == "--loss-depth-target") { o.loss_depth_target = val(); o.loss_options_given = true; }
+        else if (a == "--loss-depth-weight") { o.loss_depth_weight = std::strtof(val(), nullptr); o.loss_depth_weight_given = o.loss_options_given = true; }
+        else if (a == "--loss-depth-grad-out") { o.loss_depth_grad_out = val(); o.loss_options_given = true; }
         else if (a == "--help" || a == "-h") usage(nullptr);
         else usage(("unknown option " + a).c_str());
     }
@@ -193,10 +215,14 @@ Options parse(int argc, char** argv) {
         clash(!o.features.empty() || !o.features_out.empty(), "--features");
         for (const GradOption* older = kGradOptions; older != g; ++older) clash(given(o, *older), older->name);
     }
-    if (o.loss_target.empty() && o.loss_options_given) usage("--loss-lambda, --loss-channels and --loss-grad-out go with --loss-target");
+    if (o.loss_target.empty() && o.loss_options_given) usage("--loss-lambda, --loss-channels, --loss-grad-out and the other --loss options go with --loss-target");
     if (!o.loss_target.empty()) {
         if (o.loss_channels != 3 && o.loss_channels != 4) usage("--loss-channels must be 3 or 4");
         if (!(o.loss_lambda >= 0.0f && o.loss_lambda <= 1.0f)) usage("--loss-lambda must be in [0, 1]");
+        if (!o.loss_depth_target.empty() && o.depth.empty()) usage("--loss-depth-target needs --depth (the frame's depth image)");
+        if (o.loss_depth_target.empty() && (o.loss_depth_weight_given || !o.loss_depth_grad_out.empty()))
+            usage("--loss-depth-weight and --loss-depth-grad-out go with --loss-depth-target");
+        if (!o.loss_depth_grad_out.empty() && o.loss_grad_out.empty()) usage("--loss-depth-grad-out needs --loss-grad-out");
         for (const GradOption& g : kGradOptions)
             if (given(o, g)) usage((std::string("--loss-target cannot be combined with ") + g.name + " (a gradient run renders no frame)").c_str());
     }
@@ -389,11 +415,46 @@ int main(int argc, char** argv) {
                          target.size(), o.loss_channels);
             rc = 1;
         }
-        float sc[4] = {0, 0, 0, 0};
-        if (!rc)
+        // W * H raw float32 each: the mask and the target depth in, the depth's gradient (what --depth-grad reads) out
+        const bool frame_loss = !o.loss_mask.empty() || o.loss_background_given || !o.loss_depth_target.empty();
+        std::vector<float> mask(o.loss_mask.empty() ? 0 : px), tdepth(o.loss_depth_target.empty() ? 0 : px);
+        std::vector<float> gdepth(o.loss_depth_grad_out.empty() ? 0 : px);
+        for (const auto& in : {std::make_pair(&o.loss_mask, &mask), std::make_pair(&o.loss_depth_target, &tdepth)}) {
+            if (rc || in.second->empty()) continue;
+            f = std::fopen(in.first->c_str(), "rb");
+            const bool all = f && std::fread(in.second->data(), sizeof(float), px, f) == px && std::fgetc(f) == EOF;
+            if (f) std::fclose(f);
+            if (!all) {
+                std::fprintf(stderr, "gsrt_render: %s: not %zu float32 values (pixels)\n", in.first->c_str(), px);
+                rc = 1;
+            }
+        }
+        float sc[GSRT_FRAME_LOSS_SCALARS] = {0, 0, 0, 0, 0, 0};
+        if (!rc && frame_loss) {
+            gsrt_frame_loss_params P{};
+            P.lambda = o.loss_lambda;
+            for (int c = 0; c < 3; ++c) P.background[c] = o.loss_background[c];
+            P.depth_weight = tdepth.empty() ? 0.0f : o.loss_depth_weight;
+            P.alpha_min = 1.0f / 255.0f;
+            P.flags = o.loss_background_given ? GSRT_LOSS_BACKGROUND : 0u;
+            rc = check(gsrt_frame_loss(ctx, o.width, o.height, rgba.data(), target.data(), o.loss_channels,
+                                       mask.empty() ? nullptr : mask.data(), tdepth.empty() ? nullptr : depth.data(),
+                                       tdepth.empty() ? nullptr : tdepth.data(), &P, sc, gimg.empty() ? nullptr : gimg.data(),
+                                       gdepth.empty() ? nullptr : gdepth.data()), ctx, "frame_loss");
+            if (!rc)
+                std::printf("loss %.9g l1 %.9g ssim %.9g mse %.9g depth_l1 %.9g depth_samples %.9g\n", sc[0], sc[1], sc[2],
+                            sc[3], sc[4], sc[5]);
+        } else if (!rc) {
             rc = check(gsrt_image_loss(ctx, o.width, o.height, rgba.data(), target.data(), o.loss_channels, o.loss_lambda, sc,
                                        gimg.empty() ? nullptr : gimg.data()), ctx, "image_loss");
-        if (!rc) std::printf("loss %.9g l1 %.9g ssim %.9g mse %.9g\n", sc[0], sc[1], sc[2], sc[3]);
+            if (!rc) std::printf("loss %.9g l1 %.9g ssim %.9g mse %.9g\n", sc[0], sc[1], sc[2], sc[3]);
+        }
+        if (!rc && !gdepth.empty()) {
+            f = std::fopen(o.loss_depth_grad_out.c_str(), "wb");
+            const bool ok = f && std::fwrite(gdepth.data(), sizeof(float), gdepth.size(), f) == gdepth.size();
+            if ((f && std::fclose(f) != 0) || !ok) rc = check(GSRT_E_IO, nullptr, o.loss_depth_grad_out.c_str());
+            if (!rc) std::printf("wrote %s\n", o.loss_depth_grad_out.c_str());
+        }
         if (!rc && !gimg.empty()) {
             f = std::fopen(o.loss_grad_out.c_str(), "wb");
             const bool ok = f && std::fwrite(gimg.data(), sizeof(float), gimg.size(), f) == gimg.size();

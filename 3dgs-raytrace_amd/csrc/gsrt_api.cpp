@@ -1614,6 +1614,143 @@ gsrt_status gsrt_image_loss(gsrt_ctx* ctx, uint32_t width, uint32_t height, cons
                            &tmpv);
 }
 
+// ---- frame loss (gsrt_image_loss.hip): gsrt_image_loss over a background, under a mask, with a depth term ------------
+// what both forms of gsrt_frame_loss refuse before anything is queued or written
+static gsrt_status check_frame_loss_args(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba,
+                                         const float* target, uint32_t target_channels, const float* mask,
+                                         const float* depth, const float* target_depth, const gsrt_frame_loss_params* P,
+                                         const float* out, const float* grad_image, const float* grad_depth) {
+    if (!ctx) return GSRT_E_ARG;
+    const std::string name = "gsrt_frame_loss: ";
+    if (!rgba || !target || !out) return fail(ctx, GSRT_E_ARG, name + "rgba, target or out is NULL");
+    if (!P) return fail(ctx, GSRT_E_ARG, name + "params is NULL");
+    if (width == 0 || height == 0 || width > 32768 || height > 32768)
+        return fail(ctx, GSRT_E_ARG, name + "width and height must be 1..32768");
+    if (target_channels != 3 && target_channels != 4) return fail(ctx, GSRT_E_ARG, name + "target_channels must be 3 or 4");
+    if (!(P->lambda >= 0.0f && P->lambda <= 1.0f)) return fail(ctx, GSRT_E_ARG, name + "params.lambda must be in [0, 1]");
+    if (P->flags & ~GSRT_LOSS_BACKGROUND) return fail(ctx, GSRT_E_ARG, name + "an unknown flag in params.flags");
+    if (P->reserved) return fail(ctx, GSRT_E_ARG, name + "params.reserved must be zero");
+    if (P->flags & GSRT_LOSS_BACKGROUND)
+        for (float b : P->background)
+            if (!std::isfinite(b)) return fail(ctx, GSRT_E_ARG, name + "params.background must be finite");
+    if (!(P->depth_weight >= 0.0f)) return fail(ctx, GSRT_E_ARG, name + "params.depth_weight is negative or NaN");
+    if (!(P->alpha_min > 0.0f && P->alpha_min <= 1.0f)) return fail(ctx, GSRT_E_ARG, name + "params.alpha_min must be in (0, 1]");
+    if (!depth != !target_depth) return fail(ctx, GSRT_E_ARG, name + "depth and target_depth come together or not at all");
+    if (grad_depth && (!depth || !grad_image)) return fail(ctx, GSRT_E_ARG, name + "grad_depth needs depth and grad_image");
+    const size_t px = (size_t)width * height;
+    struct Range {
+        const float* p;
+        size_t floats;
+    };
+    const Range in[5] = {{rgba, 4 * px}, {target, target_channels * px}, {mask, px}, {depth, px}, {target_depth, px}};
+    const Range outs[3] = {{out, GSRT_FRAME_LOSS_SCALARS}, {grad_image, 4 * px}, {grad_depth, px}};
+    const auto overlap = [](const Range& a, const Range& b) {
+        const uintptr_t pa = reinterpret_cast<uintptr_t>(a.p), pb = reinterpret_cast<uintptr_t>(b.p);
+        return a.p && b.p && pa < pb + sizeof(float) * b.floats && pb < pa + sizeof(float) * a.floats;
+    };
+    for (int o = 0; o < 3; ++o) {
+        for (const Range& r : in)
+            if (overlap(outs[o], r)) return fail(ctx, GSRT_E_ARG, name + "an output overlaps an input");
+        for (int q = o + 1; q < 3; ++q)
+            if (overlap(outs[o], outs[q])) return fail(ctx, GSRT_E_ARG, name + "two outputs overlap");
+    }
+    return GSRT_OK;
+}
+
+// the call's kernels on the render stream; every pointer is a device pointer (d_out nullptr: the workspace's six floats,
+// whose address *d_out_used receives) and the arguments are checked
+static gsrt_status frame_loss_enqueue(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_rgba,
+                                      const float* d_target, uint32_t target_channels, const float* d_mask,
+                                      const float* d_depth, const float* d_target_depth, const gsrt_frame_loss_params& P,
+                                      float* d_out, float* d_grad, float* d_grad_depth, float** d_out_used = nullptr) {
+    const uintptr_t wide = reinterpret_cast<uintptr_t>(d_rgba) | reinterpret_cast<uintptr_t>(d_grad) |
+                           (target_channels == 4 ? reinterpret_cast<uintptr_t>(d_target) : 0);
+    if (wide % 16u)
+        return fail(ctx, GSRT_E_ARG, "gsrt_frame_loss: rgba, grad_image and a 4-channel target must be 16-byte aligned on the device");
+    const size_t px = (size_t)width * height, tiles = gsrt::image_loss_tiles(width, height);
+    const size_t need = 5 * tiles + 3 + (d_grad ? (9 * px + 1) / 2 : 0);
+    if (!ctx->d_loss_ws || ctx->loss_ws_doubles < need) {
+        GSRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a queued call may still use the smaller one
+        if (gsrt_status s = grow(ctx, &ctx->d_loss_ws, &ctx->loss_ws_doubles, need); s != GSRT_OK) return s;
+    }
+    float* const ws_out = reinterpret_cast<float*>(ctx->d_loss_ws + 5 * tiles);
+    if (d_out_used) *d_out_used = d_out ? d_out : ws_out;
+    gsrt::FrameLossArgs A{};
+    A.W = width, A.H = height;
+    A.rgba = d_rgba, A.target = d_target, A.mask = d_mask, A.depth = d_depth, A.target_depth = d_target_depth;
+    A.has_bg = P.flags & GSRT_LOSS_BACKGROUND;
+    for (int c = 0; c < 3; ++c) A.bg[c] = A.has_bg ? P.background[c] : 0.0f;
+    A.alpha_min = P.alpha_min, A.lambda = P.lambda, A.depth_weight = P.depth_weight;
+    gsrt::launch_frame_loss(ctx->stream, A, target_channels, ctx->d_loss_ws, ws_out + GSRT_FRAME_LOSS_SCALARS,
+                            d_out ? d_out : ws_out, d_grad, d_grad_depth);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_frame_loss_async(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_rgba,
+                                  const float* d_target, uint32_t target_channels, const float* d_mask,
+                                  const float* d_depth, const float* d_target_depth,
+                                  const gsrt_frame_loss_params* params, float* d_out, float* d_grad_image,
+                                  float* d_grad_depth) {
+    gsrt_status s = check_frame_loss_args(ctx, width, height, d_rgba, d_target, target_channels, d_mask, d_depth,
+                                          d_target_depth, params, d_out, d_grad_image, d_grad_depth);
+    if (s != GSRT_OK) return s;
+    (void)hipSetDevice(ctx->device);
+    return frame_loss_enqueue(ctx, width, height, d_rgba, d_target, target_channels, d_mask, d_depth, d_target_depth,
+                              *params, d_out, d_grad_image, d_grad_depth);
+}
+
+gsrt_status gsrt_frame_loss(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const float* target,
+                            uint32_t target_channels, const float* mask, const float* depth, const float* target_depth,
+                            const gsrt_frame_loss_params* params, float out[GSRT_FRAME_LOSS_SCALARS], float* grad_image,
+                            float* grad_depth) {
+    gsrt_status s = check_frame_loss_args(ctx, width, height, rgba, target, target_channels, mask, depth, target_depth,
+                                          params, out, grad_image, grad_depth);
+    if (s != GSRT_OK) return s;
+    (void)hipSetDevice(ctx->device);
+    const bool dev = is_device_ptr(rgba);
+    for (const float* p : {target, mask, depth, target_depth, (const float*)grad_image, (const float*)grad_depth})
+        if (p && dev != is_device_ptr(p))
+            return fail(ctx, GSRT_E_ARG, "gsrt_frame_loss: the images and gradients must all be host pointers or all be device pointers");
+    if (is_device_ptr(out)) return fail(ctx, GSRT_E_ARG, "gsrt_frame_loss: out is a host pointer");
+    const size_t px = (size_t)width * height, f = sizeof(float);
+    const size_t scalars = f * GSRT_FRAME_LOSS_SCALARS;
+    float* d_out = nullptr;
+    if (dev) {
+        s = frame_loss_enqueue(ctx, width, height, rgba, target, target_channels, mask, depth, target_depth, *params,
+                               nullptr, grad_image, grad_depth, &d_out);
+        return finish_blocking(ctx, s, {{out, d_out, scalars, "gsrt_frame_loss: scalar download failed"}});
+    }
+    // host images: one device block, rgba | target | mask | depth | target depth | the two gradients
+    Staging tmp;
+    GSRT_HIP(ctx, hipMalloc(&tmp.base, Staging::unit(f * 4 * px) + Staging::unit(f * target_channels * px) +
+                                           (mask ? Staging::unit(f * px) : 0) + (depth ? 2 * Staging::unit(f * px) : 0) +
+                                           (grad_image ? Staging::unit(f * 4 * px) : 0) +
+                                           (grad_depth ? Staging::unit(f * px) : 0)));
+    void* const tmpv = tmp.base;
+    const auto upload = [&](const float* src, size_t floats) -> float* {
+        if (!src) return nullptr;
+        float* const d = tmp.take<float>(floats);
+        if (s == GSRT_OK && hipMemcpyAsync(d, src, f * floats, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            s = fail(ctx, GSRT_E_DEVICE, "gsrt_frame_loss: upload failed");
+        return d;
+    };
+    const float* const d_rgba = upload(rgba, 4 * px);
+    const float* const d_target = upload(target, target_channels * px);
+    const float* const d_mask = upload(mask, px);
+    const float* const d_depth = upload(depth, px);
+    const float* const d_target_depth = upload(target_depth, px);
+    float* const d_grad = grad_image ? tmp.take<float>(4 * px) : nullptr;
+    float* const d_grad_depth = grad_depth ? tmp.take<float>(px) : nullptr;
+    if (s == GSRT_OK)
+        s = frame_loss_enqueue(ctx, width, height, d_rgba, d_target, target_channels, d_mask, d_depth, d_target_depth,
+                               *params, nullptr, d_grad, d_grad_depth, &d_out);
+    return finish_blocking(ctx, s, {{out, d_out, scalars, "gsrt_frame_loss: scalar download failed"},
+                                    {grad_image, d_grad, f * 4 * px, "gsrt_frame_loss: gradient download failed"},
+                                    {grad_depth, d_grad_depth, f * px, "gsrt_frame_loss: depth gradient download failed"}},
+                           &tmpv);
+}
+
 // ---- the optimiser step (gsrt_model_step.hip) -----------------------------------------------------------------------
 // On the render stream, behind the gradient calls that filled the tables. The calls work on model arrays, not on a scene.
 static const char* check_adam(const gsrt_adam_params* A) {

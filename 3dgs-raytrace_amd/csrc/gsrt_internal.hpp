@@ -171,7 +171,8 @@ struct gsrt_ctx {
     uint32_t* d_densify_ws = nullptr;
     size_t densify_ws_words = 0;
     // gsrt_image_loss: per tile three partial sums (doubles), then four floats for a blocking call's scalars, then, for a
-    // call with a gradient, the nine derivative planes of W x H floats; grown on demand, used in stream order on `stream`
+    // call with a gradient, the nine derivative planes of W x H floats; grown on demand, used in stream order on `stream`.
+    // gsrt_frame_loss lays its own call out in the same block: five doubles per tile, six floats (three doubles), the planes
     double* d_loss_ws = nullptr;
     size_t loss_ws_doubles = 0;
     // gsrt_pose_grad: per chunk of Gaussians one partial of 16 doubles, then 16 floats for a blocking call's result; grown
@@ -486,6 +487,22 @@ uint32_t image_loss_tiles(uint32_t width, uint32_t height);
 void launch_image_loss(hipStream_t s, uint32_t width, uint32_t height, const float* rgba, const float* target,
                        uint32_t target_channels, float lambda, double* partial, float* maps, float* out, float* grad);
 void image_loss_window(float out[11]);
+// the frame loss (gsrt_frame_loss; the same file and tiles). FrameLossArgs: the call's inputs as the kernels take them,
+// device pointers, mask and depth / target_depth nullptr when absent. launch_frame_loss: as launch_image_loss, with five
+// doubles a tile in `partial`, six floats in out, and grad_depth (nullable, W x H floats) written beside grad.
+struct FrameLossArgs {
+    uint32_t W, H;
+    const float* rgba;
+    const float* target;
+    const float* mask;
+    const float* depth;
+    const float* target_depth;
+    float bg[3];
+    uint32_t has_bg;
+    float alpha_min, lambda, depth_weight;
+};
+void launch_frame_loss(hipStream_t s, const FrameLossArgs& A, uint32_t target_channels, double* partial, float* maps,
+                       float* out, float* grad, float* grad_depth);
 // the camera's gradient (gsrt_pose_grad.hip). kPoseChunk: the consecutive Gaussians one workgroup of the first kernel sums
 // into one partial of 16 doubles; kPoseFinalLanes: the lanes of the second kernel's one workgroup, which sums the partials
 // (gsrt_debug_pose_grad_layout reports both). launch_pose_grad: rows (n x 8) chained to the 16 floats of out; partial holds

@@ -75,7 +75,7 @@ EXPORTS = [
     "gsrt_debug_frame_refusal_kind", "gsrt_render_splat_depth_grad", "gsrt_render_splat_depth_grad_async",
     "gsrt_splat_depth_grad_to_model", "gsrt_splat_depth_grad_to_model_async", "gsrt_debug_frame_refusal_any",
     "gsrt_density_stats_add", "gsrt_density_stats_add_async", "gsrt_densify_count", "gsrt_densify", "gsrt_densify_async",
-    "gsrt_image_loss", "gsrt_image_loss_async", "gsrt_image_loss_window",
+    "gsrt_image_loss", "gsrt_image_loss_async", "gsrt_image_loss_window", "gsrt_frame_loss", "gsrt_frame_loss_async",
     "gsrt_adam_scalars", "gsrt_model_step", "gsrt_model_step_async", "gsrt_model_activate", "gsrt_model_activate_async",
     "gsrt_model_deactivate", "gsrt_model_deactivate_async", "gsrt_model_opacity_reset", "gsrt_model_opacity_reset_async",
     "gsrt_pose_grad", "gsrt_pose_grad_async", "gsrt_pose_twist", "gsrt_ubo_apply_twist", "gsrt_debug_pose_grad_layout",
@@ -215,6 +215,8 @@ def _load():
         "gsrt_image_loss": ([P, u32, u32, P, P, u32, f32, P, P], i32),
         "gsrt_image_loss_async": ([P, u32, u32, P, P, u32, f32, P, P], i32),
         "gsrt_image_loss_window": ([P], i32),
+        "gsrt_frame_loss": ([P, u32, u32, P, P, u32, P, P, P, P, P, P, P], i32),
+        "gsrt_frame_loss_async": ([P, u32, u32, P, P, u32, P, P, P, P, P, P, P], i32),
         "gsrt_adam_scalars": ([P, P], i32),
         "gsrt_model_step": ([P, u32, P, P, P, P, P, P, P, P, P], i32),
         "gsrt_model_step_async": ([P, u32, P, P, P, P, P, P, P, P, P], i32),
@@ -730,6 +732,138 @@ def image_loss(ctx, rgba, target, lam=0.2, want_grad=True, *, width=None, height
     grad = np.zeros(x.shape, np.float32) if want_grad else None
     _check(lib.gsrt_image_loss(ctx.handle, x.shape[1], x.shape[0], _p(x), _p(y), y.shape[2], lam, _p(out), _p(grad)), ctx)
     return dict(loss=float(out[0]), l1=float(out[1]), ssim=float(out[2]), mse=float(out[3])), grad
+
+
+LOSS_BACKGROUND = 1  # GSRT_LOSS_BACKGROUND
+FRAME_LOSS_SCALARS = 6  # GSRT_FRAME_LOSS_SCALARS
+
+
+class FrameLossParams(ctypes.Structure):
+    """gsrt_frame_loss_params"""
+    _fields_ = [("lam", ctypes.c_float), ("background", ctypes.c_float * 3), ("depth_weight", ctypes.c_float),
+                ("alpha_min", ctypes.c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(FrameLossParams) == 32
+
+
+def frame_loss_params(lam=0.2, background=None, depth_weight=0.0, alpha_min=1.0 / 255.0, flags=None,
+                      reserved=0) -> FrameLossParams:
+    """a gsrt_frame_loss_params: lam the D-SSIM weight, background an (r, g, b) the frame is composited over (None: the
+    frame as it is; otherwise LOSS_BACKGROUND is set), depth_weight the weight of the depth term, alpha_min the least
+    alpha of a depth sample. flags / reserved: the struct's words as they are (flags None: from background). Nothing is
+    checked here; frame_loss refuses what gsrt_frame_loss does."""
+    bg = (0.0, 0.0, 0.0) if background is None else tuple(float(b) for b in background)
+    if len(bg) != 3:
+        raise GsrtError(E_ARG, "frame_loss_params: background is (r, g, b)")
+    if flags is None:
+        flags = 0 if background is None else LOSS_BACKGROUND
+    return FrameLossParams(lam, (ctypes.c_float * 3)(*bg), depth_weight, alpha_min, flags, reserved)
+
+
+def _frame_loss_refusal(P, width, height, channels, arrays, out, grads):
+    """why gsrt_frame_loss would refuse these arguments, or None. arrays: addresses of (rgba, target, mask, depth,
+    target_depth), 0 when absent; out: the scalars' address or 0; grads: (grad_image, grad_depth) addresses.
+    The C call's own list (gsrt.h), checked here too so that a refusal needs no device."""
+    rgba, target, mask, depth, target_depth = arrays
+    gimg, gdepth = grads
+    if not rgba or not target:
+        return "rgba or target is NULL"
+    if P is None:
+        return "params is NULL"
+    if not (1 <= width <= 32768 and 1 <= height <= 32768):
+        return "width and height must be 1..32768"
+    if channels not in (3, 4):
+        return "target_channels must be 3 or 4"
+    if not 0.0 <= P.lam <= 1.0:
+        return "lam must be in [0, 1]"
+    if P.flags & ~LOSS_BACKGROUND:
+        return "an unknown flag"
+    if P.reserved:
+        return "reserved must be zero"
+    if P.flags & LOSS_BACKGROUND and not all(np.isfinite(b) for b in P.background):
+        return "background must be finite"
+    if not P.depth_weight >= 0.0:
+        return "depth_weight is negative or NaN"
+    if not 0.0 < P.alpha_min <= 1.0:
+        return "alpha_min must be in (0, 1]"
+    if bool(depth) != bool(target_depth):
+        return "depth and target_depth come together or not at all"
+    if gdepth and (not depth or not gimg):
+        return "grad_depth needs depth and grad_image"
+    px = width * height
+    ins = [(rgba, 16 * px), (target, 4 * channels * px), (mask, 4 * px), (depth, 4 * px), (target_depth, 4 * px)]
+    outs = [(out, 4 * FRAME_LOSS_SCALARS), (gimg, 16 * px), (gdepth, 4 * px)]
+    hit = lambda a, b: a[0] and b[0] and a[0] < b[0] + b[1] and b[0] < a[0] + a[1]  # noqa: E731
+    for i, o in enumerate(outs):
+        if any(hit(o, r) for r in ins) or any(hit(o, q) for q in outs[i + 1:]):
+            return "an output overlaps an input or another output"
+    return None
+
+
+def frame_loss(ctx, rgba, target, *, mask=None, depth=None, target_depth=None, background=None, lam=0.2,
+               depth_weight=0.0, alpha_min=1.0 / 255.0, want_grad=True, params=None, width=None, height=None,
+               target_channels=None, d_out=0, d_grad=0, d_grad_depth=0, asynchronous=False):
+    """The loss of a training frame in one fused call (gsrt_frame_loss; the formulas are in gsrt.h): image_loss of the
+    frame composited over `background` ((r, g, b) or None) under the pixel weights `mask` ((H, W) or None), plus
+    depth_weight times the mean over all pixels of mask |depth / alpha - target_depth|, taken where target_depth is
+    finite and > 0 and alpha >= alpha_min. depth is the premultiplied (H, W) image of Scene.render_depth. params: a
+    FrameLossParams used as it is, in place of background, lam, depth_weight and alpha_min.
+    numpy arrays: returns (dict(loss=, l1=, ssim=, mse=, depth_l1=, depth_samples=), grad_image, grad_depth): the
+    gradients with respect to rgba (H, W, 4; alpha slot included) and to depth (H, W; None without depth), which
+    Scene.splat_grad and Scene.splat_depth_grad take as they are; both None with want_grad=False.
+    device addresses (int, 0 / None for an absent mask, depth or target_depth): width, height and target_channels are
+    needed; d_grad (H x W x 4 floats) and d_grad_depth (H x W floats) receive the gradients (0: none; want_grad is not
+    read). Blocks and returns the dict. With d_out, the address of 6 floats, the scalars are written there and None is
+    returned; then asynchronous=True only enqueues the call on ctx.stream (gsrt_frame_loss_async).
+    Arrays and addresses cannot be mixed. Every refusal of the C call is raised here as GsrtError(E_ARG) first."""
+    P = params if params is not None else frame_loss_params(lam, background, depth_weight, alpha_min)
+    if not isinstance(P, FrameLossParams):
+        raise GsrtError(E_ARG, "frame_loss: params is a FrameLossParams")
+    given = [a for a in (rgba, target, mask, depth, target_depth) if a is not None]
+    on_device = [isinstance(a, int) for a in given]
+    if any(on_device):
+        if not all(on_device):
+            raise GsrtError(E_ARG, "frame_loss: host arrays and device addresses are mixed")
+        if width is None or height is None or target_channels is None:
+            raise GsrtError(E_ARG, "frame_loss: device addresses need width, height and target_channels")
+        arrays = [int(a or 0) for a in (rgba, target, mask, depth, target_depth)]
+        why = _frame_loss_refusal(P, width, height, target_channels, arrays, int(d_out or 0),
+                                  (int(d_grad or 0), int(d_grad_depth or 0)))
+        if why is None and (arrays[0] | int(d_grad or 0) | (arrays[1] if target_channels == 4 else 0)) % 16:
+            why = "rgba, grad_image and a 4-channel target must be 16-byte aligned on the device"
+        if why:
+            raise GsrtError(E_ARG, "frame_loss: " + why)
+        args = (width, height, _addr(arrays[0]), _addr(arrays[1]), target_channels, _addr(arrays[2]), _addr(arrays[3]),
+                _addr(arrays[4]), ctypes.byref(P))
+        if asynchronous or d_out:
+            _check(lib.gsrt_frame_loss_async(ctx.handle, *args, _addr(d_out), _addr(d_grad), _addr(d_grad_depth)), ctx)
+            if not asynchronous:
+                ctx.synchronize()
+            return None
+        out = np.zeros(FRAME_LOSS_SCALARS, np.float32)
+        _check(lib.gsrt_frame_loss(ctx.handle, *args, _p(out), _addr(d_grad), _addr(d_grad_depth)), ctx)
+        return dict(zip(("loss", "l1", "ssim", "mse", "depth_l1", "depth_samples"), (float(v) for v in out)))
+    if d_out or d_grad or d_grad_depth:
+        raise GsrtError(E_ARG, "frame_loss: host arrays and device addresses are mixed")
+    x = np.ascontiguousarray(rgba, dtype=np.float32)
+    y = np.ascontiguousarray(target, dtype=np.float32)
+    if x.ndim != 3 or x.shape[2] != 4 or y.ndim != 3 or y.shape[:2] != x.shape[:2] or y.shape[2] not in (3, 4):
+        raise GsrtError(E_ARG, "frame_loss: rgba is an (H, W, 4) array and target an (H, W, 3) or (H, W, 4) one")
+    planes = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (mask, depth, target_depth)]
+    if any(a is not None and a.shape != x.shape[:2] for a in planes):
+        raise GsrtError(E_ARG, "frame_loss: mask, depth and target_depth are (H, W) arrays")
+    out = np.zeros(FRAME_LOSS_SCALARS, np.float32)
+    grad = np.zeros(x.shape, np.float32) if want_grad else None
+    gdepth = np.zeros(x.shape[:2], np.float32) if want_grad and planes[1] is not None else None
+    addr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+    why = _frame_loss_refusal(P, x.shape[1], x.shape[0], y.shape[2], [addr(x), addr(y)] + [addr(a) for a in planes],
+                              addr(out), (addr(grad), addr(gdepth)))
+    if why:
+        raise GsrtError(E_ARG, "frame_loss: " + why)
+    _check(lib.gsrt_frame_loss(ctx.handle, x.shape[1], x.shape[0], _p(x), _p(y), y.shape[2], _p(planes[0]), _p(planes[1]),
+                               _p(planes[2]), ctypes.byref(P), _p(out), _p(grad), _p(gdepth)), ctx)
+    return (dict(zip(("loss", "l1", "ssim", "mse", "depth_l1", "depth_samples"), (float(v) for v in out))), grad, gdepth)
 
 
 # ---------------------------------------------------------------- the optimiser step

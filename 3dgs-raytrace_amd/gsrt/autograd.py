@@ -32,6 +32,9 @@ fused call (gsrt.image_loss), so that a training step stays in the library's ker
         optimiser.step()
     image_metrics(ctx, rgba.detach(), target)                 # dict(loss=, l1=, ssim=, mse=, psnr=), no gradient
 
+frame_loss is the same call with a background colour, a pixel mask and an L1 depth term (gsrt.frame_loss), differentiable
+with respect to rgba, alpha included, and to the depth of render_model(..., depth=True) (the loop: its docstring).
+
 and the optimiser: model_step chains the gradient tables to the raw parameters (unnormalised quaternion, log scale, logit
 opacity), takes the Adam step and writes the next frame's scene arrays in one fused call (gsrt.model_step), so that a whole
 training loop needs neither torch.autograd nor torch.optim (the loop: model_step's docstring).
@@ -48,6 +51,8 @@ import math
 
 from . import MODE_COR, density_stats_add, image_loss
 from . import densify as _densify
+from . import frame_loss as _frame_loss
+from . import frame_loss_params as _frame_loss_params
 from . import model_step as _model_step
 
 
@@ -503,6 +508,57 @@ def photometric_loss(ctx, rgba, target, lam=0.2):
     Context.synchronize() after it."""
     _check_images("photometric_loss", rgba, target)
     return _PhotometricLoss.apply(rgba, target, ctx, float(lam))
+
+
+class _FrameLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgba, depth, target, target_depth, mask, gctx, params):
+        dev = rgba.device
+        planes = [None if t is None else t.detach().contiguous() for t in (mask, depth, target_depth)]
+        x, y = rgba.detach().contiguous(), target.detach().contiguous()
+        H, W = int(x.shape[0]), int(x.shape[1])
+        out = torch.empty((6,), dtype=torch.float32, device=dev)
+        grad = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+        gdepth = None if depth is None else torch.empty((H, W), dtype=torch.float32, device=dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+        torch.cuda.current_stream(dev).synchronize()
+        _frame_loss(gctx, x.data_ptr(), y.data_ptr(), mask=ptr(planes[0]), depth=ptr(planes[1]),
+                    target_depth=ptr(planes[2]), params=params, width=W, height=H, target_channels=int(y.shape[2]),
+                    d_out=out.data_ptr(), d_grad=grad.data_ptr(), d_grad_depth=ptr(gdepth), asynchronous=True)
+        gctx.synchronize()
+        ctx.has_depth = depth is not None
+        ctx.save_for_backward(*([grad] if gdepth is None else [grad, gdepth]))
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        kept = ctx.saved_tensors
+        return (grad_output * kept[0], grad_output * kept[1] if ctx.has_depth else None, None, None, None, None, None)
+
+
+def frame_loss(ctx, rgba, target, depth=None, target_depth=None, mask=None, background=None, lam=0.2, depth_weight=0.0,
+               alpha_min=1.0 / 255.0):
+    """The loss of a training frame (gsrt.frame_loss, gsrt_frame_loss_async; the formulas are in gsrt.h) as a 0-dim tensor:
+    photometric_loss of `rgba` composited over `background` ((r, g, b) or None) under the pixel weights `mask` ((H, W) or
+    None), plus depth_weight times the mean over all pixels of mask |depth / alpha - target_depth|, taken where
+    target_depth is finite and > 0 and alpha >= alpha_min. Differentiable with respect to `rgba`, alpha included, and to
+    `depth` ((H, W), premultiplied, as render_model(depth=True) returns it); target, target_depth and mask get nothing.
+    All tensors float32 on rgba's device. One fused call in the forward, which keeps both gradients; the backward scales
+    them by the upstream scalar. Blocking synchronisation on both sides, as photometric_loss. The depth-supervised loop:
+
+        rgba, depth = render_model(scene, ubo, center, rot, scale, opacity, sh, depth=True)
+        loss = frame_loss(ctx, rgba, target, depth, target_depth, mask=mask, background=(1, 1, 1), depth_weight=0.1)
+        loss.backward()              # both gradients go into the splat-depth gradient frame as they are
+        optimiser.step()"""
+    _check_images("frame_loss", rgba, target)
+    if (depth is None) != (target_depth is None):
+        raise ValueError("frame_loss: depth and target_depth come together or not at all")
+    for name, t in (("depth", depth), ("target_depth", target_depth), ("mask", mask)):
+        if t is not None and (t.dtype != torch.float32 or t.device != rgba.device or
+                              tuple(t.shape) != tuple(rgba.shape[:2])):
+            raise ValueError(f"frame_loss: {name} must be an (H, W) float32 tensor on rgba's device")
+    params = _frame_loss_params(float(lam), background, float(depth_weight), float(alpha_min))
+    return _FrameLoss.apply(rgba, depth, target, target_depth, mask, ctx, params)
 
 
 def image_metrics(ctx, rgba, target, lam=0.2):

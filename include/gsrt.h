@@ -629,6 +629,66 @@ gsrt_status gsrt_image_loss_async(gsrt_ctx* ctx, uint32_t width, uint32_t height
  * rounded to float once (a constant table; no device or ctx needed) */
 gsrt_status gsrt_image_loss_window(float out[11]);
 
+/* ---- frame loss: the photometric loss over a background, under a pixel mask, with a depth term ----
+ * gsrt_image_loss with the three things a training frame needs beside it, each optional, in the same fused call. Per
+ * pixel p of a width x height frame:
+ *     a = rgba[p][3], read only with GSRT_LOSS_BACKGROUND or when depth is given (otherwise alpha is not read, junk and
+ *         NaN included);   m = mask ? mask[p] : 1   (mask: float[H][W], any weights; 3DGS's alpha_mask)
+ *     x_c  = rgb_c + (1 - a) * bg_c with GSRT_LOSS_BACKGROUND (bg = params.background), rgb_c without
+ *     x'_c = m * x_c,  y'_c = m * y_c   with a mask; without one nothing is multiplied
+ *     l1, mse, ssim: gsrt_image_loss's formulas on x', y' (the same window, the same zero padding, means over N = 3 H W)
+ *     depth sample: depth given, target_depth[p] finite and > 0, and a >= alpha_min (a NaN alpha is no sample);
+ *         on a sample, with D = depth[p] (the frame's premultiplied depth, gsrt_render_depth / gsrt_depth_buffer):
+ *         q = D / a,  e = q - target_depth[p]
+ *     depth_l1 = sum over samples of m |e| / (H W)   (3DGS's mean over all pixels),  depth_samples = their count
+ *     loss = (1 - lambda) l1 + lambda (1 - ssim) + depth_weight * depth_l1
+ * out = {loss, l1, ssim, mse, depth_l1, depth_samples}: per-pixel terms in float32, summed in double in a fixed order,
+ * each scalar rounded to float once, as gsrt_image_loss does.
+ * Gradients, in the layouts gsrt_render_splat_grad and gsrt_render_splat_depth_grad take as they are. g_c is
+ * gsrt_image_loss's per-value gradient evaluated on x', y'; kd = (float)(depth_weight / (H W)) (the quotient in double):
+ *     grad_image[p][c] = m * g_c
+ *     grad_image[p][3] = B - (s * q) / a, where
+ *         B = -(m * ((g_0 * bg_0 + g_1 * bg_1) + g_2 * bg_2)) with GSRT_LOSS_BACKGROUND and +0 without,
+ *         s = (kd * m) * sign(e) on a depth sample, sign(0) = 0, and the second term is absent on any other pixel;
+ *     grad_depth[p]    = s / a on a depth sample, +0 elsewhere
+ * in float32, every operation rounded on its own in the order written (x_c = rgb_c + ((1 - a) * bg_c)); without a mask
+ * every "m *" is left out, so that a mask of ones and no mask give the same bits. With neither background nor depth the
+ * alpha slot is +0 and, with no mask either, the four shared scalars and grad_image are gsrt_image_loss's, bit for bit.
+ * This is d(D / a): Gdepth / a into grad_depth and -Gdepth D / a^2 into the alpha slot, the division the depth frame
+ * leaves to its caller. A gather without atomics: the same inputs give the same bits, scalars and both gradients.
+ * grad_image (nullable) float[H][W][4]; grad_depth (nullable) float[H][W], needs depth and grad_image. All arrays are
+ * host pointers or all device pointers (on the device rgba, grad_image and a 4-channel target 16-byte aligned); out is a
+ * host pointer; the call runs on gsrt_stream() and blocks until the outputs are complete.
+ * GSRT_E_ARG, with nothing written, named in gsrt_last_error: everything gsrt_image_loss refuses; a NULL params; an
+ * unknown flag or a non-zero reserved; a NaN or infinite background with the flag set; depth_weight negative or NaN;
+ * alpha_min outside (0, 1] or NaN; exactly one of depth and target_depth; grad_depth without depth or without
+ * grad_image; host and device pointers mixed; an output overlapping an input or another output; a misaligned device
+ * rgba, grad_image or 4-channel target.
+ * Not provided: inverse-depth or scale-and-shift-invariant depth losses, other windows, multi-scale SSIM, a per-channel
+ * mask. */
+#define GSRT_LOSS_BACKGROUND 1u
+#define GSRT_FRAME_LOSS_SCALARS 6
+typedef struct gsrt_frame_loss_params {
+    float lambda;          /* D-SSIM weight, [0, 1] */
+    float background[3];   /* read with GSRT_LOSS_BACKGROUND */
+    float depth_weight;    /* >= 0; weight of the depth term */
+    float alpha_min;       /* (0, 1]; a pixel is a depth sample only when alpha >= this */
+    uint32_t flags;
+    uint32_t reserved;     /* zero */
+} gsrt_frame_loss_params;
+gsrt_status gsrt_frame_loss(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const float* target,
+                            uint32_t target_channels, const float* mask, const float* depth, const float* target_depth,
+                            const gsrt_frame_loss_params* params, float out[GSRT_FRAME_LOSS_SCALARS], float* grad_image,
+                            float* grad_depth);
+/* the same, enqueued on gsrt_stream() without a host synchronisation, behind the frame that wrote d_rgba and d_depth and
+ * ahead of the gradient frame that reads the two gradients. Device pointers only, d_out (6 floats) included. (A call for
+ * a larger frame than any before it on this ctx allocates its workspace first.) */
+gsrt_status gsrt_frame_loss_async(gsrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_rgba,
+                                  const float* d_target, uint32_t target_channels, const float* d_mask,
+                                  const float* d_depth, const float* d_target_depth,
+                                  const gsrt_frame_loss_params* params, float* d_out, float* d_grad_image,
+                                  float* d_grad_depth);
+
 /* ---- the optimiser step on the device: fused Adam over the raw model ------------------------------
  * With these calls this header alone describes a 3DGS training loop: gsrt_render, gsrt_image_loss, gsrt_render_splat_grad,
  * gsrt_splat_grad_to_model, gsrt_render_sh_grad, gsrt_model_step, gsrt_scene_update + gsrt_refit_bvh + gsrt_scene_set_sh
