@@ -2005,6 +2005,82 @@ gsrt_status gsrt_model_deactivate_async(gsrt_ctx* ctx, uint32_t n, const gsrt_mo
     return model_deactivate_any(ctx, false, n, act, raw);
 }
 
+// gsrt_model_remap: the call is not told how many rows `in` has. With a host origin it reads the count off it (the
+// largest entry + 1), which sizes the staging and the overlap check; a device origin is not read on the host, and only
+// the first row of each `in` array takes part in the overlap check then.
+static gsrt_status model_remap_any(gsrt_ctx* ctx, bool blocking, uint32_t n_out, const int32_t* origin,
+                                   const gsrt_model_arrays* in, const gsrt_model_arrays* out) {
+    if (!ctx) return GSRT_E_ARG;
+    const std::string name = "gsrt_model_remap: ";
+    if (!in || !out) return fail(ctx, GSRT_E_ARG, name + "a NULL struct");
+    if (n_out > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, name + "n_out above GSRT_MAX_GAUSSIANS");
+    if (const char* why = check_model_sets({in, out}, *in)) return fail(ctx, GSRT_E_ARG, name + why);
+    (void)hipSetDevice(ctx->device);
+    gsrt_model_arrays a = *in, r = *out;
+    float* org = reinterpret_cast<float*>(const_cast<int32_t*>(origin));
+    if (n_out && (!org || !a.center || !a.rot_rxyz || !a.scale || !a.opacity || !r.center || !r.rot_rxyz || !r.scale ||
+                  !r.opacity))
+        return fail(ctx, GSRT_E_ARG, name + "a NULL array");
+    if (!n_out) return GSRT_OK;
+    size_t n_in = 1;
+    if (!is_device_ptr(origin)) {
+        int64_t rows = 0;
+        for (uint32_t i = 0; i < n_out; ++i) rows = std::max<int64_t>(rows, (int64_t)origin[i] + 1);
+        n_in = (size_t)rows;
+    }
+    std::vector<StepArray> list;
+    model_set_arrays(list, a, n_in, true, false);
+    model_set_arrays(list, r, n_out, false, true);
+    list.push_back({&org, sizeof(int32_t) * (size_t)n_out, true, false});
+    const int side = check_step_arrays(ctx, name, list, n_out, {});
+    if (side < 0) return GSRT_E_ARG;
+    if (!blocking && side == 0) return fail(ctx, GSRT_E_ARG, name + "the async form takes device pointers only");
+    const auto run = [&]() -> gsrt_status {
+        gsrt::launch_model_remap(ctx->stream, n_out, reinterpret_cast<const int32_t*>(org), a, r);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, GSRT_E_DEVICE, name + "launch failed");
+        return GSRT_OK;
+    };
+    if (side == 1) {
+        const gsrt_status s = run();
+        return blocking ? finish_blocking(ctx, s, {}) : s;
+    }
+    return run_staged(ctx, name, list, run);
+}
+gsrt_status gsrt_model_remap(gsrt_ctx* ctx, uint32_t n_out, const int32_t* origin, const gsrt_model_arrays* in,
+                             const gsrt_model_arrays* out) {
+    return model_remap_any(ctx, true, n_out, origin, in, out);
+}
+gsrt_status gsrt_model_remap_async(gsrt_ctx* ctx, uint32_t n_out, const int32_t* d_origin, const gsrt_model_arrays* in,
+                                   const gsrt_model_arrays* out) {
+    return model_remap_any(ctx, false, n_out, d_origin, in, out);
+}
+
+// ---- normal noise (gsrt_rng.hip) ----------------------------------------------------------------------------------
+gsrt_status gsrt_normal_noise_async(gsrt_ctx* ctx, uint64_t count, uint64_t seed, uint32_t stream_id, float* d_out) {
+    if (!ctx) return GSRT_E_ARG;
+    if (!count) return GSRT_OK;
+    if (!d_out) return fail(ctx, GSRT_E_ARG, "gsrt_normal_noise: out is NULL");
+    if (!is_device_ptr(d_out)) return fail(ctx, GSRT_E_ARG, "gsrt_normal_noise: the async form takes a device pointer only");
+    if (reinterpret_cast<uintptr_t>(d_out) % 4u) return fail(ctx, GSRT_E_ARG, "gsrt_normal_noise: out is not 4-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    gsrt::launch_normal_noise(ctx->stream, count, seed, stream_id, d_out);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+gsrt_status gsrt_normal_noise(gsrt_ctx* ctx, uint64_t count, uint64_t seed, uint32_t stream_id, float* out) {
+    if (!ctx) return GSRT_E_ARG;
+    if (!count) return GSRT_OK;
+    if (!out) return fail(ctx, GSRT_E_ARG, "gsrt_normal_noise: out is NULL");
+    if (is_device_ptr(out)) return finish_blocking(ctx, gsrt_normal_noise_async(ctx, count, seed, stream_id, out), {});
+    (void)hipSetDevice(ctx->device);
+    float* d = nullptr;
+    if (hipMalloc(&d, sizeof(float) * count) != hipSuccess) return fail(ctx, GSRT_E_OOM, "gsrt_normal_noise: device allocation failed");
+    void* const tmpv = d;
+    gsrt::launch_normal_noise(ctx->stream, count, seed, stream_id, d);
+    gsrt_status s = hipGetLastError() == hipSuccess ? GSRT_OK : fail(ctx, GSRT_E_DEVICE, "gsrt_normal_noise: launch failed");
+    return finish_blocking(ctx, s, {{out, d, sizeof(float) * count, "gsrt_normal_noise: download failed"}}, &tmpv);
+}
+
 static gsrt_status opacity_reset_any(gsrt_ctx* ctx, bool blocking, uint32_t n, float* logit, float* m, float* v,
                                      float max_opacity) {
     if (!ctx) return GSRT_E_ARG;

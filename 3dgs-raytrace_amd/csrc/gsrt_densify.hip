@@ -1,8 +1,8 @@
 // gsrt_densify.hip -- adaptive density control on the device (gsrt_density_stats_add, gsrt_densify_count, gsrt_densify):
 // the densification statistic from splat rows, the clone / split / prune / keep decision per Gaussian, and one ordered
-// compaction pass that writes the new model.
+// compaction pass that writes the new model; and gsrt_model_remap, the gather that carries the optimiser state across it.
 //
-// All four kernels are HBM-bound streaming kernels at ordinary priority, 256 lanes a workgroup as the scene build's
+// All five kernels are HBM-bound streaming kernels at ordinary priority, 256 lanes a workgroup as the scene build's
 // kernels; none is a prep kernel. Per Gaussian: k_density_stats 32 B read + 8 B read-modify-write; k_densify_count 24 B
 // read; k_densify_write 24 B + 44 B (+ 24 B noise for a split) read, 48 B per output row written, plus the 192-B SH row and
 // the feature row read once per output row and written once.
@@ -200,6 +200,79 @@ __global__ __launch_bounds__(kDensBlock) void k_densify_write(uint32_t n, const 
             d[p] = s[(size_t)src[row] * fc + word];
         }
     }
+}
+
+// gsrt_model_remap: row i of every present array of `out` is row origin[i] of `in`, or +0 where origin[i] < 0: the
+// optimiser state of gsrt_densify's output, all arrays in one launch. A workgroup owns 256 consecutive output rows, the
+// scheme of k_densify_write's copy phase: each lane moves the small fields (11 words) of its own row, then consecutive
+// lanes take consecutive pieces of the run's SH rows (WIDE: 12 uint4 pieces a row where both tables are 16-byte aligned,
+// otherwise 48 words) and consecutive words of its feature rows, the source rows read from LDS. 44 B + 4 B origin read
+// and 44 B written per row, plus the SH and feature rows once each way. No atomics.
+template <bool WIDE>
+__global__ __launch_bounds__(kDensBlock) void k_model_remap(uint32_t n_out, const int32_t* __restrict__ origin,
+                                                            const gsrt_model_arrays in, const gsrt_model_arrays out) {
+    __shared__ int32_t src[kDensBlock];
+    const uint32_t t = threadIdx.x, base = blockIdx.x * kDensBlock, i = base + t;
+    const uint32_t rows = min(kDensBlock, n_out - base);
+    const int32_t g = i < n_out ? origin[i] : -1;
+    src[t] = g;
+    if (i < n_out) {
+        const uint32_t* ic = reinterpret_cast<const uint32_t*>(in.center) + 3 * (size_t)(g < 0 ? 0 : g);
+        const uint32_t* ir = reinterpret_cast<const uint32_t*>(in.rot_rxyz) + 4 * (size_t)(g < 0 ? 0 : g);
+        const uint32_t* is = reinterpret_cast<const uint32_t*>(in.scale) + 3 * (size_t)(g < 0 ? 0 : g);
+        uint32_t* oc = reinterpret_cast<uint32_t*>(out.center) + 3 * (size_t)i;
+        uint32_t* orr = reinterpret_cast<uint32_t*>(out.rot_rxyz) + 4 * (size_t)i;
+        uint32_t* os = reinterpret_cast<uint32_t*>(out.scale) + 3 * (size_t)i;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            oc[j] = g < 0 ? 0u : ic[j];
+            os[j] = g < 0 ? 0u : is[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) orr[j] = g < 0 ? 0u : ir[j];
+        reinterpret_cast<uint32_t*>(out.opacity)[i] = g < 0 ? 0u : reinterpret_cast<const uint32_t*>(in.opacity)[g];
+    }
+    if (!in.sh && !in.feature_channels) return;
+    __syncthreads();
+    if (in.sh) {
+        if constexpr (WIDE) {
+            const uint4* s = reinterpret_cast<const uint4*>(in.sh);
+            uint4* d = reinterpret_cast<uint4*>(out.sh) + (size_t)base * kShPieces;
+            for (uint32_t p = t; p < rows * kShPieces; p += kDensBlock) {
+                const uint32_t row = p / kShPieces, piece = p - row * kShPieces;
+                const int32_t h = src[row];
+                d[p] = h < 0 ? make_uint4(0u, 0u, 0u, 0u) : s[(size_t)h * kShPieces + piece];
+            }
+        } else {
+            const uint32_t* s = reinterpret_cast<const uint32_t*>(in.sh);
+            uint32_t* d = reinterpret_cast<uint32_t*>(out.sh) + (size_t)base * 48;
+            for (uint32_t p = t; p < rows * 48u; p += kDensBlock) {
+                const uint32_t row = p / 48u, word = p - row * 48u;
+                const int32_t h = src[row];
+                d[p] = h < 0 ? 0u : s[(size_t)h * 48 + word];
+            }
+        }
+    }
+    if (const uint32_t fc = in.feature_channels) {
+        const uint32_t* s = reinterpret_cast<const uint32_t*>(in.features);
+        uint32_t* d = reinterpret_cast<uint32_t*>(out.features) + (size_t)base * fc;
+        for (uint32_t p = t; p < rows * fc; p += kDensBlock) {
+            const uint32_t row = p / fc, word = p - row * fc;
+            const int32_t h = src[row];
+            d[p] = h < 0 ? 0u : s[(size_t)h * fc + word];
+        }
+    }
+}
+
+void launch_model_remap(hipStream_t s, uint32_t n_out, const int32_t* origin, const gsrt_model_arrays& in,
+                        const gsrt_model_arrays& out) {
+    const uint32_t nblocks = densify_blocks(n_out);
+    if (!nblocks) return;
+    const bool wide = (reinterpret_cast<uintptr_t>(in.sh) | reinterpret_cast<uintptr_t>(out.sh)) % 16u == 0;
+    if (wide)
+        hipLaunchKernelGGL(k_model_remap<true>, dim3(nblocks), dim3(kDensBlock), 0, s, n_out, origin, in, out);
+    else
+        hipLaunchKernelGGL(k_model_remap<false>, dim3(nblocks), dim3(kDensBlock), 0, s, n_out, origin, in, out);
 }
 
 uint32_t densify_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kDensBlock - 1) / kDensBlock); }

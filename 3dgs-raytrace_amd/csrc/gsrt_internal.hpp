@@ -479,6 +479,11 @@ void launch_densify_count(hipStream_t s, uint32_t n, const gsrt_densify_params& 
 void launch_densify_write(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const gsrt_model_arrays& in,
                           const float* stats, const float* noise, const gsrt_model_arrays& out, int32_t* origin,
                           uint32_t cap, const uint32_t* block_base, const uint32_t* d_n_out);
+// gsrt_model_remap (gsrt_densify.hip): out's row i = in's row origin[i], +0 where origin[i] < 0; device pointers
+void launch_model_remap(hipStream_t s, uint32_t n_out, const int32_t* origin, const gsrt_model_arrays& in,
+                        const gsrt_model_arrays& out);
+// gsrt_normal_noise (gsrt_rng.hip): count Philox4x32-10 Box-Muller normals into out (a device pointer)
+void launch_normal_noise(hipStream_t s, uint64_t count, uint64_t seed, uint32_t stream_id, float* out);
 // the photometric loss (gsrt_image_loss.hip). image_loss_tiles: the tiles of a frame, each with three doubles in
 // `partial`. launch_image_loss: the statistics pass, the scalars {loss, l1, ssim, mse} into out and, when grad is not
 // nullptr, the gradient pass through maps (9 x width x height floats); every pointer a device pointer, rgba and grad

@@ -232,6 +232,54 @@ gsrt_status gsrt_ply_read(const char* path, float* center, float* rot_rxyz, floa
     return GSRT_OK;
 }
 
+// The writer: the raw model as it is (a .ply holds the unnormalised quaternion, the log scale and the logit), float32
+// little-endian, 3DGS's property order. f_rest is channel-major: f_rest_(ch * 15 + j) = sh[1 + j][ch], the inverse of the
+// reader's permutation.
+gsrt_status gsrt_ply_write(const char* path, uint32_t n, const gsrt_model_arrays* raw) {
+    if (!path || !raw) return GSRT_E_ARG;
+    if (raw->features || raw->feature_channels) return GSRT_E_ARG;
+    if (n && (!raw->center || !raw->rot_rxyz || !raw->scale || !raw->opacity)) return GSRT_E_ARG;
+    const bool with_sh = raw->sh != nullptr;
+    std::string head = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) + "\n";
+    const auto prop = [&](const std::string& name) { head += "property float " + name + "\n"; };
+    for (const char* p : {"x", "y", "z", "nx", "ny", "nz"}) prop(p);
+    if (with_sh) {
+        for (int k = 0; k < 3; ++k) prop("f_dc_" + std::to_string(k));
+        for (int k = 0; k < 45; ++k) prop("f_rest_" + std::to_string(k));
+    }
+    prop("opacity");
+    for (int k = 0; k < 3; ++k) prop("scale_" + std::to_string(k));
+    for (int k = 0; k < 4; ++k) prop("rot_" + std::to_string(k));
+    head += "end_header\n";
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return GSRT_E_IO;
+    bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
+    const size_t per = with_sh ? 62 : 14;
+    std::vector<float> buf(per * 4096);
+    for (uint64_t done = 0; done < n && ok;) {
+        const uint64_t chunk = std::min<uint64_t>(4096, n - done);
+        for (uint64_t r = 0; r < chunk; ++r) {
+            const uint64_t i = done + r;
+            float* p = buf.data() + r * per;
+            for (int k = 0; k < 3; ++k) *p++ = raw->center[3 * i + k];
+            for (int k = 0; k < 3; ++k) *p++ = 0.0f;
+            if (with_sh) {
+                const float* s = raw->sh + 48 * i;
+                for (int ch = 0; ch < 3; ++ch) *p++ = s[ch];
+                for (int ch = 0; ch < 3; ++ch)
+                    for (int j = 0; j < 15; ++j) *p++ = s[3 * (1 + j) + ch];
+            }
+            *p++ = raw->opacity[i];
+            for (int k = 0; k < 3; ++k) *p++ = raw->scale[3 * i + k];
+            for (int k = 0; k < 4; ++k) *p++ = raw->rot_rxyz[4 * i + k];
+        }
+        ok = std::fwrite(buf.data(), sizeof(float) * per, chunk, f) == chunk;
+        done += chunk;
+    }
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? GSRT_OK : GSRT_E_IO;
+}
+
 gsrt_status gsrt_scene_from_ply(gsrt_ctx* ctx, const char* path, int with_sh, gsrt_scene** out) {
     if (!ctx || !path || !out) return GSRT_E_ARG;
     uint32_t n = 0, deg = 0;

@@ -79,6 +79,10 @@ EXPORTS = [
     "gsrt_adam_scalars", "gsrt_model_step", "gsrt_model_step_async", "gsrt_model_activate", "gsrt_model_activate_async",
     "gsrt_model_deactivate", "gsrt_model_deactivate_async", "gsrt_model_opacity_reset", "gsrt_model_opacity_reset_async",
     "gsrt_pose_grad", "gsrt_pose_grad_async", "gsrt_pose_twist", "gsrt_ubo_apply_twist", "gsrt_debug_pose_grad_layout",
+    "gsrt_normal_noise", "gsrt_normal_noise_async", "gsrt_debug_philox", "gsrt_model_remap", "gsrt_model_remap_async",
+    "gsrt_ply_write", "gsrt_lr_expon", "gsrt_trainer_create", "gsrt_trainer_destroy", "gsrt_trainer_step",
+    "gsrt_trainer_densify", "gsrt_trainer_opacity_reset", "gsrt_trainer_rebuild_bvh", "gsrt_trainer_scene",
+    "gsrt_trainer_info", "gsrt_trainer_state", "gsrt_trainer_download",
 ]
 
 
@@ -231,6 +235,23 @@ def _load():
         "gsrt_pose_twist": ([P, P, P], i32),
         "gsrt_ubo_apply_twist": ([P, P], i32),
         "gsrt_debug_pose_grad_layout": ([P], i32),
+        "gsrt_normal_noise": ([P, ctypes.c_uint64, ctypes.c_uint64, u32, P], i32),
+        "gsrt_normal_noise_async": ([P, ctypes.c_uint64, ctypes.c_uint64, u32, P], i32),
+        "gsrt_debug_philox": ([ctypes.c_uint64, u32, ctypes.c_uint64, ctypes.c_uint64, P], i32),
+        "gsrt_model_remap": ([P, u32, P, P, P], i32),
+        "gsrt_model_remap_async": ([P, u32, P, P, P], i32),
+        "gsrt_ply_write": ([ctypes.c_char_p, u32, P], i32),
+        "gsrt_lr_expon": ([f32, f32, f32, u32, u32, u32, P], i32),
+        "gsrt_trainer_create": ([P, P, u32, u32, PP], i32),
+        "gsrt_trainer_destroy": ([P], None),
+        "gsrt_trainer_step": ([P, P, u32, P, u32, P, P, P, P, P], i32),
+        "gsrt_trainer_densify": ([P, P, ctypes.c_uint64, P], i32),
+        "gsrt_trainer_opacity_reset": ([P, f32], i32),
+        "gsrt_trainer_rebuild_bvh": ([P], i32),
+        "gsrt_trainer_scene": ([P, PP], i32),
+        "gsrt_trainer_info": ([P, P, P, P], i32),
+        "gsrt_trainer_state": ([P, P, P, P, P, PP], i32),
+        "gsrt_trainer_download": ([P, P, P], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -1678,3 +1699,191 @@ class Scene:
 
     def __del__(self):
         self.close()
+
+
+# ---------------------------------------------------------------- the training session
+
+def philox_words(seed, stream_id, first_block, blocks) -> np.ndarray:
+    """the raw words of normal_noise's generator (gsrt_debug_philox; no device): (blocks, 4) uint32, Philox4x32-10 with
+    the key (seed lo, seed hi) and the counters (j lo, j hi, stream_id, 0), j = first_block .. first_block + blocks - 1"""
+    out = np.zeros((blocks, 4), np.uint32)
+    _check(lib.gsrt_debug_philox(seed, stream_id, first_block, blocks, _p(out)))
+    return out
+
+
+def normal_noise(ctx, count, seed, stream_id=0, *, d_out=None, asynchronous=False):
+    """count standard normal draws (gsrt_normal_noise; the arithmetic is in gsrt.h): value i is a pure function of (seed,
+    stream_id, i). Returns a float32 array of count; with d_out, the device address of count floats, writes there and
+    returns None (asynchronous=True: enqueued on ctx.stream only)."""
+    if d_out is not None:
+        fn = lib.gsrt_normal_noise_async if asynchronous else lib.gsrt_normal_noise
+        _check(fn(ctx.handle, count, seed, stream_id, _addr(d_out)), ctx)
+        return None
+    out = np.zeros(count, np.float32)
+    _check(lib.gsrt_normal_noise(ctx.handle, count, seed, stream_id, _p(out)), ctx)
+    return out
+
+
+def model_remap(ctx, origin, arrays, *, n_out=None, feature_channels=0, out=None, asynchronous=False):
+    """The optimiser state across a densify (gsrt_model_remap): row i of every array of the result is row origin[i] of
+    `arrays` = (center, rot, scale, opacity, sh or None, features or None), or zeros where origin[i] < 0; the contract
+    of gsrt.autograd.remap_state for a whole model in one launch. numpy arrays: returns the new tuple. device addresses
+    (int): origin an address too, n_out, out = six addresses (and feature_channels) are needed; returns None."""
+    arrays = tuple(arrays) + (None,) * (6 - len(arrays))
+    if isinstance(arrays[0], int):
+        if n_out is None or out is None or not isinstance(origin, int):
+            raise GsrtError(E_ARG, "model_remap: device addresses need origin as an address, n_out and out")
+        s_in = ModelArrays(*[x or None for x in arrays], feature_channels)
+        s_out = ModelArrays(*[x or None for x in out], feature_channels)
+        fn = lib.gsrt_model_remap_async if asynchronous else lib.gsrt_model_remap
+        _check(fn(ctx.handle, n_out, _addr(origin), ctypes.byref(s_in), ctypes.byref(s_out)), ctx)
+        return None
+    org = np.ascontiguousarray(origin, dtype=np.int32).reshape(-1)
+    src = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+    n_in = src[0].shape[0]
+    if org.size and int(org.max()) >= n_in:
+        raise GsrtError(E_ARG, "model_remap: an origin entry is not a row of the arrays")
+    fc = 0 if src[5] is None else (src[5].shape[1] if src[5].ndim == 2 else 0)
+    k = org.size
+    res = [None if a is None else np.zeros((k,) + a.shape[1:], np.float32) for a in src]
+    s_in = ModelArrays(*[None if a is None else a.ctypes.data for a in src], fc)
+    s_out = ModelArrays(*[None if a is None else a.ctypes.data for a in res], fc)
+    _check(lib.gsrt_model_remap(ctx.handle, k, _p(org), ctypes.byref(s_in), ctypes.byref(s_out)), ctx)
+    return tuple(res)
+
+
+def ply_write(path, center, rot, log_scale, logit_opacity, sh=None):
+    """Write the raw model (unnormalised quaternion, log scale, logit: what model_deactivate returns and model_step
+    optimises) as a binary little-endian 3DGS .ply (gsrt_ply_write), every float as it is. sh: (n, 16, 3) / (n, 48) or
+    None (then no f_dc / f_rest properties are written)."""
+    center = _f32(center, (-1, 3))
+    n = center.shape[0]
+    rot, log_scale, logit_opacity = _f32(rot, (n, 4)), _f32(log_scale, (n, 3)), _f32(logit_opacity, (n,))
+    sh = None if sh is None else _f32(sh, (n, 48))
+    s_raw = ModelArrays(*[None if a is None else a.ctypes.data for a in (center, rot, log_scale, logit_opacity, sh)], None, 0)
+    _check(lib.gsrt_ply_write(os.fsencode(path), n, ctypes.byref(s_raw)))
+
+
+def lr_expon(lr_init, lr_final, step, max_steps, delay_mult=1.0, delay_steps=0) -> float:
+    """3DGS's get_expon_lr_func at `step` (gsrt_lr_expon; host only): log-linear from lr_init to lr_final over max_steps,
+    scaled by the delayed start when delay_steps > 0"""
+    out = ctypes.c_float(0.0)
+    _check(lib.gsrt_lr_expon(lr_init, lr_final, delay_mult, delay_steps, max_steps, step, ctypes.byref(out)))
+    return float(out.value)
+
+
+class _BorrowedScene(Scene):
+    """a scene owned by a Trainer: every Scene method works, close() only forgets the handle"""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.handle = handle
+
+    def close(self):
+        self.handle = None
+
+
+class Trainer:
+    """gsrt_trainer: a training run's state on the device (raw model, Adam moments, gradient tables, densification
+    statistics, scene and BVH, step counter) and its iterations. model = (center, rot, scale, opacity, sh or None), the
+    activated model as Scene.from_model takes it, numpy arrays or device addresses (then n is needed); capacity: the rows
+    everything is allocated for (default n)."""
+
+    def __init__(self, ctx: Context, model, capacity=None, *, n=None):
+        addr, n, fc, keep, dev = _model_set("Trainer: model", model, n, False)
+        if n is None:
+            raise GsrtError(E_ARG, "Trainer: device addresses need n")
+        s_model = ModelArrays(*addr, fc)
+        h = ctypes.c_void_p()
+        _check(lib.gsrt_trainer_create(ctx.handle, ctypes.byref(s_model), n, n if capacity is None else capacity,
+                                       ctypes.byref(h)), ctx)
+        self.ctx, self.handle, self.has_sh = ctx, h, addr[4] is not None
+        ctx._scenes.add(self)  # closed with the context, before it
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib.gsrt_trainer_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def info(self) -> dict:
+        n, cap, step = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib.gsrt_trainer_info(self.handle, ctypes.byref(n), ctypes.byref(cap), ctypes.byref(step)), self.ctx)
+        return dict(n=int(n.value), capacity=int(cap.value), step=int(step.value))
+
+    def step(self, ubo, target, adam, *, k=0, mask=None, target_depth=None, lam=0.2, params=None, target_channels=None,
+             want_scalars=True):
+        """One iteration against one view (gsrt_trainer_step). target: (H, W, 3) or (H, W, 4), mask / target_depth (H, W)
+        or None, numpy arrays or device addresses (then target_channels is needed). adam: an AdamParams whose step is
+        ignored. params: a FrameLossParams (default: frame_loss_params(lam)). Returns dict(loss=, l1=, ssim=, mse=,
+        depth_l1=, depth_samples=), or None with want_scalars=False."""
+        P = params if params is not None else frame_loss_params(lam)
+        keep = []
+        if isinstance(target, int):
+            if target_channels is None:
+                raise GsrtError(E_ARG, "Trainer.step: a device target needs target_channels")
+            args = [_addr(target), target_channels, _addr(mask), _addr(target_depth)]
+        else:
+            y = np.ascontiguousarray(target, dtype=np.float32)
+            h, w = int(ubo["height"][0]), int(ubo["width"][0])
+            if y.ndim != 3 or y.shape[:2] != (h, w):
+                raise GsrtError(E_ARG, "Trainer.step: target is an (H, W, 3) or (H, W, 4) array of the ubo's frame")
+            planes = [a if a is None or isinstance(a, int) else _f32(a, (h, w)) for a in (mask, target_depth)]
+            keep += [y] + planes
+            args = [_p(y), y.shape[2] if target_channels is None else target_channels, _addr(planes[0]), _addr(planes[1])]
+        out = np.zeros(FRAME_LOSS_SCALARS, np.float32) if want_scalars else None
+        _check(lib.gsrt_trainer_step(self.handle, _p(ubo), k, args[0], args[1], args[2], args[3], ctypes.byref(P),
+                                     ctypes.byref(adam), _p(out)), self.ctx)
+        if out is None:
+            return None
+        return dict(zip(("loss", "l1", "ssim", "mse", "depth_l1", "depth_samples"), (float(v) for v in out)))
+
+    def densify(self, params, seed=0) -> int:
+        """clone, split and prune with the statistics gathered since the last densify (gsrt_trainer_densify); returns the
+        new n. GsrtError(E_ARG) with nothing changed when the new model exceeds the capacity. Scenes obtained from scene()
+        earlier are dead after it."""
+        got = ctypes.c_uint32(0)
+        _check(lib.gsrt_trainer_densify(self.handle, ctypes.byref(params), seed, ctypes.byref(got)), self.ctx)
+        return int(got.value)
+
+    def opacity_reset(self, max_opacity=0.01):
+        _check(lib.gsrt_trainer_opacity_reset(self.handle, max_opacity), self.ctx)
+
+    def rebuild_bvh(self):
+        _check(lib.gsrt_trainer_rebuild_bvh(self.handle), self.ctx)
+
+    def scene(self) -> Scene:
+        """the trainer's scene, borrowed (evaluation views); dead after the next densify()"""
+        h = ctypes.c_void_p()
+        _check(lib.gsrt_trainer_scene(self.handle, ctypes.byref(h)), self.ctx)
+        return _BorrowedScene(self.ctx, h)
+
+    def state(self) -> dict:
+        """device addresses (gsrt_trainer_state), borrowed until the next densify(): raw, m, v as (center, rot, scale,
+        opacity, sh or None), grads as (center, cov, splat, sh or None), stats"""
+        raw, m, v, g = ModelArrays(), ModelArrays(), ModelArrays(), ModelGrads()
+        st = ctypes.c_void_p()
+        _check(lib.gsrt_trainer_state(self.handle, ctypes.byref(raw), ctypes.byref(m), ctypes.byref(v), ctypes.byref(g),
+                                      ctypes.byref(st)), self.ctx)
+        five = lambda a: (a.center, a.rot_rxyz, a.scale, a.opacity, a.sh)  # noqa: E731
+        return dict(raw=five(raw), m=five(m), v=five(v), grads=(g.center, g.cov, g.splat, g.sh), stats=st.value)
+
+    def download(self, act=True):
+        """(raw, act): the raw model and, with act, its activation, each (center (n, 3), rot (n, 4), scale (n, 3), opacity
+        (n,), sh (n, 48) or None) as numpy arrays (gsrt_trainer_download)"""
+        n = self.info()["n"]
+        new = lambda: _new_model(n, [1, 1, 1, 1, 1 if self.has_sh else None, None], 0)[:5]  # noqa: E731
+        raw, a = new(), (new() if act else None)
+        s = lambda o: ModelArrays(*[None if x is None else x.ctypes.data for x in o], None, 0)  # noqa: E731
+        s_raw, s_act = s(raw), (s(a) if act else None)
+        _check(lib.gsrt_trainer_download(self.handle, ctypes.byref(s_raw), None if s_act is None else ctypes.byref(s_act)),
+               self.ctx)
+        return tuple(raw), (tuple(a) if act else None)

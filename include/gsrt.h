@@ -160,6 +160,14 @@ gsrt_status gsrt_scene_set_sh(gsrt_scene* scene, const float* sh);
 gsrt_status gsrt_ply_info(const char* path, uint32_t* n, uint32_t* sh_degree);
 gsrt_status gsrt_ply_read(const char* path, float* center, float* rot_rxyz, float* scale, float* opacity, float* sh);
 gsrt_status gsrt_scene_from_ply(gsrt_ctx* ctx, const char* path, int with_sh, gsrt_scene** out);
+/* The writer: a binary little-endian 3DGS .ply of the raw model (gsrt_model_arrays below, host pointers: unnormalised
+ * quaternion, log scale, logit; what gsrt_model_deactivate gives and gsrt_model_step optimises), every value written as
+ * the float32 it is: nothing is recomputed. Properties, in 3DGS's order: x y z nx ny nz f_dc_0..2 f_rest_0..44 opacity
+ * scale_0..2 rot_0..3; the normals are 0, f_rest is channel-major (f_rest_(15 ch + j) = sh[1 + j][ch], the inverse of
+ * the reader's permutation). raw->sh == NULL writes no f_dc and no f_rest properties. n may be 0.
+ * GSRT_E_ARG: a NULL path, raw or required array (n > 0); a model with features. GSRT_E_IO: the file cannot be written. */
+struct gsrt_model_arrays;
+gsrt_status gsrt_ply_write(const char* path, uint32_t n, const struct gsrt_model_arrays* raw);
 
 /* ---- triangle meshes co-traced with the Gaussians ---------------------- */
 /* Scene 33 holds a triangle-mesh sphere beside its two Gaussians (SceneList.cpp:123, Model::CreateSphere,
@@ -501,9 +509,9 @@ gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* scene, const gsrt_u
 /* ---- adaptive density control: clone, split and prune a model on the device ----------------------
  * The model is the gsrt_scene_from_model arrays; the calls below work on arrays, not on a scene: a scene's size is fixed,
  * so after gsrt_densify the caller creates a new scene from the new arrays (gsrt_scene_from_model takes device pointers)
- * and builds its BVH. The library has no random numbers: a split's samples come from the caller's noise, so a result is
- * a pure function of its inputs. Not provided: screen-radius pruning, resizing a scene in place (an opacity reset:
- * gsrt_model_opacity_reset below). */
+ * and builds its BVH. A split's samples come from the caller's noise, so a result is a pure function of its inputs;
+ * gsrt_normal_noise (below) draws such noise on the device from a seed. Not provided: screen-radius pruning, resizing a
+ * scene in place (an opacity reset: gsrt_model_opacity_reset below). */
 typedef struct gsrt_model_arrays {   /* the gsrt_scene_from_model convention */
     float* center;    /* n x 3 */
     float* rot_rxyz;  /* n x 4, used as given */
@@ -587,6 +595,31 @@ gsrt_status gsrt_densify(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n,
 gsrt_status gsrt_densify_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* d_stats,
                                const float* d_noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
                                int32_t* d_origin, uint32_t cap, uint32_t* d_n_out);
+/* Counter-based standard normal noise, e.g. gsrt_densify's: out[i], i < count, is a pure function of (seed, stream_id, i).
+ * It does not depend on count or on how the work is laid out: a prefix of a longer call is the shorter call bit for bit.
+ * The generator is Philox4x32-10 (Salmon et al. 2011, as Random123 states it) with the key (seed lo, seed hi); block j has
+ * the counter (j lo, j hi, stream_id, 0), and its four output words x0..x3 give out[4j .. 4j + 3] as two Box-Muller pairs,
+ * (x0, x1) -> out[4j], out[4j + 1] and (x2, x3) -> out[4j + 2], out[4j + 3]. Per pair (xa, xb), in float32, every operation
+ * rounded on its own:
+ *     ua = ((float)(xa >> 8) + 0.5f) * 2^-24,   ub = ((float)(xb >> 8) + 0.5f) * 2^-24        (both in (0, 1])
+ *     r  = sqrtf(-2.0f * logf(ua)),   th = 6.2831855f * ub,   z0 = r * cosf(th),   z1 = r * sinf(th)
+ * with the device's logf, cosf and sinf (accurate to a few ulp; |z| < 5.9). A count that is no multiple of 4 drops the
+ * tail of the last block. out is a host or a device pointer (4-byte aligned; whole 16-byte stores are used where it is
+ * 16-byte aligned); the call runs on gsrt_stream() and blocks until out is complete. count == 0 writes nothing.
+ * GSRT_E_ARG: a NULL ctx, or a NULL or misaligned out with count > 0. */
+gsrt_status gsrt_normal_noise(gsrt_ctx* ctx, uint64_t count, uint64_t seed, uint32_t stream_id, float* out);
+/* the same, enqueued on gsrt_stream(); a device pointer only */
+gsrt_status gsrt_normal_noise_async(gsrt_ctx* ctx, uint64_t count, uint64_t seed, uint32_t stream_id, float* d_out);
+/* The optimiser state across a gsrt_densify: row i, i < n_out, of every present array of `out` is row origin[i] of `in`,
+ * bit for bit, where origin[i] >= 0, and +0 in every word where origin[i] < 0 (a newly made Gaussian starts with fresh
+ * moments): one gather over a whole gsrt_model_arrays (the layout the moments m and v of gsrt_model_step have). origin is
+ * gsrt_densify's; an entry >= 0 must be a row of `in`, whose length the call is not told. Pointer and presence rules and
+ * refusals as for gsrt_model_deactivate with `in` the input and `out` the output, except that no array of `out` may
+ * overlap one of `in` (the gather is not in place); origin lives on the side, host or device, of the arrays. */
+gsrt_status gsrt_model_remap(gsrt_ctx* ctx, uint32_t n_out, const int32_t* origin, const gsrt_model_arrays* in,
+                             const gsrt_model_arrays* out);
+gsrt_status gsrt_model_remap_async(gsrt_ctx* ctx, uint32_t n_out, const int32_t* d_origin, const gsrt_model_arrays* in,
+                                   const gsrt_model_arrays* out);
 
 /* ---- photometric loss: L1 + D-SSIM of a frame against a target image, with its gradient ---------
  * The loss of 3DGS's training step in one fused call: rgba is a frame as the renderer leaves it (float[H][W][4], used as
@@ -714,7 +747,7 @@ gsrt_status gsrt_frame_loss_async(gsrt_ctx* ctx, uint32_t width, uint32_t height
  * (lr_sh_rest), features. A group whose lr is exactly 0 is frozen: its raw, m and v words keep their bits. With
  * GSRT_ADAM_SPARSE a Gaussian that was not seen keeps every raw, m and v word bit for bit (3DGS's sparse Adam); "seen" is
  * gsrt_density_stats_add's: any of its splat row's slots 0..5 != 0.0f. Without the flag every Gaussian is stepped.
- * Not provided: other optimisers, learning-rate schedules (change lr_* per call), weight decay. */
+ * Not provided: other optimisers, learning-rate schedules beside gsrt_lr_expon (change lr_* per call), weight decay. */
 #define GSRT_ADAM_SPARSE 1u
 typedef struct gsrt_adam_params {
     float lr_center, lr_rot, lr_scale, lr_opacity, lr_sh_dc, lr_sh_rest, lr_features;
@@ -787,6 +820,79 @@ gsrt_status gsrt_model_opacity_reset(gsrt_ctx* ctx, uint32_t n, float* logit_opa
                                      float max_opacity);
 gsrt_status gsrt_model_opacity_reset_async(gsrt_ctx* ctx, uint32_t n, float* d_logit_opacity, float* d_m_opacity,
                                            float* d_v_opacity, float max_opacity);
+
+/* 3DGS's get_expon_lr_func, host only (no ctx, no device): the log-linear decay from lr_init at step 0 to lr_final at
+ * max_steps with the delayed start, computed in double and rounded to float once. With t = clamp(step / max_steps, 0, 1):
+ *     lr = delay * exp(log(lr_init) (1 - t) + log(lr_final) t),
+ *     delay = delay_steps > 0 ? delay_mult + (1 - delay_mult) sin(pi / 2 * clamp(step / delay_steps, 0, 1)) : 1,
+ * and lr = 0 when lr_init and lr_final are both 0. GSRT_E_ARG: a NULL lr; max_steps == 0; a negative or NaN rate, or
+ * exactly one of lr_init and lr_final zero; a NaN delay_mult. */
+gsrt_status gsrt_lr_expon(float lr_init, float lr_final, float delay_mult, uint32_t delay_steps, uint32_t max_steps,
+                          uint32_t step, float* lr);
+
+/* ---- the training session: one object that owns a run's state on the device ------------------------
+ * gsrt_trainer holds what a 3DGS training run carries from iteration to iteration, all of it in HBM: the raw model, both
+ * Adam moment sets, the gradient tables, the densification statistics, the scene with its BVH, and the step counter. Its
+ * calls are the sequences the entry points above compose to, with the stream ordering their comments ask for applied once,
+ * here. Everything is allocated for `capacity` rows at creation (two sets of raw, m and v for the out-of-place densify,
+ * the tables, noise, origin, stats, the scene arrays of a step); only the frame-sized buffers are regrown, when the frame
+ * size changes. One trainer per ctx at a time is the tested use; calls on one trainer are serialised by the caller, like
+ * every call on its ctx.
+ * gsrt_trainer_create: model is the activated model (gsrt_scene_from_model's convention; host or device pointers, all on
+ * one side), n of `capacity` rows used. The raw model is gsrt_model_deactivate of it, the moments and statistics are +0,
+ * the scene is gsrt_scene_from_model of the model as given, with its BVH built. GSRT_E_ARG: a NULL pointer; a model with
+ * features; n == 0; capacity < n; capacity > GSRT_MAX_GAUSSIANS.
+ * gsrt_trainer_step: one iteration against one view. In order, all on gsrt_stream(): a COR frame of ubo with k
+ * (gsrt_render_async; with target_depth a depth frame, gsrt_render_depth_async); gsrt_frame_loss_async of it against
+ * target (width x height x target_channels), mask (nullable) and target_depth (nullable) with params: with no option set
+ * its first four scalars and its gradient are gsrt_image_loss's; gsrt_render_splat_grad_async (with target_depth
+ * gsrt_render_splat_depth_grad_async); gsrt_density_stats_add_async into the trainer's statistics; the matching
+ * gsrt_splat*_grad_to_model_async; for a model with SH gsrt_render_sh_grad_async; gsrt_model_step_async with adam, whose
+ * .step is ignored: the step number is the trainer's counter + 1. Then gsrt_synchronize, gsrt_scene_update with the
+ * step's scene arrays, gsrt_refit_bvh(scene, NULL) and, with SH, gsrt_scene_set_sh, so that the next frame of the scene is
+ * the stepped model's; the counter advances. scalars (host, nullable) receives gsrt_frame_loss's six. A step synchronises
+ * with the host once in gsrt_synchronize (the scalars are read behind it) and once where gsrt_scene_set_sh drains the
+ * queued frames. target, mask and target_depth are all host pointers or all device pointers; host ones are copied into
+ * buffers of the trainer's. What gsrt_frame_loss, gsrt_adam_scalars or one of the frames would refuse is refused before
+ * anything is enqueued, with the trainer, its counter included, as it was (GSRT_E_ARG; gsrt_last_error of the ctx says
+ * why): NULL ubo, target, params or adam; a bad frame size or samples == 0; target_channels not 3 or 4; bad loss or Adam
+ * parameters; mixed pointers; a misaligned 4-channel device target; a scene that was given a triangle mesh.
+ * gsrt_trainer_densify: noise = gsrt_normal_noise(6 n, seed, stream_id = the step counter); gsrt_model_activate of the raw
+ * model; gsrt_densify_async with params and the trainer's statistics into the second buffer set; n_out is read back (one
+ * uint32) and written to *n_out (nullable). When it exceeds the capacity: GSRT_E_ARG with nothing changed (model, moments,
+ * statistics, scene, n). Otherwise gsrt_model_deactivate of the new model, gsrt_model_remap of m and of v by the pass's
+ * origin, the statistics set to +0, a new scene with a new BVH created from the new model, and the old scene destroyed:
+ * A SCENE HANDLE OBTAINED FROM gsrt_trainer_scene BEFORE THIS CALL IS DEAD AFTER IT. A densify that prunes every
+ * Gaussian (n_out == 0) is refused the same way.
+ * gsrt_trainer_opacity_reset: gsrt_model_opacity_reset on the raw model and the moments, then the scene's arrays from
+ * gsrt_model_activate, so that the next frame shows it.
+ * gsrt_trainer_rebuild_bvh: gsrt_build_bvh of the scene, for callers whose Gaussians have moved far; a step only refits
+ * (the topology is kept), and the trainer never rebuilds on its own.
+ * gsrt_trainer_scene: the trainer's scene, borrowed, for evaluation views (gsrt_render, gsrt_pose_grad, ...); not to be
+ * destroyed, updated or given a mesh or features by the caller. gsrt_trainer_info: n, capacity and the step counter (each
+ * nullable). gsrt_trainer_state: the device addresses, borrowed and valid until the next gsrt_trainer_densify or
+ * gsrt_trainer_destroy, of the raw model, the moments, the gradient tables of the last step and the statistics (n x 2);
+ * each nullable. gsrt_trainer_download: after draining the ctx, the raw model into raw_out and / or its activation
+ * (gsrt_model_activate) into act_out: host arrays of n rows, sh NULL exactly when the model has none; either may be NULL.
+ * Every call returns GSRT_E_ARG for a NULL trainer.
+ * Not provided: features in a trainer; SH degree ramp-up; screen-radius pruning; batched views; sharded frames; pose
+ * refinement inside the trainer (gsrt_pose_grad remains callable on the borrowed scene); HIP graph capture of the step. */
+typedef struct gsrt_trainer gsrt_trainer;
+gsrt_status gsrt_trainer_create(gsrt_ctx* ctx, const gsrt_model_arrays* model, uint32_t n, uint32_t capacity,
+                                gsrt_trainer** out);
+void gsrt_trainer_destroy(gsrt_trainer* trainer);
+gsrt_status gsrt_trainer_step(gsrt_trainer* trainer, const gsrt_ubo* ubo, uint32_t k, const float* target,
+                              uint32_t target_channels, const float* mask, const float* target_depth,
+                              const gsrt_frame_loss_params* params, const gsrt_adam_params* adam,
+                              float scalars[GSRT_FRAME_LOSS_SCALARS]);
+gsrt_status gsrt_trainer_densify(gsrt_trainer* trainer, const gsrt_densify_params* params, uint64_t seed, uint32_t* n_out);
+gsrt_status gsrt_trainer_opacity_reset(gsrt_trainer* trainer, float max_opacity);
+gsrt_status gsrt_trainer_rebuild_bvh(gsrt_trainer* trainer);
+gsrt_status gsrt_trainer_scene(gsrt_trainer* trainer, gsrt_scene** scene);
+gsrt_status gsrt_trainer_info(const gsrt_trainer* trainer, uint32_t* n, uint32_t* capacity, uint32_t* step);
+gsrt_status gsrt_trainer_state(gsrt_trainer* trainer, gsrt_model_arrays* raw, gsrt_model_arrays* m, gsrt_model_arrays* v,
+                               gsrt_model_grads* grads, const float** stats);
+gsrt_status gsrt_trainer_download(gsrt_trainer* trainer, const gsrt_model_arrays* raw_out, const gsrt_model_arrays* act_out);
 
 /* ---- camera pose gradients: the backward of a frame to the model-view matrix -----------------------
  * The training loop above takes the cameras as known. For pose refinement and tracking (noisy COLMAP poses, SLAM,

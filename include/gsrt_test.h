@@ -104,6 +104,11 @@ gsrt_status gsrt_render_sharded_emulated_dump8(gsrt_scene* scene, const gsrt_ubo
  * sums into one partial, the lanes of the second kernel's one workgroup}, so that tests can place n at the seams */
 gsrt_status gsrt_debug_pose_grad_layout(uint32_t out[2]);
 
+/* the raw words of gsrt_normal_noise's generator (host only, no device): Philox4x32-10 with the key (seed lo, seed hi),
+ * blocks first_block .. first_block + blocks - 1 with the counter (j lo, j hi, stream_id, 0); out receives 4 * blocks
+ * words, block after block */
+gsrt_status gsrt_debug_philox(uint64_t seed, uint32_t stream_id, uint64_t first_block, uint64_t blocks, uint32_t* out);
+
 /* ---- synthetic inputs (std::mt19937(seed) + uniform_real_distribution<float>) ---- */
 gsrt_status gsrt_synth_cloud(uint32_t kind, uint32_t n, uint32_t seed, int with_sh, float* center,
                              float* rot_rxyz, float* scale, float* opacity, float* sh);
