@@ -18,28 +18,12 @@
 #include <vector>
 
 #include "../../include/gsrt_test.h"
-#include "gsrt_internal.hpp"
+#include "gsrt_api_util.hpp"
 
 using gsrt::fail;
-
-namespace {
-
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
-constexpr uint32_t kFieldFloats[5] = {3, 4, 3, 1, 48};  // centre, rot, scale, opacity, sh
-float* gsrt_model_arrays::*const kFields[5] = {&gsrt_model_arrays::center, &gsrt_model_arrays::rot_rxyz,
-                                               &gsrt_model_arrays::scale, &gsrt_model_arrays::opacity,
-                                               &gsrt_model_arrays::sh};
-
-}  // namespace
+using gsrt::is_device_ptr;
+using gsrt::model_fields;
+using gsrt::ModelField;
 
 struct gsrt_trainer {
     gsrt_ctx* ctx = nullptr;
@@ -75,11 +59,12 @@ bool dev_alloc(gsrt_trainer* t, T** p, size_t count) {
     return true;
 }
 
-bool alloc_set(gsrt_trainer* t, gsrt_model_arrays& a, bool with_sh) {
-    for (int f = 0; f < 5; ++f) {
-        if (f == 4 && !with_sh) continue;
-        if (!dev_alloc(t, &(a.*kFields[f]), (size_t)kFieldFloats[f] * t->cap)) return false;
-    }
+// the arrays that `like` has, for the trainer's capacity
+bool alloc_set(gsrt_trainer* t, gsrt_model_arrays& a, const gsrt_model_arrays& like) {
+    ModelField f[6];
+    const uint32_t nf = model_fields(like, f);
+    for (uint32_t i = 0; i < nf; ++i)
+        if (!dev_alloc(t, &(a.*f[i].member), (size_t)f[i].floats * t->cap)) return false;
     return true;
 }
 
@@ -177,9 +162,11 @@ gsrt_status gsrt_trainer_create(gsrt_ctx* ctx, const gsrt_model_arrays* model, u
     if (n == 0 || capacity < n || capacity > GSRT_MAX_GAUSSIANS)
         return fail(ctx, GSRT_E_ARG, name + "needs 1 <= n <= capacity <= GSRT_MAX_GAUSSIANS");
     if (!model->center || !model->rot_rxyz || !model->scale || !model->opacity) return fail(ctx, GSRT_E_ARG, name + "a NULL array");
-    const bool dev = on_device(model->center);
-    for (int f = 1; f < 5; ++f)
-        if (model->*kFields[f] && on_device(model->*kFields[f]) != dev)
+    ModelField mf[6];
+    const uint32_t nf = model_fields(*model, mf);  // sh only when the model has it
+    const bool dev = is_device_ptr(model->center);
+    for (uint32_t f = 1; f < nf; ++f)
+        if (is_device_ptr(model->*mf[f].member) != dev)
             return fail(ctx, GSRT_E_ARG, name + "the arrays must all be host pointers or all be device pointers");
     (void)hipSetDevice(ctx->device);
     gsrt_trainer* t = new (std::nothrow) gsrt_trainer;
@@ -190,9 +177,11 @@ gsrt_status gsrt_trainer_create(gsrt_ctx* ctx, const gsrt_model_arrays* model, u
     t->has_sh = model->sh != nullptr;
     const size_t cap = capacity;
     bool ok = true;
+    gsrt_model_arrays no_sh = *model;  // an activated set's SH rows are a raw set's
+    no_sh.sh = nullptr;
     for (int i = 0; i < 2 && ok; ++i)
-        ok = alloc_set(t, t->raw[i], t->has_sh) && alloc_set(t, t->m[i], t->has_sh) && alloc_set(t, t->v[i], t->has_sh) &&
-             alloc_set(t, t->act[i], false);
+        ok = alloc_set(t, t->raw[i], *model) && alloc_set(t, t->m[i], *model) && alloc_set(t, t->v[i], *model) &&
+             alloc_set(t, t->act[i], no_sh);
     ok = ok && dev_alloc(t, &t->g_center, 3 * cap) && dev_alloc(t, &t->g_cov, 6 * cap) && dev_alloc(t, &t->g_splat, 8 * cap) &&
          (!t->has_sh || dev_alloc(t, &t->g_sh, 48 * cap)) && dev_alloc(t, &t->stats, 2 * cap) &&
          dev_alloc(t, &t->noise, 6 * cap) && dev_alloc(t, &t->scalars, 8) && dev_alloc(t, &t->origin, cap) &&
@@ -208,14 +197,12 @@ gsrt_status gsrt_trainer_create(gsrt_ctx* ctx, const gsrt_model_arrays* model, u
     };
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     gsrt_model_arrays a0 = with_sh_of(t->act[0], t->raw[0]);
-    for (int f = 0; f < 5; ++f)
-        if (f < 4 || t->has_sh)
-            hip(hipMemcpyAsync(a0.*kFields[f], model->*kFields[f], sizeof(float) * kFieldFloats[f] * n, kind, st), "upload");
+    for (uint32_t f = 0; f < nf; ++f)
+        hip(hipMemcpyAsync(a0.*mf[f].member, model->*mf[f].member, sizeof(float) * mf[f].floats * n, kind, st), "upload");
     for (int i = 0; i < 2; ++i)
         for (gsrt_model_arrays* set : {&t->m[i], &t->v[i]})
-            for (int f = 0; f < 5; ++f)
-                if (f < 4 || t->has_sh)
-                    hip(hipMemsetAsync(set->*kFields[f], 0, sizeof(float) * kFieldFloats[f] * cap, st), "memset");
+            for (uint32_t f = 0; f < nf; ++f)
+                hip(hipMemsetAsync(set->*mf[f].member, 0, sizeof(float) * mf[f].floats * cap, st), "memset");
     hip(hipMemsetAsync(t->stats, 0, sizeof(float) * 2 * cap, st), "memset");
     if (s == GSRT_OK) s = gsrt_model_deactivate_async(ctx, n, &a0, &t->raw[0]);
     if (s == GSRT_OK) s = gsrt_synchronize(ctx);  // gsrt_scene_from_model reads a device source at the call
@@ -242,28 +229,22 @@ gsrt_status gsrt_trainer_step(gsrt_trainer* t, const gsrt_ubo* ubo, uint32_t k, 
     const uint32_t W = ubo->width, H = ubo->height;
     if (W == 0 || H == 0 || W > 32768 || H > 32768) return fail(ctx, GSRT_E_ARG, name + "bad frame size");
     if (target_channels != 3 && target_channels != 4) return fail(ctx, GSRT_E_ARG, name + "target_channels must be 3 or 4");
-    if (!(P->lambda >= 0.0f && P->lambda <= 1.0f)) return fail(ctx, GSRT_E_ARG, name + "params.lambda must be in [0, 1]");
-    if (P->flags & ~GSRT_LOSS_BACKGROUND) return fail(ctx, GSRT_E_ARG, name + "an unknown flag in params.flags");
-    if (P->reserved) return fail(ctx, GSRT_E_ARG, name + "params.reserved must be zero");
-    if (P->flags & GSRT_LOSS_BACKGROUND)
-        for (float b : P->background)
-            if (!std::isfinite(b)) return fail(ctx, GSRT_E_ARG, name + "params.background must be finite");
-    if (!(P->depth_weight >= 0.0f)) return fail(ctx, GSRT_E_ARG, name + "params.depth_weight is negative or NaN");
-    if (!(P->alpha_min > 0.0f && P->alpha_min <= 1.0f)) return fail(ctx, GSRT_E_ARG, name + "params.alpha_min must be in (0, 1]");
+    gsrt_status s = gsrt::check_frame_loss_params(ctx, name, *P);
+    if (s != GSRT_OK) return s;
     gsrt_adam_params A = *adam;
     A.step = t->step + 1;  // the trainer counts
     float ks[GSRT_ADAM_SCALARS];
     if (A.step == 0 || gsrt_adam_scalars(&A, ks) != GSRT_OK) return fail(ctx, GSRT_E_ARG, name + "bad Adam parameters");
-    const bool dev = on_device(target);
+    const bool dev = is_device_ptr(target);
     for (const float* p : {mask, target_depth})
-        if (p && on_device(p) != dev)
+        if (p && is_device_ptr(p) != dev)
             return fail(ctx, GSRT_E_ARG, name + "target, mask and target_depth must all be host pointers or all be device pointers");
     if (dev && target_channels == 4 && reinterpret_cast<uintptr_t>(target) % 16u)
         return fail(ctx, GSRT_E_ARG, name + "a 4-channel device target must be 16-byte aligned");
     const bool with_depth = target_depth != nullptr;
     const uint32_t fwd = GSRT_MODE_COR | (with_depth ? GSRT_FLAG_DEPTH : 0u);
     const uint32_t bwd = GSRT_MODE_COR | (with_depth ? GSRT_FLAG_SPLAT_DEPTH_GRAD : GSRT_FLAG_SPLAT_GRAD);
-    gsrt_status s = frame_ok(t, fwd, 0, ubo->samples);
+    s = frame_ok(t, fwd, 0, ubo->samples);
     if (s == GSRT_OK) s = frame_ok(t, bwd, with_depth ? 5u : 4u, ubo->samples);
     if (s == GSRT_OK && t->has_sh) s = frame_ok(t, GSRT_MODE_COR | GSRT_FLAG_SH_GRAD, 2, ubo->samples);
     if (s != GSRT_OK) return s;
@@ -418,8 +399,10 @@ gsrt_status gsrt_trainer_download(gsrt_trainer* t, const gsrt_model_arrays* raw_
         if (o->features || o->feature_channels) return fail(ctx, GSRT_E_ARG, name + "a trainer's model has no features");
         if (!o->center || !o->rot_rxyz || !o->scale || !o->opacity) return fail(ctx, GSRT_E_ARG, name + "a NULL array");
         if ((o->sh != nullptr) != t->has_sh) return fail(ctx, GSRT_E_ARG, name + "sh is NULL exactly when the model has none");
-        for (int f = 0; f < 5; ++f)
-            if (o->*kFields[f] && on_device(o->*kFields[f])) return fail(ctx, GSRT_E_ARG, name + "the outputs are host arrays");
+        ModelField mf[6];
+        const uint32_t nf = model_fields(*o, mf);
+        for (uint32_t f = 0; f < nf; ++f)
+            if (is_device_ptr(o->*mf[f].member)) return fail(ctx, GSRT_E_ARG, name + "the outputs are host arrays");
     }
     (void)hipSetDevice(ctx->device);
     gsrt_status s = gsrt_synchronize(ctx);
@@ -429,10 +412,11 @@ gsrt_status gsrt_trainer_download(gsrt_trainer* t, const gsrt_model_arrays* raw_
         if (s == GSRT_OK) s = gsrt_synchronize(ctx);
     }
     const auto copy = [&](const gsrt_model_arrays* dst, const gsrt_model_arrays& src) {
-        for (int f = 0; f < 5 && dst; ++f)
-            if ((f < 4 || t->has_sh) && s == GSRT_OK &&
-                hipMemcpy(dst->*kFields[f], src.*kFields[f], sizeof(float) * kFieldFloats[f] * t->n, hipMemcpyDeviceToHost) !=
-                    hipSuccess)
+        ModelField mf[6];
+        const uint32_t nf = model_fields(src, mf);
+        for (uint32_t f = 0; f < nf && dst; ++f)
+            if (s == GSRT_OK && hipMemcpy(dst->*mf[f].member, src.*mf[f].member, sizeof(float) * mf[f].floats * t->n,
+                                          hipMemcpyDeviceToHost) != hipSuccess)
                 s = fail(ctx, GSRT_E_DEVICE, name + "download failed");
     };
     copy(raw_out, t->raw[t->cur]);
