@@ -4,7 +4,7 @@
 //   gsrt_train --ply IN.ply --views LIST --width W --height H --fovy F --iters N --out OUT.ply
 //              [--samples S] [--lambda L] [--densify-every D] [--densify-from A] [--densify-until U]
 //              [--opacity-reset-every R] [--grad-threshold T] [--split-scale X] [--min-opacity O] [--capacity C]
-//              [--seed S] [--device D]
+//              [--sh-degree-every N] [--max-screen-radius R] [--seed S] [--device D]
 //
 // LIST holds one "camera_file target.bin" per line: the camera file is gsrt_camera_from_file's (eye and centre, six
 // floats), target.bin is H*W*3 float32, the format gsrt_render's --loss-target reads. Views are taken round-robin. Every
@@ -13,6 +13,9 @@
 // rates are 3DGS's defaults, and so are the densification numbers (every 100 iterations from 500 until 15000 at a
 // view-space gradient of 0.0002, a prune below opacity 0.005, an opacity reset to 0.01 every 3000). A densify pass is off
 // unless --densify-every is given. --split-scale is 3DGS's percent_dense times the scene extent, which the caller knows.
+// --sh-degree-every N: 3DGS's ramp-up, the active SH degree of iteration i (from 1) is i / N, up to 3 or the .ply's (3DGS:
+// 1000); 0, the default, keeps degree 3 throughout. --max-screen-radius R: the screen-size prune of a densify pass after
+// the first opacity reset, in pixels (3DGS: 20); 0, the default, is off.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,7 +34,9 @@ namespace {
                  "usage: gsrt_train --ply IN.ply --views LIST --width W --height H --fovy F --iters N --out OUT.ply\n"
                  "                  [--samples S] [--lambda L] [--densify-every D] [--densify-from A] [--densify-until U]\n"
                  "                  [--opacity-reset-every R] [--grad-threshold T] [--split-scale X] [--min-opacity O]\n"
-                 "                  [--capacity C] [--seed S] [--device D]\n");
+                 "                  [--capacity C] [--sh-degree-every N] [--max-screen-radius R] [--seed S] [--device D]\n"
+                 "  --sh-degree-every N    raise the active SH degree from 0 by one every N iterations (0: degree 3 throughout)\n"
+                 "  --max-screen-radius R  after the first opacity reset a densify prunes screen radii above R pixels (0: off)\n");
     std::exit(2);
 }
 
@@ -52,8 +57,9 @@ float to_f32(const char* s, const std::string& flag) {
 struct Options {
     std::string ply, views, out;
     uint32_t width = 0, height = 0, iters = 0, samples = 1, device = 0, capacity = 0;
-    uint32_t densify_every = 0, densify_from = 500, densify_until = 15000, reset_every = 0;
+    uint32_t densify_every = 0, densify_from = 500, densify_until = 15000, reset_every = 0, sh_degree_every = 0;
     float fovy = 0.0f, lambda = 0.2f, grad_threshold = 0.0002f, split_scale = 0.01f, min_opacity = 0.005f;
+    float max_screen_radius = 0.0f;
     uint64_t seed = 0;
 };
 
@@ -94,6 +100,8 @@ int main(int argc, char** argv) {
         else if (a == "--split-scale") o.split_scale = to_f32(val(), a);
         else if (a == "--min-opacity") o.min_opacity = to_f32(val(), a);
         else if (a == "--capacity") o.capacity = to_u32(val(), a);
+        else if (a == "--sh-degree-every") o.sh_degree_every = to_u32(val(), a);
+        else if (a == "--max-screen-radius") o.max_screen_radius = to_f32(val(), a);
         else if (a == "--seed") o.seed = std::strtoull(val(), nullptr, 10);
         else if (a == "--device") o.device = to_u32(val(), a);
         else if (a == "--help" || a == "-h") usage(nullptr);
@@ -105,6 +113,7 @@ int main(int argc, char** argv) {
     if (!o.iters) usage("--iters must be at least 1");
     if (!o.samples) usage("--samples must be at least 1");
     if (!(o.lambda >= 0.0f && o.lambda <= 1.0f)) usage("--lambda must be in [0, 1]");
+    if (!(o.max_screen_radius >= 0.0f)) usage("--max-screen-radius must be >= 0");
 
     // the model: the reader's activated arrays; the trainer makes them raw
     uint32_t n = 0, degree = 0;
@@ -161,8 +170,14 @@ int main(int argc, char** argv) {
     dens.grad_threshold = o.grad_threshold, dens.split_scale = o.split_scale, dens.min_opacity = o.min_opacity;
     dens.shrink = 1.6f;
 
+    const uint32_t top_degree = degree < 3 ? degree : 3;
+    bool was_reset = false;
     for (uint32_t it = 0; it < o.iters; ++it) {
         const View& v = views[it % views.size()];
+        if (o.sh_degree_every) {
+            const uint32_t d = (it + 1) / o.sh_degree_every;
+            if ((s = gsrt_trainer_set_sh_degree(tr, d < top_degree ? d : top_degree)) != GSRT_OK) die(ctx, "gsrt_trainer_set_sh_degree", s);
+        }
         if ((s = gsrt_lr_expon(1.6e-4f, 1.6e-6f, 0.01f, 0, o.iters, it, &adam.lr_center)) != GSRT_OK) die(ctx, "gsrt_lr_expon", s);
         float sc[GSRT_FRAME_LOSS_SCALARS];
         if ((s = gsrt_trainer_step(tr, &v.ubo, 0, v.target.data(), 3, nullptr, nullptr, &loss, &adam, sc)) != GSRT_OK)
@@ -170,14 +185,16 @@ int main(int argc, char** argv) {
         const uint32_t done = it + 1;
         if (o.densify_every && done >= o.densify_from && done <= o.densify_until && done % o.densify_every == 0) {
             uint32_t rows = 0;
-            s = gsrt_trainer_densify(tr, &dens, o.seed, &rows);
+            s = gsrt_trainer_densify_screen(tr, &dens, was_reset ? o.max_screen_radius : 0.0f, o.seed, &rows);
             if (s == GSRT_E_ARG)  // over the capacity (or nothing left): the model stays as it is
                 std::fprintf(stderr, "gsrt_train: iteration %u: no densify (%s)\n", done, gsrt_last_error(ctx));
             else if (s != GSRT_OK)
                 die(ctx, "gsrt_trainer_densify", s);
         }
-        if (o.reset_every && done % o.reset_every == 0 && done < o.iters)
+        if (o.reset_every && done % o.reset_every == 0 && done < o.iters) {
             if ((s = gsrt_trainer_opacity_reset(tr, 0.01f)) != GSRT_OK) die(ctx, "gsrt_trainer_opacity_reset", s);
+            was_reset = true;
+        }
         if (done % 100 == 0 || done == o.iters) {
             gsrt_trainer_info(tr, &n, nullptr, nullptr);
             std::printf("%u %.6f %.6f %.6f %u\n", done, (double)sc[0], (double)sc[1], (double)sc[2], n);

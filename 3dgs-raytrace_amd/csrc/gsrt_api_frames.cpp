@@ -418,6 +418,52 @@ gsrt_status gsrt_splat_depth_grad_to_model(gsrt_scene* sc, const gsrt_ubo* ubo, 
     return model_grad_blocking(sc, ubo, grad_splat, grad_center, grad_cov, accumulate, true);
 }
 
+// ---- per-view statistics with the screen radius (k_view_stats, gsrt_densify.hip) -----------------------------------
+// On the render stream behind the gradient frame that wrote the rows, reading the scene's parameters as the chain above.
+static gsrt_status check_view_stats_args(gsrt_scene* sc, const gsrt_ubo* ubo, const float* rows, const float* stats) {
+    if (!sc || !ubo) return GSRT_E_ARG;
+    const std::string name = "gsrt_view_stats_add: ";
+    if (!rows || !stats) return fail(sc->ctx, GSRT_E_ARG, name + "grad_splat or stats is NULL");
+    if (!ubo->width || !ubo->height) return fail(sc->ctx, GSRT_E_ARG, name + "width and height must be non-zero");
+    if (sc->ntri) return fail(sc->ctx, GSRT_E_ARG, name + "not for a scene with a triangle mesh");
+    if (!sc->bvh_built) return fail(sc->ctx, GSRT_E_STATE, name + "before gsrt_build_bvh");
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_view_stats_add_async(gsrt_scene* sc, const gsrt_ubo* ubo, const float* d_grad_splat, float* d_stats,
+                                      float* d_radii) {
+    gsrt_status s = check_view_stats_args(sc, ubo, d_grad_splat, d_stats);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    if (reinterpret_cast<uintptr_t>(d_grad_splat) % 16u)
+        return fail(ctx, GSRT_E_ARG, "gsrt_view_stats_add: grad_splat must be 16-byte aligned on the device");
+    (void)hipSetDevice(ctx->device);
+    if (!sc->n) return GSRT_OK;
+    if (d_radii) {  // the parameters are read only for the radius
+        if ((s = gsrt::wait_updates(ctx, ctx->stream)) != GSRT_OK) return s;
+        ctx->serial_pending = true;
+        ctx->serial_reads = true;
+    }
+    gsrt::launch_view_stats(ctx->stream, sc->n, *ubo, sc->d_params, d_grad_splat, d_stats, d_radii);
+    GSRT_HIP(ctx, hipGetLastError());
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_view_stats_add(gsrt_scene* sc, const gsrt_ubo* ubo, const float* grad_splat, float* stats, float* radii) {
+    gsrt_status s = check_view_stats_args(sc, ubo, grad_splat, stats);
+    if (s != GSRT_OK) return s;
+    gsrt_ctx* ctx = sc->ctx;
+    (void)hipSetDevice(ctx->device);
+    const size_t n = sc->n;
+    std::vector<CallArray> list = {{&grad_splat, sizeof(float) * 8 * n, true, false},
+                                   {&stats, sizeof(float) * 2 * n, true, true},
+                                   {&radii, sizeof(float) * n, true, true}};
+    if (gsrt::call_side(list) == gsrt::Side::mixed)
+        return fail(ctx, GSRT_E_ARG, "gsrt_view_stats_add: the arrays must all be host pointers or all be device pointers");
+    return gsrt::run_staged(ctx, "gsrt_view_stats_add: ", list,
+                            [&] { return gsrt_view_stats_add_async(sc, ubo, grad_splat, stats, radii); });
+}
+
 // ---- the camera's gradient (gsrt_pose_grad.hip) -------------------------------------------------------------------
 // On the render stream behind the gradient frame that wrote the rows, reading the scene's parameters as the chain above.
 static gsrt_status check_pose_grad_args(gsrt_scene* sc, const gsrt_ubo* ubo, const float* rows, const float* out) {

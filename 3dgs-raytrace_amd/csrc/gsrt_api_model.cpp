@@ -79,12 +79,16 @@ gsrt_status gsrt_density_stats_add(gsrt_ctx* ctx, uint32_t n, uint32_t width, ui
                       [&] { return gsrt_density_stats_add_async(ctx, n, width, height, grad_splat, stats); });
 }
 
-gsrt_status gsrt_densify_count(gsrt_ctx* ctx, uint32_t n, const float* scale, const float* opacity, const float* stats,
-                               const gsrt_densify_params* params, uint32_t* n_out) {
+// gsrt_densify_count is this with radii nullptr and max_radius 0 (fn: the name the refusals carry)
+static gsrt_status densify_count_any(gsrt_ctx* ctx, const char* fn, uint32_t n, const float* scale, const float* opacity,
+                                     const float* stats, const gsrt_densify_params* params, const float* radii,
+                                     float max_radius, uint32_t* n_out) {
     if (!ctx) return GSRT_E_ARG;
-    if (!n_out || (n && (!scale || !opacity || !stats))) return fail(ctx, GSRT_E_ARG, "gsrt_densify_count: a NULL pointer");
-    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, "gsrt_densify_count: n above GSRT_MAX_GAUSSIANS");
-    gsrt_status s = check_densify_params(ctx, "gsrt_densify_count", params);
+    const std::string name = std::string(fn) + ": ";
+    if (!n_out || (n && (!scale || !opacity || !stats))) return fail(ctx, GSRT_E_ARG, name + "a NULL pointer");
+    if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, name + "n above GSRT_MAX_GAUSSIANS");
+    if (std::isnan(max_radius)) return fail(ctx, GSRT_E_ARG, name + "max_screen_radius is NaN");
+    gsrt_status s = check_densify_params(ctx, fn, params);
     if (s != GSRT_OK) return s;
     *n_out = 0;
     if (!n) return GSRT_OK;
@@ -93,24 +97,39 @@ gsrt_status gsrt_densify_count(gsrt_ctx* ctx, uint32_t n, const float* scale, co
     // each array on its own side
     std::vector<CallArray> list = {{&scale, sizeof(float) * 3 * n, true, false},
                                    {&opacity, sizeof(float) * n, true, false},
-                                   {&stats, sizeof(float) * 2 * n, true, false}};
+                                   {&stats, sizeof(float) * 2 * n, true, false},
+                                   {&radii, sizeof(float) * n, true, false}};
     uint32_t* const d_n = ctx->d_densify_ws + gsrt::densify_blocks(n);
-    const std::vector<Download> count = {{n_out, d_n, sizeof(uint32_t), "gsrt_densify_count: download failed"}};
-    return run_staged(ctx, "gsrt_densify_count: ", list, [&]() -> gsrt_status {
-        gsrt::launch_densify_count(ctx->stream, n, *params, scale, opacity, stats, ctx->d_densify_ws, d_n);
-        if (hipGetLastError() != hipSuccess) return fail(ctx, GSRT_E_DEVICE, "gsrt_densify_count: launch failed");
+    const std::string what = name + "download failed";
+    const std::vector<Download> count = {{n_out, d_n, sizeof(uint32_t), what.c_str()}};
+    return run_staged(ctx, name, list, [&]() -> gsrt_status {
+        gsrt::launch_densify_count(ctx->stream, n, *params, scale, opacity, stats, radii, max_radius, ctx->d_densify_ws, d_n);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, GSRT_E_DEVICE, name + "launch failed");
         return GSRT_OK;
     }, &count);
 }
 
+gsrt_status gsrt_densify_count(gsrt_ctx* ctx, uint32_t n, const float* scale, const float* opacity, const float* stats,
+                               const gsrt_densify_params* params, uint32_t* n_out) {
+    return densify_count_any(ctx, "gsrt_densify_count", n, scale, opacity, stats, params, nullptr, 0.0f, n_out);
+}
+gsrt_status gsrt_densify_screen_count(gsrt_ctx* ctx, uint32_t n, const float* scale, const float* opacity,
+                                      const float* stats, const gsrt_densify_params* params, const float* radii,
+                                      float max_screen_radius, uint32_t* n_out) {
+    return densify_count_any(ctx, "gsrt_densify_screen_count", n, scale, opacity, stats, params, radii, max_screen_radius,
+                             n_out);
+}
+
 // what both forms of gsrt_densify refuse before anything is queued
-static gsrt_status check_densify_args(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats,
-                                      const float* noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
-                                      const int32_t* origin, uint32_t cap, const uint32_t* n_out) {
+static gsrt_status check_densify_args(gsrt_ctx* ctx, const char* fn, const gsrt_model_arrays* in, uint32_t n,
+                                      const float* stats, const float* noise, const gsrt_densify_params* params,
+                                      float max_radius, const gsrt_model_arrays* out, const int32_t* origin, uint32_t cap,
+                                      const uint32_t* n_out) {
     if (!ctx) return GSRT_E_ARG;
-    const std::string name = "gsrt_densify: ";
+    const std::string name = std::string(fn) + ": ";
     if (!in || !out || !n_out) return fail(ctx, GSRT_E_ARG, name + "in, out or n_out is NULL");
-    if (gsrt_status s = check_densify_params(ctx, "gsrt_densify", params); s != GSRT_OK) return s;
+    if (gsrt_status s = check_densify_params(ctx, fn, params); s != GSRT_OK) return s;
+    if (std::isnan(max_radius)) return fail(ctx, GSRT_E_ARG, name + "max_screen_radius is NaN");
     if (n > GSRT_MAX_GAUSSIANS) return fail(ctx, GSRT_E_ARG, name + "n above GSRT_MAX_GAUSSIANS");
     for (const gsrt_model_arrays* m : {in, out})
         if (m->feature_channels > GSRT_MAX_FEATURES || (m->features == nullptr) != (m->feature_channels == 0))
@@ -130,61 +149,96 @@ static gsrt_status check_densify_args(gsrt_ctx* ctx, const gsrt_model_arrays* in
 }
 
 // both kernels of the pass on the render stream; every pointer is a device pointer and the arguments are checked
-static gsrt_status densify_enqueue(gsrt_ctx* ctx, const gsrt_model_arrays& in, uint32_t n, const float* d_stats,
-                                   const float* d_noise, const gsrt_densify_params& P, const gsrt_model_arrays& out,
-                                   int32_t* d_origin, uint32_t cap, uint32_t* d_n_out) {
+static gsrt_status densify_enqueue(gsrt_ctx* ctx, const std::string& name, const gsrt_model_arrays& in, uint32_t n,
+                                   const float* d_stats, const float* d_noise, const gsrt_densify_params& P,
+                                   const float* d_radii, float max_radius, const gsrt_model_arrays& out, int32_t* d_origin,
+                                   uint32_t cap, uint32_t* d_n_out) {
     if ((reinterpret_cast<uintptr_t>(in.sh) | reinterpret_cast<uintptr_t>(out.sh)) % 16u)
-        return fail(ctx, GSRT_E_ARG, "gsrt_densify: sh must be 16-byte aligned on the device");
+        return fail(ctx, GSRT_E_ARG, name + "sh must be 16-byte aligned on the device");
     if (gsrt_status s = densify_workspace(ctx, n); s != GSRT_OK) return s;
-    gsrt::launch_densify_count(ctx->stream, n, P, in.scale, in.opacity, d_stats, ctx->d_densify_ws, d_n_out);
-    gsrt::launch_densify_write(ctx->stream, n, P, in, d_stats, d_noise, out, d_origin, cap, ctx->d_densify_ws, d_n_out);
+    gsrt::launch_densify_count(ctx->stream, n, P, in.scale, in.opacity, d_stats, d_radii, max_radius, ctx->d_densify_ws,
+                               d_n_out);
+    gsrt::launch_densify_write(ctx->stream, n, P, in, d_stats, d_radii, max_radius, d_noise, out, d_origin, cap,
+                               ctx->d_densify_ws, d_n_out);
     GSRT_HIP(ctx, hipGetLastError());
     return GSRT_OK;
+}
+
+// gsrt_densify_async is this with radii nullptr and max_radius 0
+static gsrt_status densify_async_any(gsrt_ctx* ctx, const char* fn, const gsrt_model_arrays* in, uint32_t n,
+                                     const float* d_stats, const float* d_noise, const gsrt_densify_params* params,
+                                     const float* d_radii, float max_radius, const gsrt_model_arrays* out,
+                                     int32_t* d_origin, uint32_t cap, uint32_t* d_n_out) {
+    gsrt_status s = check_densify_args(ctx, fn, in, n, d_stats, d_noise, params, max_radius, out, d_origin, cap, d_n_out);
+    if (s != GSRT_OK) return s;
+    (void)hipSetDevice(ctx->device);
+    return densify_enqueue(ctx, std::string(fn) + ": ", *in, n, d_stats, d_noise, *params, d_radii, max_radius, *out,
+                           d_origin, cap, d_n_out);
 }
 
 gsrt_status gsrt_densify_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* d_stats,
                                const float* d_noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
                                int32_t* d_origin, uint32_t cap, uint32_t* d_n_out) {
-    gsrt_status s = check_densify_args(ctx, in, n, d_stats, d_noise, params, out, d_origin, cap, d_n_out);
-    if (s != GSRT_OK) return s;
-    (void)hipSetDevice(ctx->device);
-    return densify_enqueue(ctx, *in, n, d_stats, d_noise, *params, *out, d_origin, cap, d_n_out);
+    return densify_async_any(ctx, "gsrt_densify", in, n, d_stats, d_noise, params, nullptr, 0.0f, out, d_origin, cap, d_n_out);
+}
+gsrt_status gsrt_densify_screen_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* d_stats,
+                                      const float* d_noise, const gsrt_densify_params* params, const float* d_radii,
+                                      float max_screen_radius, const gsrt_model_arrays* out, int32_t* d_origin,
+                                      uint32_t cap, uint32_t* d_n_out) {
+    return densify_async_any(ctx, "gsrt_densify_screen", in, n, d_stats, d_noise, params, d_radii, max_screen_radius, out,
+                             d_origin, cap, d_n_out);
 }
 
-gsrt_status gsrt_densify(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats, const float* noise,
-                         const gsrt_densify_params* params, const gsrt_model_arrays* out, int32_t* origin, uint32_t cap,
-                         uint32_t* n_out) {
-    gsrt_status s = check_densify_args(ctx, in, n, stats, noise, params, out, origin, cap, n_out);
+// gsrt_densify is this with radii nullptr and max_radius 0
+static gsrt_status densify_any(gsrt_ctx* ctx, const char* fn, const gsrt_model_arrays* in, uint32_t n, const float* stats,
+                               const float* noise, const gsrt_densify_params* params, const float* radii, float max_radius,
+                               const gsrt_model_arrays* out, int32_t* origin, uint32_t cap, uint32_t* n_out) {
+    gsrt_status s = check_densify_args(ctx, fn, in, n, stats, noise, params, max_radius, out, origin, cap, n_out);
     if (s != GSRT_OK) return s;
+    const std::string name = std::string(fn) + ": ";
     *n_out = 0;
     if (!n) return GSRT_OK;
     (void)hipSetDevice(ctx->device);
-    // inputs | stats | noise | outputs | origin, all on the host or all on the device (absent arrays take no side)
+    // inputs | stats | noise | radii | outputs | origin, all on the host or all on the device (absent arrays take no side)
     gsrt_model_arrays a_in = *in, a_out = *out;
     std::vector<CallArray> list;
     model_set_arrays(list, a_in, n, true, false);
     list.push_back({&stats, sizeof(float) * 2 * n, true, false});
     list.push_back({&noise, sizeof(float) * 6 * n, true, false});
+    list.push_back({&radii, sizeof(float) * n, true, false});
     const size_t first_out = list.size();
     model_set_arrays(list, a_out, cap, false, true);
     list.push_back({&origin, sizeof(int32_t) * (size_t)cap, false, true});
     if (gsrt::call_side(list) == Side::mixed)
-        return fail(ctx, GSRT_E_ARG, "gsrt_densify: the arrays must all be host pointers or all be device pointers");
+        return fail(ctx, GSRT_E_ARG, name + "the arrays must all be host pointers or all be device pointers");
     if ((s = densify_workspace(ctx, n)) != GSRT_OK) return s;
     uint32_t* const d_n = ctx->d_densify_ws + gsrt::densify_blocks(n);
-    return run_staged(ctx, "gsrt_densify: ", list, [&]() -> gsrt_status {
-        gsrt_status e = densify_enqueue(ctx, a_in, n, stats, noise, *params, a_out, origin, cap, d_n);
+    return run_staged(ctx, name, list, [&]() -> gsrt_status {
+        gsrt_status e = densify_enqueue(ctx, name, a_in, n, stats, noise, *params, radii, max_radius, a_out, origin, cap, d_n);
         // the count decides what comes back: the stream is drained here for it
         if (e == GSRT_OK && (hipMemcpyAsync(n_out, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                              hipStreamSynchronize(ctx->stream) != hipSuccess))
-            e = fail(ctx, GSRT_E_DEVICE, "gsrt_densify: count download failed");
+            e = fail(ctx, GSRT_E_DEVICE, name + "count download failed");
         if (e == GSRT_OK && (*n_out > cap || *n_out > GSRT_MAX_GAUSSIANS))  // the pass wrote nothing
-            return fail(ctx, GSRT_E_ARG, "gsrt_densify: " + std::to_string(*n_out) + " output rows needed, cap is " +
+            return fail(ctx, GSRT_E_ARG, name + std::to_string(*n_out) + " output rows needed, cap is " +
                                              std::to_string(cap) + " (at most GSRT_MAX_GAUSSIANS rows)");
         if (e == GSRT_OK && cap)  // only the rows written are downloaded
             for (size_t i = first_out; i < list.size(); ++i) list[i].bytes = list[i].bytes / cap * *n_out;
         return e;
     });
+}
+
+gsrt_status gsrt_densify(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats, const float* noise,
+                         const gsrt_densify_params* params, const gsrt_model_arrays* out, int32_t* origin, uint32_t cap,
+                         uint32_t* n_out) {
+    return densify_any(ctx, "gsrt_densify", in, n, stats, noise, params, nullptr, 0.0f, out, origin, cap, n_out);
+}
+gsrt_status gsrt_densify_screen(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats,
+                                const float* noise, const gsrt_densify_params* params, const float* radii,
+                                float max_screen_radius, const gsrt_model_arrays* out, int32_t* origin, uint32_t cap,
+                                uint32_t* n_out) {
+    return densify_any(ctx, "gsrt_densify_screen", in, n, stats, noise, params, radii, max_screen_radius, out, origin, cap,
+                       n_out);
 }
 
 // ---- photometric loss (gsrt_image_loss.hip) -----------------------------------------------------------------------
@@ -431,9 +485,11 @@ gsrt_status gsrt_adam_scalars(const gsrt_adam_params* adam, float out[GSRT_ADAM_
 static gsrt_status model_step_any(gsrt_ctx* ctx, const char* fn, bool blocking, uint32_t n, const gsrt_model_arrays* raw,
                                   const gsrt_model_arrays* m, const gsrt_model_arrays* v, const gsrt_model_grads* grads,
                                   const gsrt_adam_params* adam, bool step, const gsrt_model_arrays* act,
-                                  gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out, float* grad_raw) {
+                                  gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out, float* grad_raw,
+                                  uint32_t sh_degree = 3) {
     if (!ctx) return GSRT_E_ARG;
     const std::string name = std::string(fn) + ": ";
+    if (sh_degree > 3) return fail(ctx, GSRT_E_ARG, name + "sh_degree must be 0..3");
     if (!raw || (step && (!m || !v || !grads || !adam))) return fail(ctx, GSRT_E_ARG, name + "a NULL struct");
     if (step)
         if (const char* why = check_adam(adam)) return fail(ctx, GSRT_E_ARG, name + why);
@@ -476,7 +532,8 @@ static gsrt_status model_step_any(gsrt_ctx* ctx, const char* fn, bool blocking, 
     gsrt::AdamScalars K{};
     if (step) adam_scalars(*adam, K);
     const auto run = [&]() -> gsrt_status {
-        gsrt::launch_model_step(ctx->stream, n, step ? &K : nullptr, r, &mm, &vv, &gg, aa, params_out, aabbs_out, grad_raw);
+        gsrt::launch_model_step(ctx->stream, n, step ? &K : nullptr, r, &mm, &vv, &gg, aa, params_out, aabbs_out, grad_raw,
+                                sh_degree);
         if (hipGetLastError() != hipSuccess) return fail(ctx, GSRT_E_DEVICE, name + "launch failed");
         return GSRT_OK;
     };
@@ -495,6 +552,21 @@ gsrt_status gsrt_model_step_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_ar
                                   const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
                                   float* grad_raw) {
     return model_step_any(ctx, "gsrt_model_step", false, n, raw, m, v, grads, adam, true, act, params_out, aabbs_out, grad_raw);
+}
+gsrt_status gsrt_model_step_degree(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* m,
+                                   const gsrt_model_arrays* v, const gsrt_model_grads* grads, const gsrt_adam_params* adam,
+                                   uint32_t sh_degree, const gsrt_model_arrays* act, gsrt_gauss_param* params_out,
+                                   gsrt_aabb* aabbs_out, float* grad_raw) {
+    return model_step_any(ctx, "gsrt_model_step_degree", true, n, raw, m, v, grads, adam, true, act, params_out, aabbs_out,
+                          grad_raw, sh_degree);
+}
+gsrt_status gsrt_model_step_degree_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw,
+                                         const gsrt_model_arrays* m, const gsrt_model_arrays* v,
+                                         const gsrt_model_grads* grads, const gsrt_adam_params* adam, uint32_t sh_degree,
+                                         const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
+                                         float* grad_raw) {
+    return model_step_any(ctx, "gsrt_model_step_degree", false, n, raw, m, v, grads, adam, true, act, params_out, aabbs_out,
+                          grad_raw, sh_degree);
 }
 gsrt_status gsrt_model_activate(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* act,
                                 gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out) {

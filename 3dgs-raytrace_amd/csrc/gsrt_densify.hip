@@ -1,11 +1,13 @@
-// gsrt_densify.hip -- adaptive density control on the device (gsrt_density_stats_add, gsrt_densify_count, gsrt_densify):
-// the densification statistic from splat rows, the clone / split / prune / keep decision per Gaussian, and one ordered
-// compaction pass that writes the new model; and gsrt_model_remap, the gather that carries the optimiser state across it.
+// gsrt_densify.hip -- adaptive density control on the device (gsrt_density_stats_add, gsrt_view_stats_add,
+// gsrt_densify_count, gsrt_densify and their _screen forms): the densification statistic from splat rows, alone or with
+// the largest screen radius beside it, the clone / split / prune / keep decision per Gaussian, and one ordered compaction
+// pass that writes the new model; and gsrt_model_remap, the gather that carries the optimiser state across it.
 //
-// All five kernels are HBM-bound streaming kernels at ordinary priority, 256 lanes a workgroup as the scene build's
-// kernels; none is a prep kernel. Per Gaussian: k_density_stats 32 B read + 8 B read-modify-write; k_densify_count 24 B
-// read; k_densify_write 24 B + 44 B (+ 24 B noise for a split) read, 48 B per output row written, plus the 192-B SH row and
-// the feature row read once per output row and written once.
+// All six kernels are HBM-bound streaming kernels at ordinary priority, 256 lanes a workgroup as the scene build's
+// kernels; none is a prep kernel. Per Gaussian: k_density_stats 32 B read + 8 B read-modify-write; k_view_stats the same
+// and, for a seen Gaussian, its 48-B gsrt_gauss_param read + 4 B of radii read (and written when the radius grows);
+// k_densify_count 24 B read (+ 4 B with radii); k_densify_write 24 B + 44 B (+ 24 B noise for a split) read, 48 B per
+// output row written, plus the 192-B SH row and the feature row read once per output row and written once.
 //
 // The order of the output is the order of the input: Gaussian g's c_g in {0, 1, 2} rows start at o_g = sum of c_h over
 // h < g. The sum has three levels: a lane's offset in its wave is two ballots and two popcounts (c >= 1 and c == 2 below
@@ -16,6 +18,7 @@
 #include <cstdint>
 
 #include "gsrt_internal.hpp"
+#include "gsrt_project.hpp"
 
 namespace gsrt {
 
@@ -43,18 +46,59 @@ __global__ __launch_bounds__(256) void k_density_stats(uint32_t n, float half_w,
     s[1] = s[1] + 1.0f;
 }
 
+// gsrt_view_stats_add: k_density_stats' statistic, the same operations in the same order, and beside it the largest
+// screen radius (radii, nullable). One lane per Gaussian, no atomics. The loads follow what gsrt_project.hpp records for
+// k_pose_partial: the row first, as two whole float4s, and the gsrt_gauss_param of a seen Gaussian only, issued with its
+// radius word ahead of the statistic's read-modify-write so that the two round trips overlap. The radius
+// is 3DGS's: 3 sigma of the larger eigenvalue of the chain's own V (the 0.3 low-pass included), each operation rounded on
+// its own. A NaN r fails the comparison and stores nothing; an unseen, behind-camera or singular Gaussian's word is
+// not touched. 25 VGPRs, no scratch: eight waves a SIMD, as k_density_stats.
+__global__ __launch_bounds__(256) void k_view_stats(uint32_t n, const gsrt_ubo ubo,
+                                                    const gsrt_gauss_param* __restrict__ params,
+                                                    const float* __restrict__ rows, float* __restrict__ stats,
+                                                    float* __restrict__ radii) {
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const float4* row = reinterpret_cast<const float4*>(rows) + 2 * (size_t)g;  // 32-byte rows of a 16-byte aligned table
+    const float4 a = row[0], b = row[1];
+    const bool seen = a.x != 0.0f || a.y != 0.0f || a.z != 0.0f || a.w != 0.0f || b.x != 0.0f || b.y != 0.0f;
+    if (!seen) return;  // the statistic's words and the radius stay bit for bit as they were
+    gsrt_gauss_param p;
+    float have = 0.0f;
+    if (radii) {
+        p = params[g];  // as k_splat_grad_to_model reads it: a borrowed array need not be 16-byte aligned
+        have = radii[g];
+    }
+    const float half_w = 0.5f * (float)ubo.width, half_h = 0.5f * (float)ubo.height;
+    const float gx = a.x * half_w, gy = a.y * half_h;
+    const float norm = sqrtf(gx * gx + gy * gy);
+    float* s = stats + 2 * (size_t)g;
+    s[0] = s[0] + norm;
+    s[1] = s[1] + 1.0f;
+    if (!radii) return;
+    CorChain f;
+    if (cor_chain(ubo, p, f) != kCorValid) return;
+    const float mid = 0.5f * (f.v00 + f.v11);
+    const float disc = fmaf(mid, mid, -f.det);
+    const float lam = mid + sqrtf(fmaxf(0.1f, disc));
+    const float r = ceilf(3.0f * sqrtf(lam));
+    if (r > have) radii[g] = r;
+}
+
 // the decision of gsrt_densify for Gaussian g: its output rows (0 prune, 1 keep, 2 clone or split) and whether the two
-// are split children. m is the largest scale as k_cov3d takes it.
+// are split children. m is the largest scale as k_cov3d takes it. radii (nullable) with max_radius > 0: the screen-size
+// prune of the _screen forms; a NaN radius fails the comparison and does not prune.
 __device__ inline uint32_t densify_rows(const gsrt_densify_params& P, const float* __restrict__ scale,
-                                        const float* __restrict__ opacity, const float* __restrict__ stats, uint32_t g,
-                                        bool& split) {
+                                        const float* __restrict__ opacity, const float* __restrict__ stats,
+                                        const float* __restrict__ radii, float max_radius, uint32_t g, bool& split) {
     const float s0 = scale[3 * (size_t)g + 0], s1 = scale[3 * (size_t)g + 1], s2 = scale[3 * (size_t)g + 2];
     float m = s0;
     if (s1 > m) m = s1;
     if (s2 > m) m = s2;
     const float sum = stats[2 * (size_t)g + 0], cnt = stats[2 * (size_t)g + 1];
     const float mean = cnt > 0.0f ? sum / cnt : 0.0f;
-    const bool prune = !(opacity[g] >= P.min_opacity) || (P.max_scale > 0.0f && m > P.max_scale);
+    const bool prune = !(opacity[g] >= P.min_opacity) || (P.max_scale > 0.0f && m > P.max_scale) ||
+                       (radii && max_radius > 0.0f && radii[g] > max_radius);
     const bool dens = !prune && mean >= P.grad_threshold;
     split = dens && m > P.split_scale;
     return prune ? 0u : dens ? 2u : 1u;
@@ -64,11 +108,12 @@ __global__ __launch_bounds__(kDensBlock) void k_densify_count(uint32_t n, const 
                                                               const float* __restrict__ scale,
                                                               const float* __restrict__ opacity,
                                                               const float* __restrict__ stats,
+                                                              const float* __restrict__ radii, float max_radius,
                                                               uint32_t* __restrict__ block_total) {
     __shared__ uint32_t wsum[kDensWaves];
     const uint32_t t = threadIdx.x, g = blockIdx.x * kDensBlock + t;
     bool split = false;
-    const uint32_t c = g < n ? densify_rows(P, scale, opacity, stats, g, split) : 0u;
+    const uint32_t c = g < n ? densify_rows(P, scale, opacity, stats, radii, max_radius, g, split) : 0u;
     const uint64_t m1 = __ballot(c >= 1u), m2 = __ballot(c == 2u);
     if ((t & 63u) == 0) wsum[t >> 6] = (uint32_t)(__popcll(m1) + __popcll(m2));
     __syncthreads();
@@ -114,6 +159,7 @@ __global__ __launch_bounds__(256) void k_densify_scan(uint32_t nblocks, uint32_t
 // Nothing is stored when the total exceeds cap (or the largest scene): the whole grid leaves first.
 __global__ __launch_bounds__(kDensBlock) void k_densify_write(uint32_t n, const gsrt_densify_params P,
                                                               const gsrt_model_arrays in, const float* __restrict__ stats,
+                                                              const float* __restrict__ radii, float max_radius,
                                                               const float* __restrict__ noise, const gsrt_model_arrays out,
                                                               int32_t* __restrict__ origin, uint32_t cap,
                                                               const uint32_t* __restrict__ block_base,
@@ -124,7 +170,7 @@ __global__ __launch_bounds__(kDensBlock) void k_densify_write(uint32_t n, const 
     if (total > cap || total > GSRT_MAX_GAUSSIANS) return;
     const uint32_t t = threadIdx.x, g = blockIdx.x * kDensBlock + t;
     bool split = false;
-    const uint32_t c = g < n ? densify_rows(P, in.scale, in.opacity, stats, g, split) : 0u;
+    const uint32_t c = g < n ? densify_rows(P, in.scale, in.opacity, stats, radii, max_radius, g, split) : 0u;
     const uint64_t m1 = __ballot(c >= 1u), m2 = __ballot(c == 2u);
     const uint32_t wave = t >> 6;
     if ((t & 63u) == 0) wsum[wave] = (uint32_t)(__popcll(m1) + __popcll(m2));
@@ -283,21 +329,31 @@ void launch_density_stats(hipStream_t s, uint32_t n, uint32_t width, uint32_t he
                        0.5f * (float)width, 0.5f * (float)height, rows, stats);
 }
 
+void launch_view_stats(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params, const float* rows,
+                       float* stats, float* radii) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_view_stats, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, s, n, ubo, params, rows,
+                       stats, radii);
+}
+
 void launch_densify_count(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const float* scale, const float* opacity,
-                          const float* stats, uint32_t* block_total, uint32_t* d_n_out) {
+                          const float* stats, const float* radii, float max_radius, uint32_t* block_total,
+                          uint32_t* d_n_out) {
     const uint32_t nblocks = densify_blocks(n);
     if (nblocks)
-        hipLaunchKernelGGL(k_densify_count, dim3(nblocks), dim3(kDensBlock), 0, s, n, P, scale, opacity, stats, block_total);
+        hipLaunchKernelGGL(k_densify_count, dim3(nblocks), dim3(kDensBlock), 0, s, n, P, scale, opacity, stats, radii,
+                           max_radius, block_total);
     hipLaunchKernelGGL(k_densify_scan, dim3(1), dim3(256), 0, s, nblocks, block_total, d_n_out);
 }
 
 void launch_densify_write(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const gsrt_model_arrays& in,
-                          const float* stats, const float* noise, const gsrt_model_arrays& out, int32_t* origin,
-                          uint32_t cap, const uint32_t* block_base, const uint32_t* d_n_out) {
+                          const float* stats, const float* radii, float max_radius, const float* noise,
+                          const gsrt_model_arrays& out, int32_t* origin, uint32_t cap, const uint32_t* block_base,
+                          const uint32_t* d_n_out) {
     const uint32_t nblocks = densify_blocks(n);
     if (!nblocks) return;
-    hipLaunchKernelGGL(k_densify_write, dim3(nblocks), dim3(kDensBlock), 0, s, n, P, in, stats, noise, out, origin, cap,
-                       block_base, d_n_out);
+    hipLaunchKernelGGL(k_densify_write, dim3(nblocks), dim3(kDensBlock), 0, s, n, P, in, stats, radii, max_radius, noise,
+                       out, origin, cap, block_base, d_n_out);
 }
 
 }  // namespace gsrt

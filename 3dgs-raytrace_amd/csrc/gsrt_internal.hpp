@@ -469,16 +469,23 @@ void launch_sh_grad_compact(hipStream_t s, float* dst, const float* rows, uint32
 void launch_splat_grad_to_model(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params,
                                 const float* rows, float* grad_center, float* grad_cov, bool accumulate, bool depth = false);
 // adaptive density control (gsrt_densify.hip). launch_density_stats: stats[g] += {norm, 1} for every seen splat row.
+// launch_view_stats: the same statistic and, with radii (nullable), radii[g] = max(radii[g], the screen radius of a seen
+// Gaussian that cor_chain finds valid for ubo, from params); rows and params 16-byte aligned.
+// radii (nullable) and max_radius of the count and write passes: the screen-size prune, off with nullptr or <= 0.
 // launch_densify_count: the count kernel's workgroup totals into block_total[0..densify_blocks(n)), scanned in place to
 // the workgroups' first output rows, and the sum into *d_n_out. launch_densify_write: the compaction pass, which reads
 // both and stores nothing when *d_n_out exceeds cap
 uint32_t densify_blocks(uint32_t n);
 void launch_density_stats(hipStream_t s, uint32_t n, uint32_t width, uint32_t height, const float* rows, float* stats);
+void launch_view_stats(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt_gauss_param* params, const float* rows,
+                       float* stats, float* radii);
 void launch_densify_count(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const float* scale, const float* opacity,
-                          const float* stats, uint32_t* block_total, uint32_t* d_n_out);
+                          const float* stats, const float* radii, float max_radius, uint32_t* block_total,
+                          uint32_t* d_n_out);
 void launch_densify_write(hipStream_t s, uint32_t n, const gsrt_densify_params& P, const gsrt_model_arrays& in,
-                          const float* stats, const float* noise, const gsrt_model_arrays& out, int32_t* origin,
-                          uint32_t cap, const uint32_t* block_base, const uint32_t* d_n_out);
+                          const float* stats, const float* radii, float max_radius, const float* noise,
+                          const gsrt_model_arrays& out, int32_t* origin, uint32_t cap, const uint32_t* block_base,
+                          const uint32_t* d_n_out);
 // gsrt_model_remap (gsrt_densify.hip): out's row i = in's row origin[i], +0 where origin[i] < 0; device pointers
 void launch_model_remap(hipStream_t s, uint32_t n_out, const int32_t* origin, const gsrt_model_arrays& in,
                         const gsrt_model_arrays& out);
@@ -521,7 +528,8 @@ void launch_pose_grad(hipStream_t s, uint32_t n, const gsrt_ubo& ubo, const gsrt
 // floats (ss per group: centre, rot, log scale, logit, SH coefficient 0, SH rest, features), bit i of frozen set when
 // group i's lr is 0, the flags. launch_model_step: K == nullptr is the activation alone (m, v, G unused); every pointer a
 // device pointer, act's members, params, aabbs and grad_raw nullable. The SH / feature rows are stepped in place and
-// copied to act's where that is another array.
+// copied to act's where that is another array. sh_degree 0..3: the words from 3 (sh_degree + 1)^2 on of an SH row keep
+// their bits in raw, m and v (gsrt_model_step_degree); 3 steps the whole row.
 struct AdamScalars {
     float beta1, beta2, a1, a2, c2, eps;
     float ss[7];
@@ -529,7 +537,8 @@ struct AdamScalars {
 };
 void launch_model_step(hipStream_t s, uint32_t n, const AdamScalars* K, const gsrt_model_arrays& raw,
                        const gsrt_model_arrays* m, const gsrt_model_arrays* v, const gsrt_model_grads* G,
-                       const gsrt_model_arrays& act, gsrt_gauss_param* params, gsrt_aabb* aabbs, float* grad_raw);
+                       const gsrt_model_arrays& act, gsrt_gauss_param* params, gsrt_aabb* aabbs, float* grad_raw,
+                       uint32_t sh_degree = 3);
 void launch_model_deactivate(hipStream_t s, uint32_t n, const gsrt_model_arrays& act, const gsrt_model_arrays& raw);
 void launch_opacity_reset(hipStream_t s, uint32_t n, float limit, float* logit, float* m, float* v);
 // the last frame's framebuffer: d_fb, or the alternating buffer a slot-stream frame rendered into

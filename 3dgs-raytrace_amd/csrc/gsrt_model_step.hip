@@ -261,20 +261,23 @@ __global__ __launch_bounds__(256) void k_model_geom(uint32_t n, const AdamScalar
 
 // The SH (len 48: words 0..2 of a row are coefficient 0, group ss_head) or feature rows (len C, one group), flat over
 // the table. W = 4: one float4 a lane (len a multiple of 4, 16-byte aligned bases); W = 1: one word a lane.
-// frozen_head / frozen_rest: that group's words keep their bits. act_rows (nullable): the updated words are stored
-// there too, for every Gaussian.
+// frozen_head / frozen_rest: that group's words keep their bits. limit: so do the words from `limit` on of a row (the SH
+// words above the active degree, 3 (d + 1)^2 of 48; len: none). The test is per word: 3, 12 and 27 are no multiples
+// of 4, so a W == 4 lane can straddle the limit; a lane wholly past it touches m, v and the gradient no more than an
+// unseen Gaussian's does. act_rows (nullable): the updated words are stored there too, for every Gaussian.
 template <int W>
-__global__ __launch_bounds__(256) void k_model_rows(size_t count, uint32_t len, uint32_t head, const AdamScalars K,
-                                                    float ss_head, float ss_rest, uint32_t frozen_head,
-                                                    uint32_t frozen_rest, float* raw, float* mom1, float* mom2,
+__global__ __launch_bounds__(256) void k_model_rows(size_t count, uint32_t len, uint32_t head, uint32_t limit,
+                                                    const AdamScalars K, float ss_head, float ss_rest,
+                                                    uint32_t frozen_head, uint32_t frozen_rest, float* raw, float* mom1,
+                                                    float* mom2,
                                                     const float* __restrict__ grad, const float* __restrict__ splat,
                                                     uint32_t splat_vec, float* act_rows) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     const size_t w0 = i * W, g = w0 / len;
     const uint32_t wi = (uint32_t)(w0 - g * len);
-    bool stepped = true;
-    if (K.flags & GSRT_ADAM_SPARSE) {
+    bool stepped = wi < limit;
+    if (stepped && (K.flags & GSRT_ADAM_SPARSE)) {
         float row[6];
         if (splat_vec) load_splat6<true>(splat, g, row);
         else load_splat6<false>(splat, g, row);
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(256) void k_model_rows(size_t count, uint32_t len, 
 #pragma unroll
         for (int j = 0; j < W; ++j) {
             const bool is_head = wi + j < head;
-            if (is_head ? frozen_head : frozen_rest) continue;  // the words keep their bits
+            if ((is_head ? frozen_head : frozen_rest) || wi + j >= limit) continue;  // the words keep their bits
             adam_word(K, is_head ? ss_head : ss_rest, gr[j], p[j], m[j], v[j]);
         }
         if constexpr (W == 4) {
@@ -349,24 +352,26 @@ static uint32_t blocks256(size_t count) { return (uint32_t)((count + 255) / 256)
 static bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 // one table of rows: the float4 path when the row length and every base allow it
-static void launch_rows(hipStream_t s, uint32_t n, uint32_t len, uint32_t head, const AdamScalars& K, float ss_head,
-                        float ss_rest, bool frozen_head, bool frozen_rest, float* raw, float* m, float* v, const float* grad,
-                        const float* splat, float* act_rows) {
+static void launch_rows(hipStream_t s, uint32_t n, uint32_t len, uint32_t head, uint32_t limit, const AdamScalars& K,
+                        float ss_head, float ss_rest, bool frozen_head, bool frozen_rest, float* raw, float* m, float* v,
+                        const float* grad, const float* splat, float* act_rows) {
     const size_t words = (size_t)n * len;
     const bool vec = len % 4 == 0 && aligned(raw, 16) && aligned(m, 16) && aligned(v, 16) && aligned(grad, 16) &&
                      aligned(act_rows, 16);
     const uint32_t splat_vec = aligned(splat, 16) ? 1u : 0u;
     if (vec)
-        hipLaunchKernelGGL(k_model_rows<4>, dim3(blocks256(words / 4)), dim3(256), 0, s, words / 4, len, head, K, ss_head,
-                           ss_rest, frozen_head ? 1u : 0u, frozen_rest ? 1u : 0u, raw, m, v, grad, splat, splat_vec, act_rows);
+        hipLaunchKernelGGL(k_model_rows<4>, dim3(blocks256(words / 4)), dim3(256), 0, s, words / 4, len, head, limit, K,
+                           ss_head, ss_rest, frozen_head ? 1u : 0u, frozen_rest ? 1u : 0u, raw, m, v, grad, splat, splat_vec,
+                           act_rows);
     else
-        hipLaunchKernelGGL(k_model_rows<1>, dim3(blocks256(words)), dim3(256), 0, s, words, len, head, K, ss_head, ss_rest,
-                           frozen_head ? 1u : 0u, frozen_rest ? 1u : 0u, raw, m, v, grad, splat, splat_vec, act_rows);
+        hipLaunchKernelGGL(k_model_rows<1>, dim3(blocks256(words)), dim3(256), 0, s, words, len, head, limit, K, ss_head,
+                           ss_rest, frozen_head ? 1u : 0u, frozen_rest ? 1u : 0u, raw, m, v, grad, splat, splat_vec, act_rows);
 }
 
 void launch_model_step(hipStream_t s, uint32_t n, const AdamScalars* K, const gsrt_model_arrays& raw,
                        const gsrt_model_arrays* m, const gsrt_model_arrays* v, const gsrt_model_grads* G,
-                       const gsrt_model_arrays& act, gsrt_gauss_param* params, gsrt_aabb* aabbs, float* grad_raw) {
+                       const gsrt_model_arrays& act, gsrt_gauss_param* params, gsrt_aabb* aabbs, float* grad_raw,
+                       uint32_t sh_degree) {
     if (!n) return;
     bool vec = aligned(raw.rot_rxyz, 16) && aligned(act.rot_rxyz, 16) && aligned(params, 16) && aligned(aabbs, 8);
     if (K)
@@ -383,18 +388,20 @@ void launch_model_step(hipStream_t s, uint32_t n, const AdamScalars* K, const gs
         else hipLaunchKernelGGL((k_model_geom<false, false>), grid, block, 0, s, n, zero, raw, none, none, no_grads, act, params, aabbs, nullptr);
     }
     // the rows: stepped where a group moves, copied to act where it is another array
-    struct Table { float* raw; float* m; float* v; const float* grad; float* act; uint32_t len, head; int g_head, g_rest; };
+    struct Table { float* raw; float* m; float* v; const float* grad; float* act; uint32_t len, head, limit; int g_head, g_rest; };
+    const uint32_t sh_words = 3u * (sh_degree + 1u) * (sh_degree + 1u);  // the active words of an SH row
     const Table tables[2] = {
-        {raw.sh, K ? m->sh : nullptr, K ? v->sh : nullptr, K ? G->sh : nullptr, act.sh, 48u, 3u, 4, 5},
+        {raw.sh, K ? m->sh : nullptr, K ? v->sh : nullptr, K ? G->sh : nullptr, act.sh, 48u, 3u, sh_words, 4, 5},
         {raw.features, K ? m->features : nullptr, K ? v->features : nullptr, K ? G->features : nullptr, act.features,
-         raw.feature_channels, 0u, 6, 6}};
+         raw.feature_channels, 0u, raw.feature_channels, 6, 6}};
     for (const Table& t : tables) {
         if (!t.raw) continue;
         float* const act_rows = t.act && t.act != t.raw ? t.act : nullptr;
-        const bool fh = !K || ((K->frozen >> t.g_head) & 1u), fr = !K || ((K->frozen >> t.g_rest) & 1u);
+        const bool fh = !K || ((K->frozen >> t.g_head) & 1u);
+        const bool fr = !K || ((K->frozen >> t.g_rest) & 1u) || t.limit <= t.head;  // degree 0: no word of the rest moves
         if (K && !(fh && fr))
-            launch_rows(s, n, t.len, t.head, *K, K->ss[t.g_head], K->ss[t.g_rest], fh, fr, t.raw, t.m, t.v, t.grad, G->splat,
-                        act_rows);
+            launch_rows(s, n, t.len, t.head, t.limit, *K, K->ss[t.g_head], K->ss[t.g_rest], fh, fr, t.raw, t.m, t.v, t.grad,
+                        G->splat, act_rows);
         else if (act_rows)
             (void)hipMemcpyAsync(act_rows, t.raw, sizeof(float) * (size_t)n * t.len, hipMemcpyDeviceToDevice, s);
     }

@@ -6,7 +6,7 @@
 //   two sets of raw, m, v (cur and the other one, which gsrt_trainer_densify writes and then makes cur),
 //   two activated sets without SH (act[0]: gsrt_model_activate's output, the densify pass's input; act[1]: its output;
 //   an activated model's SH rows are its raw model's, so act[i].sh points into a raw set),
-//   the gradient tables (centre 3, cov 6, splat rows 8, SH 48), stats 2, noise 6, origin 1, the scene arrays of a step
+//   the gradient tables (centre 3, cov 6, splat rows 8, SH 48), stats 2, radii 1, noise 6, origin 1, the scene arrays of a step
 //   (params 12, aabbs 6), and a few scalars. The frame buffers (rgba, depth, both gradients, staged targets) follow the
 //   frame size.
 #include <hip/hip_runtime.h>
@@ -29,12 +29,13 @@ struct gsrt_trainer {
     gsrt_ctx* ctx = nullptr;
     gsrt_scene* scene = nullptr;
     uint32_t n = 0, cap = 0, step = 0;
+    uint32_t sh_degree = 3;           // the active SH degree of a step
     bool has_sh = false;
     int cur = 0;                      // the buffer set in use
     gsrt_model_arrays raw[2]{}, m[2]{}, v[2]{};
     gsrt_model_arrays act[2]{};       // act[i].sh is set per use
     float *g_center = nullptr, *g_cov = nullptr, *g_splat = nullptr, *g_sh = nullptr;
-    float *stats = nullptr, *noise = nullptr, *scalars = nullptr;
+    float *stats = nullptr, *radii = nullptr, *noise = nullptr, *scalars = nullptr;
     int32_t* origin = nullptr;
     uint32_t* d_n_out = nullptr;
     gsrt_gauss_param* params = nullptr;
@@ -183,7 +184,7 @@ gsrt_status gsrt_trainer_create(gsrt_ctx* ctx, const gsrt_model_arrays* model, u
         ok = alloc_set(t, t->raw[i], *model) && alloc_set(t, t->m[i], *model) && alloc_set(t, t->v[i], *model) &&
              alloc_set(t, t->act[i], no_sh);
     ok = ok && dev_alloc(t, &t->g_center, 3 * cap) && dev_alloc(t, &t->g_cov, 6 * cap) && dev_alloc(t, &t->g_splat, 8 * cap) &&
-         (!t->has_sh || dev_alloc(t, &t->g_sh, 48 * cap)) && dev_alloc(t, &t->stats, 2 * cap) &&
+         (!t->has_sh || dev_alloc(t, &t->g_sh, 48 * cap)) && dev_alloc(t, &t->stats, 2 * cap) && dev_alloc(t, &t->radii, cap) &&
          dev_alloc(t, &t->noise, 6 * cap) && dev_alloc(t, &t->scalars, 8) && dev_alloc(t, &t->origin, cap) &&
          dev_alloc(t, &t->d_n_out, 4) && dev_alloc(t, &t->params, cap) && dev_alloc(t, &t->aabbs, cap);
     if (!ok) {
@@ -204,6 +205,7 @@ gsrt_status gsrt_trainer_create(gsrt_ctx* ctx, const gsrt_model_arrays* model, u
             for (uint32_t f = 0; f < nf; ++f)
                 hip(hipMemsetAsync(set->*mf[f].member, 0, sizeof(float) * mf[f].floats * cap, st), "memset");
     hip(hipMemsetAsync(t->stats, 0, sizeof(float) * 2 * cap, st), "memset");
+    hip(hipMemsetAsync(t->radii, 0, sizeof(float) * cap, st), "memset");
     if (s == GSRT_OK) s = gsrt_model_deactivate_async(ctx, n, &a0, &t->raw[0]);
     if (s == GSRT_OK) s = gsrt_synchronize(ctx);  // gsrt_scene_from_model reads a device source at the call
     if (s == GSRT_OK) s = gsrt_scene_from_model(ctx, a0.center, a0.rot_rxyz, a0.scale, a0.opacity, a0.sh, n, &t->scene);
@@ -276,7 +278,7 @@ gsrt_status gsrt_trainer_step(gsrt_trainer* t, const gsrt_ubo* ubo, uint32_t k, 
             s = gsrt_frame_loss_async(ctx, W, H, t->rgba, d_target, target_channels, d_mask, t->depth, d_tdepth, P, t->scalars,
                                       t->gimg, t->gdepth);
         if (s == GSRT_OK) s = gsrt_render_splat_depth_grad_async(sc, ubo, GSRT_MODE_COR, k, t->gimg, t->gdepth, t->g_splat, 0);
-        if (s == GSRT_OK) s = gsrt_density_stats_add_async(ctx, t->n, W, H, t->g_splat, t->stats);
+        if (s == GSRT_OK) s = gsrt_view_stats_add_async(sc, ubo, t->g_splat, t->stats, t->radii);
         if (s == GSRT_OK) s = gsrt_splat_depth_grad_to_model_async(sc, ubo, t->g_splat, t->g_center, t->g_cov, 0);
     } else {
         s = gsrt_render_async(sc, ubo, GSRT_MODE_COR, k, t->rgba, nullptr);
@@ -284,11 +286,12 @@ gsrt_status gsrt_trainer_step(gsrt_trainer* t, const gsrt_ubo* ubo, uint32_t k, 
             s = gsrt_frame_loss_async(ctx, W, H, t->rgba, d_target, target_channels, d_mask, nullptr, nullptr, P, t->scalars,
                                       t->gimg, nullptr);
         if (s == GSRT_OK) s = gsrt_render_splat_grad_async(sc, ubo, GSRT_MODE_COR, k, t->gimg, t->g_splat, 0);
-        if (s == GSRT_OK) s = gsrt_density_stats_add_async(ctx, t->n, W, H, t->g_splat, t->stats);
+        if (s == GSRT_OK) s = gsrt_view_stats_add_async(sc, ubo, t->g_splat, t->stats, t->radii);
         if (s == GSRT_OK) s = gsrt_splat_grad_to_model_async(sc, ubo, t->g_splat, t->g_center, t->g_cov, 0);
     }
     if (s == GSRT_OK && t->has_sh) s = gsrt_render_sh_grad_async(sc, ubo, GSRT_MODE_COR, k, t->gimg, t->g_sh, 0);
-    if (s == GSRT_OK) s = gsrt_model_step_async(ctx, t->n, &raw, &m, &v, &grads, &A, nullptr, t->params, t->aabbs, nullptr);
+    if (s == GSRT_OK)
+        s = gsrt_model_step_degree_async(ctx, t->n, &raw, &m, &v, &grads, &A, t->sh_degree, nullptr, t->params, t->aabbs, nullptr);
     if (s != GSRT_OK) {
         (void)gsrt_synchronize(ctx);
         return s;
@@ -305,19 +308,27 @@ gsrt_status gsrt_trainer_step(gsrt_trainer* t, const gsrt_ubo* ubo, uint32_t k, 
 }
 
 gsrt_status gsrt_trainer_densify(gsrt_trainer* t, const gsrt_densify_params* P, uint64_t seed, uint32_t* n_out) {
+    return gsrt_trainer_densify_screen(t, P, 0.0f, seed, n_out);
+}
+
+gsrt_status gsrt_trainer_densify_screen(gsrt_trainer* t, const gsrt_densify_params* P, float max_screen_radius, uint64_t seed,
+                                        uint32_t* n_out) {
     if (!t) return GSRT_E_ARG;
     gsrt_ctx* ctx = t->ctx;
     const std::string name = "gsrt_trainer_densify: ";
     if (!P) return fail(ctx, GSRT_E_ARG, name + "params is NULL");
     if (P->reserved[0] || P->reserved[1] || P->reserved[2] || !(P->shrink > 0.0f))
         return fail(ctx, GSRT_E_ARG, name + "bad params (a non-zero reserved word, or shrink not > 0)");
+    if (std::isnan(max_screen_radius)) return fail(ctx, GSRT_E_ARG, name + "max_screen_radius is NaN");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = (hipStream_t)gsrt_stream(ctx);
     const int cur = t->cur, oth = 1 - t->cur;
     const gsrt_model_arrays a_in = with_sh_of(t->act[0], t->raw[cur]), a_out = with_sh_of(t->act[1], t->raw[oth]);
     gsrt_status s = gsrt_normal_noise_async(ctx, 6ull * t->n, seed, t->step, t->noise);
     if (s == GSRT_OK) s = gsrt_model_activate_async(ctx, t->n, &t->raw[cur], &a_in, nullptr, nullptr);
-    if (s == GSRT_OK) s = gsrt_densify_async(ctx, &a_in, t->n, t->stats, t->noise, P, &a_out, t->origin, t->cap, t->d_n_out);
+    if (s == GSRT_OK)
+        s = gsrt_densify_screen_async(ctx, &a_in, t->n, t->stats, t->noise, P, t->radii, max_screen_radius, &a_out, t->origin,
+                                      t->cap, t->d_n_out);
     uint32_t rows = 0;
     if (s == GSRT_OK && (hipMemcpyAsync(&rows, t->d_n_out, sizeof rows, hipMemcpyDeviceToHost, st) != hipSuccess ||
                          hipStreamSynchronize(st) != hipSuccess))
@@ -332,7 +343,8 @@ gsrt_status gsrt_trainer_densify(gsrt_trainer* t, const gsrt_densify_params* P, 
     if (s == GSRT_OK) s = gsrt_model_remap_async(ctx, rows, t->origin, &t->v[cur], &t->v[oth]);
     // the scene is that of the new raw model's activation, as after a step
     if (s == GSRT_OK) s = gsrt_model_activate_async(ctx, rows, &t->raw[oth], &a_out, nullptr, nullptr);
-    if (s == GSRT_OK && hipMemsetAsync(t->stats, 0, sizeof(float) * 2 * (size_t)t->cap, st) != hipSuccess)
+    if (s == GSRT_OK && (hipMemsetAsync(t->stats, 0, sizeof(float) * 2 * (size_t)t->cap, st) != hipSuccess ||
+                         hipMemsetAsync(t->radii, 0, sizeof(float) * (size_t)t->cap, st) != hipSuccess))
         s = fail(ctx, GSRT_E_DEVICE, name + "memset failed");
     if (s == GSRT_OK) s = gsrt_synchronize(ctx);
     gsrt_scene* fresh = nullptr;
@@ -387,6 +399,25 @@ gsrt_status gsrt_trainer_state(gsrt_trainer* t, gsrt_model_arrays* raw, gsrt_mod
     if (v) *v = t->v[t->cur];
     if (grads) *grads = {t->g_center, t->g_cov, t->g_splat, t->has_sh ? t->g_sh : nullptr, nullptr};
     if (stats) *stats = t->stats;
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_trainer_radii(gsrt_trainer* t, const float** radii) {
+    if (!t || !radii) return GSRT_E_ARG;
+    *radii = t->radii;
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_trainer_set_sh_degree(gsrt_trainer* t, uint32_t sh_degree) {
+    if (!t) return GSRT_E_ARG;
+    if (sh_degree > 3) return fail(t->ctx, GSRT_E_ARG, "gsrt_trainer_set_sh_degree: sh_degree must be 0..3");
+    t->sh_degree = sh_degree;
+    return GSRT_OK;
+}
+
+gsrt_status gsrt_trainer_sh_degree(const gsrt_trainer* t, uint32_t* sh_degree) {
+    if (!t || !sh_degree) return GSRT_E_ARG;
+    *sh_degree = t->sh_degree;
     return GSRT_OK;
 }
 

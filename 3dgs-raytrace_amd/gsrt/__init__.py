@@ -82,7 +82,10 @@ EXPORTS = [
     "gsrt_normal_noise", "gsrt_normal_noise_async", "gsrt_debug_philox", "gsrt_model_remap", "gsrt_model_remap_async",
     "gsrt_ply_write", "gsrt_lr_expon", "gsrt_trainer_create", "gsrt_trainer_destroy", "gsrt_trainer_step",
     "gsrt_trainer_densify", "gsrt_trainer_opacity_reset", "gsrt_trainer_rebuild_bvh", "gsrt_trainer_scene",
-    "gsrt_trainer_info", "gsrt_trainer_state", "gsrt_trainer_download",
+    "gsrt_trainer_info", "gsrt_trainer_state", "gsrt_trainer_download", "gsrt_view_stats_add", "gsrt_view_stats_add_async",
+    "gsrt_densify_screen", "gsrt_densify_screen_async", "gsrt_densify_screen_count", "gsrt_model_step_degree",
+    "gsrt_model_step_degree_async", "gsrt_trainer_densify_screen", "gsrt_trainer_set_sh_degree", "gsrt_trainer_sh_degree",
+    "gsrt_trainer_radii",
 ]
 
 
@@ -252,6 +255,17 @@ def _load():
         "gsrt_trainer_info": ([P, P, P, P], i32),
         "gsrt_trainer_state": ([P, P, P, P, P, PP], i32),
         "gsrt_trainer_download": ([P, P, P], i32),
+        "gsrt_view_stats_add": ([P, P, P, P, P], i32),
+        "gsrt_view_stats_add_async": ([P, P, P, P, P], i32),
+        "gsrt_densify_screen": ([P, P, u32, P, P, P, P, f32, P, P, u32, P], i32),
+        "gsrt_densify_screen_async": ([P, P, u32, P, P, P, P, f32, P, P, u32, P], i32),
+        "gsrt_densify_screen_count": ([P, u32, P, P, P, P, P, f32, P], i32),
+        "gsrt_model_step_degree": ([P, u32, P, P, P, P, P, u32, P, P, P, P], i32),
+        "gsrt_model_step_degree_async": ([P, u32, P, P, P, P, P, u32, P, P, P, P], i32),
+        "gsrt_trainer_densify_screen": ([P, P, f32, ctypes.c_uint64, P], i32),
+        "gsrt_trainer_set_sh_degree": ([P, u32], i32),
+        "gsrt_trainer_sh_degree": ([P, P], i32),
+        "gsrt_trainer_radii": ([P, PP], i32),
     }
     for name, (args, res) in sig.items():
         # an experiment build named by GSRT_LIB_PATH (an older revision under A/B) may predate a symbol; the
@@ -645,9 +659,30 @@ def density_stats_add(ctx, grad_splat, stats, width, height, n=None, asynchronou
     return stats
 
 
-def densify_count(ctx, scale, opacity, stats, params, n=None) -> int:
+def view_stats_add(scene, ubo, grad_splat, stats, radii=None, asynchronous=False):
+    """density_stats_add for a scene's Gaussians, with the largest screen radius beside it (gsrt_view_stats_add): stats
+    (n, 2) gets exactly density_stats_add's bits for ubo's width and height; radii (n,), or None for the statistic alone,
+    becomes max(radii, r) for every seen Gaussian the COR projection of ubo finds valid, r = ceil(3 sqrt(the larger
+    eigenvalue of its 2-D covariance)) in pixels. All numpy float32 arrays changed in place, or all device addresses (int);
+    asynchronous (device addresses only) enqueues on the ctx's stream without waiting. Returns (stats, radii)."""
+    if isinstance(grad_splat, int) or isinstance(stats, int) or isinstance(radii, int):
+        fn = lib.gsrt_view_stats_add_async if asynchronous else lib.gsrt_view_stats_add
+        _check(fn(scene.handle, _p(ubo), _addr(grad_splat), _addr(stats), _addr(radii)), scene.ctx)
+        return stats, radii
+    n = scene.n
+    for name, a, shape in (("stats", stats, (n, 2)), ("radii", radii, (n,))):
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and
+                                  a.shape == shape):
+            raise GsrtError(E_ARG, f"view_stats_add: {name} is a C-contiguous float32 array of shape {shape}, changed in place")
+    rows = _f32(grad_splat, (n, 8))
+    _check(lib.gsrt_view_stats_add(scene.handle, _p(ubo), _p(rows), _p(stats), _p(radii)), scene.ctx)
+    return stats, radii
+
+
+def densify_count(ctx, scale, opacity, stats, params, n=None, radii=None, max_screen_radius=0.0) -> int:
     """the rows densify would write (gsrt_densify_count): scale (n, 3), opacity (n,), stats (n, 2) as numpy arrays or
-    device addresses (int, with n given), params a DensifyParams"""
+    device addresses (int, with n given), params a DensifyParams. With radii (n,) (view_stats_add's) the screen-size prune
+    takes part (gsrt_densify_screen_count): a Gaussian whose radius is > max_screen_radius (> 0) is pruned."""
     keep = []
     if n is None:
         n = np.asarray(opacity).reshape(-1).shape[0]
@@ -658,13 +693,17 @@ def densify_count(ctx, scale, opacity, stats, params, n=None) -> int:
         keep.append(_f32(x, shape))
         return _p(keep[-1])
     out = ctypes.c_uint32(0)
+    if radii is not None:
+        _check(lib.gsrt_densify_screen_count(ctx.handle, n, arg(scale, (n, 3)), arg(opacity, (n,)), arg(stats, (n, 2)),
+                                             ctypes.byref(params), arg(radii, (n,)), max_screen_radius, ctypes.byref(out)), ctx)
+        return int(out.value)
     _check(lib.gsrt_densify_count(ctx.handle, n, arg(scale, (n, 3)), arg(opacity, (n,)), arg(stats, (n, 2)),
                                   ctypes.byref(params), ctypes.byref(out)), ctx)
     return int(out.value)
 
 
 def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features=None, *, n=None, feature_channels=0,
-            out=None, origin=None, cap=None, d_n_out=None):
+            out=None, origin=None, cap=None, d_n_out=None, radii=None, max_screen_radius=0.0):
     """Clone, split, prune or keep every Gaussian of a model and write the new one, in input order (gsrt_densify; the
     rule and the arithmetic are in gsrt.h). stats: (n, 2) from density_stats_add; noise: (n, 2, 3), the caller's normal
     draws for the two children of a split; params: a DensifyParams (densify_params).
@@ -674,19 +713,26 @@ def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features
     device addresses (int; sh / features 0 or None when absent): n, feature_channels, out = the six output addresses in
     the same order, origin and cap (rows of room) are needed. Blocks and returns n_out (GsrtError E_ARG when it exceeds
     cap: nothing was written then); with d_n_out, the device address of one uint32, the pass is only enqueued on
-    ctx.stream (gsrt_densify_async) and None is returned."""
+    ctx.stream (gsrt_densify_async) and None is returned.
+    radii (n,) (view_stats_add's; a numpy array or a device address like the others) with max_screen_radius > 0: the
+    screen-size prune (gsrt_densify_screen), a Gaussian whose radius is > max_screen_radius is pruned; radii=None is
+    gsrt_densify itself."""
+    screen = radii is not None
     if isinstance(center, int):
         if n is None or out is None or origin is None or cap is None:
             raise GsrtError(E_ARG, "densify: device addresses need n, out, origin and cap")
         a_in = ModelArrays(center, rot, scale, opacity, sh or None, features or None, feature_channels)
         a_out = ModelArrays(*[x or None for x in out], feature_channels)
+        head = (ctx.handle, ctypes.byref(a_in), n, _addr(stats), _addr(noise), ctypes.byref(params))
+        if screen:
+            head += (_addr(radii), max_screen_radius)
         if d_n_out is not None:
-            _check(lib.gsrt_densify_async(ctx.handle, ctypes.byref(a_in), n, _addr(stats), _addr(noise), ctypes.byref(params),
-                                          ctypes.byref(a_out), _addr(origin), cap, _addr(d_n_out)), ctx)
+            fn = lib.gsrt_densify_screen_async if screen else lib.gsrt_densify_async
+            _check(fn(*head, ctypes.byref(a_out), _addr(origin), cap, _addr(d_n_out)), ctx)
             return None
         got = ctypes.c_uint32(0)
-        _check(lib.gsrt_densify(ctx.handle, ctypes.byref(a_in), n, _addr(stats), _addr(noise), ctypes.byref(params),
-                                ctypes.byref(a_out), _addr(origin), cap, ctypes.byref(got)), ctx)
+        fn = lib.gsrt_densify_screen if screen else lib.gsrt_densify
+        _check(fn(*head, ctypes.byref(a_out), _addr(origin), cap, ctypes.byref(got)), ctx)
         return int(got.value)
     center = _f32(center, (-1, 3))
     n = center.shape[0]
@@ -696,7 +742,8 @@ def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features
     sh = None if sh is None else _f32(sh, (n, 48))
     features = None if features is None else _f32(features, (n, -1) if n else np.asarray(features).shape)
     fc = 0 if features is None else features.shape[1]
-    rows = densify_count(ctx, scale, opacity, stats, params) if cap is None else cap
+    radii = _f32(radii, (n,)) if screen else None
+    rows = densify_count(ctx, scale, opacity, stats, params, radii=radii, max_screen_radius=max_screen_radius) if cap is None else cap
     o = [np.zeros((rows, 3), np.float32), np.zeros((rows, 4), np.float32), np.zeros((rows, 3), np.float32),
          np.zeros(rows, np.float32), None if sh is None else np.zeros((rows, 48), np.float32),
          None if features is None else np.zeros((rows, fc), np.float32)]
@@ -704,8 +751,11 @@ def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features
     a_in = ModelArrays(*[None if a is None else a.ctypes.data for a in (center, rot, scale, opacity, sh, features)], fc)
     a_out = ModelArrays(*[None if a is None else a.ctypes.data for a in o], fc)
     got = ctypes.c_uint32(0)
-    _check(lib.gsrt_densify(ctx.handle, ctypes.byref(a_in), n, _p(stats), _p(noise), ctypes.byref(params),
-                            ctypes.byref(a_out), _p(org), rows, ctypes.byref(got)), ctx)
+    head = (ctx.handle, ctypes.byref(a_in), n, _p(stats), _p(noise), ctypes.byref(params))
+    if screen:
+        head += (_p(radii), max_screen_radius)
+    _check((lib.gsrt_densify_screen if screen else lib.gsrt_densify)(*head, ctypes.byref(a_out), _p(org), rows,
+                                                                      ctypes.byref(got)), ctx)
     k = int(got.value)
     o = [None if a is None else a[:k] for a in o]
     if o[4] is not None:
@@ -971,7 +1021,7 @@ def _new_model(n, src_addr, fc, sh_shape=(48,)):
 
 
 def model_step(ctx, raw, m, v, grads, adam, *, n=None, feature_channels=0, act=None, params_out=None, aabbs_out=None,
-               grad_raw=None, want_act=True, want_grad_raw=False, asynchronous=False):
+               grad_raw=None, want_act=True, want_grad_raw=False, asynchronous=False, sh_degree=3):
     """One optimiser step on the raw model (gsrt_model_step; the formulas are in gsrt.h): the gradient tables chained to the
     raw parameters, Adam, and the next frame's arrays. raw, m, v: (center (n, 3), rot (n, 4) unnormalised, log scale
     (n, 3), logit opacity (n,), sh (n, 48) / (n, 16, 3) or None, features (n, C) or None), the moments in the same layout,
@@ -982,7 +1032,9 @@ def model_step(ctx, raw, m, v, grads, adam, *, n=None, feature_channels=0, act=N
     or None): act is the activated model, sh / features in it the stepped arrays themselves.
     device addresses (int; 0 or None when absent): n (and feature_channels) are needed; act = six addresses or None,
     params_out, aabbs_out, grad_raw addresses or None. Blocks and returns None; asynchronous=True only enqueues the call
-    on ctx.stream (gsrt_model_step_async): synchronise before Scene.update / Scene.attach read params_out / aabbs_out."""
+    on ctx.stream (gsrt_model_step_async): synchronise before Scene.update / Scene.attach read params_out / aabbs_out.
+    sh_degree (0..3): the active SH degree (gsrt_model_step_degree): the SH words from 3 (sh_degree + 1)^2 on keep their
+    bits in raw, m and v; 3, the default, is gsrt_model_step itself."""
     r_addr, n, fc, k1, dev = _model_set("model_step: raw", raw, n, True)
     m_addr, _, fcm, k2, dev_m = _model_set("model_step: m", m, n, True)
     v_addr, _, fcv, k3, dev_v = _model_set("model_step: v", v, n, True)
@@ -1004,9 +1056,13 @@ def model_step(ctx, raw, m, v, grads, adam, *, n=None, feature_channels=0, act=N
     s_g = ModelGrads(*g_addr)
     if dev:
         s_act = None if act is None else ModelArrays(*[x or None for x in act], fc)
-        fn = lib.gsrt_model_step_async if asynchronous else lib.gsrt_model_step
-        _check(fn(ctx.handle, n, ctypes.byref(s_raw), ctypes.byref(s_m), ctypes.byref(s_v), ctypes.byref(s_g),
-                  ctypes.byref(adam), None if s_act is None else ctypes.byref(s_act), _addr(params_out), _addr(aabbs_out),
+        head = (ctx.handle, n, ctypes.byref(s_raw), ctypes.byref(s_m), ctypes.byref(s_v), ctypes.byref(s_g), ctypes.byref(adam))
+        if sh_degree != 3:
+            fn = lib.gsrt_model_step_degree_async if asynchronous else lib.gsrt_model_step_degree
+            head += (sh_degree,)
+        else:
+            fn = lib.gsrt_model_step_async if asynchronous else lib.gsrt_model_step
+        _check(fn(*head, None if s_act is None else ctypes.byref(s_act), _addr(params_out), _addr(aabbs_out),
                   _addr(grad_raw)), ctx)
         return None
     out = _new_model(n, r_addr, fc) if want_act else None
@@ -1015,9 +1071,11 @@ def model_step(ctx, raw, m, v, grads, adam, *, n=None, feature_channels=0, act=N
         s_act = ModelArrays(*[None if a is None else a.ctypes.data for a in out], fc)
     params, aabbs = np.zeros((n, 12), np.float32), np.zeros((n, 6), np.float32)
     graw = np.zeros((n, 11), np.float32) if want_grad_raw else None
-    _check(lib.gsrt_model_step(ctx.handle, n, ctypes.byref(s_raw), ctypes.byref(s_m), ctypes.byref(s_v), ctypes.byref(s_g),
-                               ctypes.byref(adam), None if out is None else ctypes.byref(s_act), _p(params), _p(aabbs),
-                               _p(graw)), ctx)
+    head = (ctx.handle, n, ctypes.byref(s_raw), ctypes.byref(s_m), ctypes.byref(s_v), ctypes.byref(s_g), ctypes.byref(adam))
+    fn = lib.gsrt_model_step
+    if sh_degree != 3:
+        fn, head = lib.gsrt_model_step_degree, head + (sh_degree,)
+    _check(fn(*head, None if out is None else ctypes.byref(s_act), _p(params), _p(aabbs), _p(graw)), ctx)
     return dict(act=None if out is None else tuple(out), params=params, aabbs=aabbs, grad_raw=graw)
 
 
@@ -1629,6 +1687,10 @@ class Scene:
         _check(fn(self.handle, _p(ubo), ctypes.c_void_p(d_grad_splat or None), ctypes.c_void_p(d_grad_center or None),
                   ctypes.c_void_p(d_grad_cov or None), 1 if accumulate else 0), self.ctx)
 
+    def view_stats_add(self, ubo, grad_splat, stats, radii=None, asynchronous=False):
+        """gsrt.view_stats_add of this scene: the densification statistic of the rows and the largest screen radius"""
+        return view_stats_add(self, ubo, grad_splat, stats, radii, asynchronous)
+
     def pose_grad(self, ubo, rows, depth=False):
         """The camera's gradient (gsrt_pose_grad): rows is the (n, 8) table of splat_grad (depth=True: of splat_depth_grad)
         for the same ubo and scene parameters, a numpy array or a device address; returns (16,) float32, the partial
@@ -1846,12 +1908,39 @@ class Trainer:
             return None
         return dict(zip(("loss", "l1", "ssim", "mse", "depth_l1", "depth_samples"), (float(v) for v in out)))
 
-    def densify(self, params, seed=0) -> int:
-        """clone, split and prune with the statistics gathered since the last densify (gsrt_trainer_densify); returns the
+    @property
+    def sh_degree(self) -> int:
+        """the active SH degree of the following steps, 0..3 (gsrt_trainer_sh_degree / gsrt_trainer_set_sh_degree; 3 at
+        creation): the SH words above it keep their bits, 3DGS's ramp-up when the caller raises it as it goes"""
+        d = ctypes.c_uint32(0)
+        _check(lib.gsrt_trainer_sh_degree(self.handle, ctypes.byref(d)), self.ctx)
+        return int(d.value)
+
+    @sh_degree.setter
+    def sh_degree(self, d):
+        if not 0 <= int(d) <= 0xFFFFFFFF:
+            raise GsrtError(E_ARG, "Trainer.sh_degree: 0..3")
+        _check(lib.gsrt_trainer_set_sh_degree(self.handle, int(d)), self.ctx)
+
+    def radii(self) -> int:
+        """the device address of the screen radii gathered since the last densify (gsrt_trainer_radii): n floats in use,
+        borrowed until the next densify()"""
+        p = ctypes.c_void_p()
+        _check(lib.gsrt_trainer_radii(self.handle, ctypes.byref(p)), self.ctx)
+        return int(p.value)
+
+    def densify(self, params, seed=0, max_screen_radius=0.0) -> int:
+        """clone, split and prune with the statistics gathered since the last densify (gsrt_trainer_densify; with
+        max_screen_radius > 0 the screen-size prune too, gsrt_trainer_densify_screen: a Gaussian whose largest screen radius
+        since the last densify is above it is pruned); returns the
         new n. GsrtError(E_ARG) with nothing changed when the new model exceeds the capacity. Scenes obtained from scene()
         earlier are dead after it."""
         got = ctypes.c_uint32(0)
-        _check(lib.gsrt_trainer_densify(self.handle, ctypes.byref(params), seed, ctypes.byref(got)), self.ctx)
+        if max_screen_radius == 0.0:
+            _check(lib.gsrt_trainer_densify(self.handle, ctypes.byref(params), seed, ctypes.byref(got)), self.ctx)
+        else:
+            _check(lib.gsrt_trainer_densify_screen(self.handle, ctypes.byref(params), max_screen_radius, seed,
+                                                   ctypes.byref(got)), self.ctx)
         return int(got.value)
 
     def opacity_reset(self, max_opacity=0.01):

@@ -203,7 +203,9 @@ def render_rgba(scene, ubo, opacity, sh=None, mode=MODE_COR, k=0):
 
 def _add_density_stats(ctx, rows):
     """render_model(..., density_stats=t): this view's statistic from the splat rows just queued, behind them on the stream"""
-    if ctx.density_stats is not None:
+    if ctx.radii is not None:  # the same statistic, with the largest screen radius beside it
+        ctx.scene.view_stats_add(ctx.ubo, rows.data_ptr(), ctx.density_stats.data_ptr(), ctx.radii.data_ptr(), asynchronous=True)
+    elif ctx.density_stats is not None:
         W, H = int(ctx.ubo["width"][0]), int(ctx.ubo["height"][0])
         density_stats_add(ctx.scene.ctx, rows.data_ptr(), ctx.density_stats.data_ptr(), W, H, n=ctx.scene.n,
                           asynchronous=True)
@@ -238,7 +240,7 @@ def _view_grad(d_view):
 
 class _RenderModel(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats):
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats, radii):
         n = scene.n
         ubo = _ubo_with_view(ubo, view)
         params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
@@ -256,7 +258,7 @@ class _RenderModel(torch.autograd.Function):
         scene.ctx.synchronize()
         ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
         ctx.sh_shape = None if sh is None else tuple(sh.shape)
-        ctx.density_stats = density_stats
+        ctx.density_stats, ctx.radii = density_stats, radii
         ctx.has_view = view is not None
         return rgba
 
@@ -278,14 +280,14 @@ class _RenderModel(torch.autograd.Function):
         if d_sh is not None:
             ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
         ctx.scene.ctx.synchronize()
-        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, _view_grad(d_view), None, None, None, None, None
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, _view_grad(d_view), None, None, None, None, None, None
 
 
 class _RenderModelDepth(torch.autograd.Function):
     """_RenderModel with the expected depth as a second differentiable output (render_model(..., depth=True))"""
 
     @staticmethod
-    def forward(ctx, center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats):
+    def forward(ctx, center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats, radii):
         n = scene.n
         ubo = _ubo_with_view(ubo, view)
         params = torch.zeros((n, 12), dtype=torch.float32, device=center.device)  # GaussParam: centre, opacity, cov3d, pad
@@ -305,7 +307,7 @@ class _RenderModelDepth(torch.autograd.Function):
         ctx.scene, ctx.ubo, ctx.mode, ctx.k = scene, ubo.copy(), mode, k  # the camera as it is now
         ctx.sh_shape = None if sh is None else tuple(sh.shape)
         ctx.image = (H, W, center.device)
-        ctx.density_stats = density_stats
+        ctx.density_stats, ctx.radii = density_stats, radii
         ctx.has_view = view is not None
         return rgba, depth
 
@@ -332,7 +334,7 @@ class _RenderModelDepth(torch.autograd.Function):
         if d_sh is not None:  # the depth does not depend on SH
             ctx.scene.sh_grad_async(ctx.ubo, g.data_ptr(), d_sh.data_ptr(), False, ctx.mode, ctx.k)
         ctx.scene.ctx.synchronize()
-        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, _view_grad(d_view), None, None, None, None, None
+        return d_c, d_v, rows[:, 5].contiguous(), d_sh, None, _view_grad(d_view), None, None, None, None, None, None
 
 
 def model_covariance(rot, scale):
@@ -348,7 +350,7 @@ def model_covariance(rot, scale):
 
 
 def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR, k=0, depth=False, density_stats=None,
-                 view=None):
+                 view=None, radii=None):
     """One colour frame of a whole model as a torch tensor rgba[H, W, 4], differentiable with respect to `center` (n, 3),
     `rot` (n, 4; r, x, y, z, used as given), `scale` (n, 3), `opacity` (n,) and, when given, the SH table `sh` ((n, 16, 3)
     or (n, 48)): float32 GPU tensors for a scene of n Gaussians with a built BVH. cov3d is formed here with torch
@@ -370,6 +372,9 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
     density_stats: an (n, 2) float32 GPU tensor [sum, count], or None. When given, the backward adds this view's
     densification statistic to it (gsrt.density_stats_add of the splat rows it has just computed, on the plain path and the
     depth path alike); the caller zeroes it. None changes nothing.
+    radii: an (n,) float32 GPU tensor, or None; needs density_stats. When given, the backward's statistic call is
+    gsrt.view_stats_add: density_stats receives the same bits, and radii[g] becomes the largest screen radius (pixels) of
+    Gaussian g over the views that saw it, for densify(..., radii=, max_screen_radius=); the caller zeroes it.
     view: a (4, 4) float32 GPU tensor, the camera's model-view matrix with view[r, c] = model_view[c * 4 + r], or None. When
     given, the forward renders with a copy of `ubo` whose model_view is `view` and whose model_view_inverse is its inverse
     (computed in float64, outside the graph), and the backward adds one Scene.pose_grad_async behind the model chain and
@@ -392,11 +397,14 @@ def render_model(scene, ubo, center, rot, scale, opacity, sh=None, mode=MODE_COR
         raise ValueError("render_model: density_stats must be a contiguous (n, 2) float32 tensor on the GPU")
     if view is not None and (view.dtype != torch.float32 or not view.is_cuda or tuple(view.shape) != (4, 4)):
         raise ValueError("render_model: view must be a (4, 4) float32 tensor on the GPU")
+    if radii is not None and (density_stats is None or radii.dtype != torch.float32 or not radii.is_cuda or
+                              tuple(radii.shape) != (n,) or not radii.is_contiguous()):
+        raise ValueError("render_model: radii must be a contiguous (n,) float32 tensor on the GPU, beside density_stats")
     fn = _RenderModelDepth if depth else _RenderModel
-    return fn.apply(center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats)
+    return fn.apply(center, cov3d, opacity, sh, aabbs, view, scene, ubo, mode, k, density_stats, radii)
 
 
-def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features=None):
+def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features=None, radii=None, max_screen_radius=0.0):
     """Adaptive density control of a model on the device (gsrt.densify, gsrt_densify_async): clone, split, prune or keep
     every Gaussian by the rule of gsrt.h and return the new model (center', rot', scale', opacity', sh', features',
     origin) as torch tensors of n_out rows, in input order; sh' / features' are None when sh / features are. ctx: the
@@ -405,6 +413,8 @@ def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features
     random numbers): float32 GPU tensors; params: gsrt.densify_params(...). The outputs are allocated at 2 n rows, which
     always suffices, and returned as trimmed views. origin (int32) holds g for Gaussian g itself and -1 - g for a row
     newly made from g: remap_state carries optimiser state across. Gradients do not flow through this call.
+    radii (n,) (render_model's radii) with max_screen_radius > 0: 3DGS's screen-size prune (gsrt_densify_screen_async), a
+    Gaussian whose largest screen radius is above max_screen_radius is pruned; the caller zeroes radii afterwards.
 
     The whole loop, with Adam moments m and v per parameter tensor:
 
@@ -439,6 +449,8 @@ def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features
     if features is not None:
         fc = int(features.shape[1]) if features.dim() == 2 else -1
         tensors.append(("features", features, (n, fc)))
+    if radii is not None:
+        tensors.append(("radii", radii, (n,)))
     for name, t, shape in tensors:
         if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
             raise ValueError(f"densify: {name} must be a {shape} float32 tensor on the GPU")
@@ -453,7 +465,8 @@ def densify(ctx, center, rot, scale, opacity, sh, stats, noise, params, features
     torch.cuda.current_stream(dev).synchronize()
     _densify(ctx, ptr(src["center"]), ptr(src["rot"]), ptr(src["scale"]), ptr(src["opacity"]), ptr(src.get("sh")),
              ptr(src["stats"]), ptr(src["noise"]), params, ptr(src.get("features")), n=n, feature_channels=fc,
-             out=[ptr(t) for t in out], origin=origin.data_ptr(), cap=cap, d_n_out=n_out.data_ptr())
+             out=[ptr(t) for t in out], origin=origin.data_ptr(), cap=cap, d_n_out=n_out.data_ptr(),
+             radii=None if radii is None else ptr(src["radii"]), max_screen_radius=max_screen_radius)
     ctx.synchronize()
     rows = int(n_out.item())
     return tuple(None if t is None else t[:rows] for t in out) + (origin[:rows],)
@@ -586,7 +599,7 @@ def _model_tensors(name, tensors, n, dev, fc=None):
     return tensors
 
 
-def model_step(ctx, raw, m, v, grads, adam, want_act=True, want_grad_raw=False):
+def model_step(ctx, raw, m, v, grads, adam, want_act=True, want_grad_raw=False, sh_degree=3):
     """One optimiser step of the raw model in the library's own kernels (gsrt.model_step, gsrt_model_step_async; the
     formulas are in gsrt.h). ctx: the gsrt.Context. raw, m, v: (center (n, 3), rot (n, 4) unnormalised, log scale (n, 3),
     logit opacity (n,), sh (n, 16, 3) / (n, 48) or None, features (n, C) or None), the two Adam moments in the same layout:
@@ -597,6 +610,8 @@ def model_step(ctx, raw, m, v, grads, adam, want_act=True, want_grad_raw=False):
     None): the activated model (sh / features in it are raw's own tensors), the scene arrays for Scene.update, and the
     chained gradient the step used. Blocking synchronisation on both sides: torch's current stream before the call,
     Context.synchronize() after it. Gradients do not flow through this call.
+    sh_degree (0..3): the active SH degree (gsrt_model_step_degree_async): the SH words above it keep their bits in raw, m
+    and v; raise it as the run goes for 3DGS's ramp-up. 3 is the plain step.
 
     The whole loop, without torch.autograd or torch.optim (n Gaussians, a W x H target; new = torch.empty on the GPU):
 
@@ -640,6 +655,6 @@ def model_step(ctx, raw, m, v, grads, adam, want_act=True, want_grad_raw=False):
     torch.cuda.current_stream(dev).synchronize()
     _model_step(ctx, [ptr(t) for t in raw], [ptr(t) for t in m], [ptr(t) for t in v], [ptr(t) for t in grads], adam, n=n,
                 feature_channels=fc, act=None if act is None else [ptr(t) for t in act], params_out=params.data_ptr(),
-                aabbs_out=aabbs.data_ptr(), grad_raw=ptr(graw), asynchronous=True)
+                aabbs_out=aabbs.data_ptr(), grad_raw=ptr(graw), asynchronous=True, sh_degree=sh_degree)
     ctx.synchronize()
     return dict(act=act, params=params, aabbs=aabbs, grad_raw=graw)

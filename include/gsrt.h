@@ -510,8 +510,9 @@ gsrt_status gsrt_splat_depth_grad_to_model_async(gsrt_scene* scene, const gsrt_u
  * The model is the gsrt_scene_from_model arrays; the calls below work on arrays, not on a scene: a scene's size is fixed,
  * so after gsrt_densify the caller creates a new scene from the new arrays (gsrt_scene_from_model takes device pointers)
  * and builds its BVH. A split's samples come from the caller's noise, so a result is a pure function of its inputs;
- * gsrt_normal_noise (below) draws such noise on the device from a seed. Not provided: screen-radius pruning, resizing a
- * scene in place (an opacity reset: gsrt_model_opacity_reset below). */
+ * gsrt_normal_noise (below) draws such noise on the device from a seed. 3DGS's screen-size prune is gsrt_view_stats_add
+ * (the largest screen radius beside the statistic) with gsrt_densify_screen. Not provided: resizing a scene in place (an
+ * opacity reset: gsrt_model_opacity_reset below), radii of sharded frames, a world-extent prune beyond max_scale. */
 typedef struct gsrt_model_arrays {   /* the gsrt_scene_from_model convention */
     float* center;    /* n x 3 */
     float* rot_rxyz;  /* n x 4, used as given */
@@ -595,6 +596,46 @@ gsrt_status gsrt_densify(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n,
 gsrt_status gsrt_densify_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* d_stats,
                                const float* d_noise, const gsrt_densify_params* params, const gsrt_model_arrays* out,
                                int32_t* d_origin, uint32_t cap, uint32_t* d_n_out);
+/* gsrt_density_stats_add for a scene's Gaussians (n is the scene's, width and height are the ubo's), and beside it 3DGS's
+ * max_radii2D: the largest screen radius of each Gaussian over the views that saw it. One lane per Gaussian, no atomics.
+ * stats (n x 2): exactly what gsrt_density_stats_add does for the same rows, bit for bit: the same operations in the same
+ * order, the same "seen" rule; an unseen Gaussian's words are untouched.
+ * radii (n floats, nullable; the caller zeroes it): only for a seen Gaussian whose COR projection of ubo is valid (its
+ * centre in front of the camera, det V > 0), from the scene's current parameters (a borrowed array included, read as
+ * gsrt_splat_grad_to_model reads it). With V = [[v00, v01], [v01, v11]] and det the COR projection's own float32 values
+ * (V = T Sigma T^T + 0.3 I: the low-pass is included, as in 3DGS), in float32, each operation rounded on its own:
+ *     mid  = 0.5f * (v00 + v11)
+ *     disc = fmaf(mid, mid, -det)
+ *     lam  = mid + sqrtf(fmaxf(0.1f, disc))
+ *     r    = ceilf(3.0f * sqrtf(lam))
+ *     if (r > radii[g]) radii[g] = r            (a NaN r stores nothing)
+ * An unseen, behind-camera or singular Gaussian keeps its word bit for bit.
+ * grad_splat, stats and radii are all host pointers or all device pointers (grad_splat 16-byte aligned on the device). The
+ * call runs on gsrt_stream(), behind the gradient frame that wrote the rows, and blocks until both arrays are complete.
+ * GSRT_E_ARG: a NULL scene, ubo, grad_splat or stats; mixed pointers; width or height 0; a scene with a triangle mesh.
+ * GSRT_E_STATE: before gsrt_build_bvh. */
+gsrt_status gsrt_view_stats_add(gsrt_scene* scene, const gsrt_ubo* ubo, const float* grad_splat, float* stats,
+                                float* radii);
+/* the same, enqueued on gsrt_stream(); device pointers only */
+gsrt_status gsrt_view_stats_add_async(gsrt_scene* scene, const gsrt_ubo* ubo, const float* d_grad_splat, float* d_stats,
+                                      float* d_radii);
+/* gsrt_densify, gsrt_densify_async and gsrt_densify_count in every word of their contracts, with one more term in the
+ * decision, 3DGS's screen-size prune (radii: gsrt_view_stats_add's, n floats, nullable):
+ *     prune = prune || (radii && max_screen_radius > 0 && radii[g] > max_screen_radius)
+ * A NaN radius does not prune. With radii == NULL or max_screen_radius <= 0 the result is gsrt_densify's, bit for bit (the
+ * same kernels run). radii lives on the side, host or device, of the other arrays (on its own side for the count form).
+ * GSRT_E_ARG also: a NaN max_screen_radius. 3DGS uses 20 pixels, after its first opacity reset. */
+gsrt_status gsrt_densify_screen(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* stats,
+                                const float* noise, const gsrt_densify_params* params, const float* radii,
+                                float max_screen_radius, const gsrt_model_arrays* out, int32_t* origin, uint32_t cap,
+                                uint32_t* n_out);
+gsrt_status gsrt_densify_screen_async(gsrt_ctx* ctx, const gsrt_model_arrays* in, uint32_t n, const float* d_stats,
+                                      const float* d_noise, const gsrt_densify_params* params, const float* d_radii,
+                                      float max_screen_radius, const gsrt_model_arrays* out, int32_t* d_origin,
+                                      uint32_t cap, uint32_t* d_n_out);
+gsrt_status gsrt_densify_screen_count(gsrt_ctx* ctx, uint32_t n, const float* scale, const float* opacity,
+                                      const float* stats, const gsrt_densify_params* params, const float* radii,
+                                      float max_screen_radius, uint32_t* n_out);
 /* Counter-based standard normal noise, e.g. gsrt_densify's: out[i], i < count, is a pure function of (seed, stream_id, i).
  * It does not depend on count or on how the work is laid out: a prefix of a longer call is the shorter call bit for bit.
  * The generator is Philox4x32-10 (Salmon et al. 2011, as Random123 states it) with the key (seed lo, seed hi); block j has
@@ -798,6 +839,25 @@ gsrt_status gsrt_model_step_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_ar
                                   const gsrt_model_arrays* v, const gsrt_model_grads* grads, const gsrt_adam_params* adam,
                                   const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
                                   float* grad_raw);
+/* gsrt_model_step with an active SH degree, 3DGS's ramp-up (it starts at 0 and raises the degree every 1000 iterations):
+ * sh_degree in 0..3. The words >= 3 (sh_degree + 1)^2 of each Gaussian's SH row are frozen: those words of raw->sh, m->sh
+ * and v->sh keep their bits, exactly as a group with rate 0 does. The words below are stepped with gsrt_model_step's
+ * arithmetic (lr_sh_dc for coefficient 0, lr_sh_rest for the others; the bias corrections use adam->step either way), and
+ * everything else is gsrt_model_step's: act rows and the scene arrays are written for all words. sh_degree == 3 is
+ * gsrt_model_step bit for bit (that call is this one with 3). A model without SH ignores the degree.
+ * The frames still evaluate all 16 coefficients: a model whose inactive rows are zero (3DGS's initialisation, what
+ * gsrt_train makes of SfM points) receives no gradient there from a frozen zero and renders as the lower degree does; a
+ * model loaded with non-zero inactive rows keeps showing them, frozen.
+ * GSRT_E_ARG also: sh_degree > 3. */
+gsrt_status gsrt_model_step_degree(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* m,
+                                   const gsrt_model_arrays* v, const gsrt_model_grads* grads, const gsrt_adam_params* adam,
+                                   uint32_t sh_degree, const gsrt_model_arrays* act, gsrt_gauss_param* params_out,
+                                   gsrt_aabb* aabbs_out, float* grad_raw);
+gsrt_status gsrt_model_step_degree_async(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw,
+                                         const gsrt_model_arrays* m, const gsrt_model_arrays* v,
+                                         const gsrt_model_grads* grads, const gsrt_adam_params* adam, uint32_t sh_degree,
+                                         const gsrt_model_arrays* act, gsrt_gauss_param* params_out, gsrt_aabb* aabbs_out,
+                                         float* grad_raw);
 /* The activation and packing alone, for step 0 and after a densify: the same arithmetic, the same kernel code path; raw is
  * only read. act, params_out and aabbs_out as for gsrt_model_step, with its pointer and aliasing rules and refusals. */
 gsrt_status gsrt_model_activate(gsrt_ctx* ctx, uint32_t n, const gsrt_model_arrays* raw, const gsrt_model_arrays* act,
@@ -839,15 +899,16 @@ gsrt_status gsrt_lr_expon(float lr_init, float lr_final, float delay_mult, uint3
  * size changes. One trainer per ctx at a time is the tested use; calls on one trainer are serialised by the caller, like
  * every call on its ctx.
  * gsrt_trainer_create: model is the activated model (gsrt_scene_from_model's convention; host or device pointers, all on
- * one side), n of `capacity` rows used. The raw model is gsrt_model_deactivate of it, the moments and statistics are +0,
- * the scene is gsrt_scene_from_model of the model as given, with its BVH built. GSRT_E_ARG: a NULL pointer; a model with
+ * one side), n of `capacity` rows used. The raw model is gsrt_model_deactivate of it, the moments, the statistics and
+ * the screen radii (`capacity` floats) are +0, the active SH degree is 3, the scene is gsrt_scene_from_model of the model as given, with its BVH built. GSRT_E_ARG: a NULL pointer; a model with
  * features; n == 0; capacity < n; capacity > GSRT_MAX_GAUSSIANS.
  * gsrt_trainer_step: one iteration against one view. In order, all on gsrt_stream(): a COR frame of ubo with k
  * (gsrt_render_async; with target_depth a depth frame, gsrt_render_depth_async); gsrt_frame_loss_async of it against
  * target (width x height x target_channels), mask (nullable) and target_depth (nullable) with params: with no option set
  * its first four scalars and its gradient are gsrt_image_loss's; gsrt_render_splat_grad_async (with target_depth
- * gsrt_render_splat_depth_grad_async); gsrt_density_stats_add_async into the trainer's statistics; the matching
- * gsrt_splat*_grad_to_model_async; for a model with SH gsrt_render_sh_grad_async; gsrt_model_step_async with adam, whose
+ * gsrt_render_splat_depth_grad_async); gsrt_view_stats_add_async into the trainer's statistics (the bits
+ * gsrt_density_stats_add_async leaves) and screen radii; the matching gsrt_splat*_grad_to_model_async; for a model with SH
+ * gsrt_render_sh_grad_async; gsrt_model_step_degree_async with adam and the trainer's SH degree, whose
  * .step is ignored: the step number is the trainer's counter + 1. Then gsrt_synchronize, gsrt_scene_update with the
  * step's scene arrays, gsrt_refit_bvh(scene, NULL) and, with SH, gsrt_scene_set_sh, so that the next frame of the scene is
  * the stepped model's; the counter advances. scalars (host, nullable) receives gsrt_frame_loss's six. A step synchronises
@@ -861,9 +922,13 @@ gsrt_status gsrt_lr_expon(float lr_init, float lr_final, float delay_mult, uint3
  * model; gsrt_densify_async with params and the trainer's statistics into the second buffer set; n_out is read back (one
  * uint32) and written to *n_out (nullable). When it exceeds the capacity: GSRT_E_ARG with nothing changed (model, moments,
  * statistics, scene, n). Otherwise gsrt_model_deactivate of the new model, gsrt_model_remap of m and of v by the pass's
- * origin, the statistics set to +0, a new scene with a new BVH created from the new model, and the old scene destroyed:
+ * origin, the statistics and the screen radii set to +0 (as 3DGS resets max_radii2D), a new scene with a new BVH created from the new model, and the old scene destroyed:
  * A SCENE HANDLE OBTAINED FROM gsrt_trainer_scene BEFORE THIS CALL IS DEAD AFTER IT. A densify that prunes every
  * Gaussian (n_out == 0) is refused the same way.
+ * gsrt_trainer_densify_screen: the same sequence with gsrt_densify_screen_async, the trainer's screen radii and
+ * max_screen_radius (NaN: GSRT_E_ARG); gsrt_trainer_densify is this call with 0.
+ * gsrt_trainer_set_sh_degree / gsrt_trainer_sh_degree: the active SH degree of the following steps (gsrt_model_step_degree;
+ * 3 at creation). d > 3 is GSRT_E_ARG; without SH a degree is accepted and ignored.
  * gsrt_trainer_opacity_reset: gsrt_model_opacity_reset on the raw model and the moments, then the scene's arrays from
  * gsrt_model_activate, so that the next frame shows it.
  * gsrt_trainer_rebuild_bvh: gsrt_build_bvh of the scene, for callers whose Gaussians have moved far; a step only refits
@@ -872,10 +937,11 @@ gsrt_status gsrt_lr_expon(float lr_init, float lr_final, float delay_mult, uint3
  * destroyed, updated or given a mesh or features by the caller. gsrt_trainer_info: n, capacity and the step counter (each
  * nullable). gsrt_trainer_state: the device addresses, borrowed and valid until the next gsrt_trainer_densify or
  * gsrt_trainer_destroy, of the raw model, the moments, the gradient tables of the last step and the statistics (n x 2);
- * each nullable. gsrt_trainer_download: after draining the ctx, the raw model into raw_out and / or its activation
+ * each nullable. gsrt_trainer_radii: the screen radii (n floats in use), borrowed under the same rule.
+ * gsrt_trainer_download: after draining the ctx, the raw model into raw_out and / or its activation
  * (gsrt_model_activate) into act_out: host arrays of n rows, sh NULL exactly when the model has none; either may be NULL.
  * Every call returns GSRT_E_ARG for a NULL trainer.
- * Not provided: features in a trainer; SH degree ramp-up; screen-radius pruning; batched views; sharded frames; pose
+ * Not provided: features in a trainer; degree-limited frames (they evaluate all 16 SH coefficients); batched views; sharded frames; pose
  * refinement inside the trainer (gsrt_pose_grad remains callable on the borrowed scene); HIP graph capture of the step. */
 typedef struct gsrt_trainer gsrt_trainer;
 gsrt_status gsrt_trainer_create(gsrt_ctx* ctx, const gsrt_model_arrays* model, uint32_t n, uint32_t capacity,
@@ -886,6 +952,11 @@ gsrt_status gsrt_trainer_step(gsrt_trainer* trainer, const gsrt_ubo* ubo, uint32
                               const gsrt_frame_loss_params* params, const gsrt_adam_params* adam,
                               float scalars[GSRT_FRAME_LOSS_SCALARS]);
 gsrt_status gsrt_trainer_densify(gsrt_trainer* trainer, const gsrt_densify_params* params, uint64_t seed, uint32_t* n_out);
+gsrt_status gsrt_trainer_densify_screen(gsrt_trainer* trainer, const gsrt_densify_params* params, float max_screen_radius,
+                                        uint64_t seed, uint32_t* n_out);
+gsrt_status gsrt_trainer_set_sh_degree(gsrt_trainer* trainer, uint32_t sh_degree);
+gsrt_status gsrt_trainer_sh_degree(const gsrt_trainer* trainer, uint32_t* sh_degree);
+gsrt_status gsrt_trainer_radii(gsrt_trainer* trainer, const float** radii);
 gsrt_status gsrt_trainer_opacity_reset(gsrt_trainer* trainer, float max_opacity);
 gsrt_status gsrt_trainer_rebuild_bvh(gsrt_trainer* trainer);
 gsrt_status gsrt_trainer_scene(gsrt_trainer* trainer, gsrt_scene** scene);
