@@ -4,28 +4,11 @@ import numpy as np
 import pytest
 
 import gsrt
+import lbvh_ref
 import oracle as O
+from lbvh_ref import _expand, _morton_np  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def _expand(v):
-    v = v.astype(np.uint64)
-    v = (v * 0x00010001) & 0xFF0000FF
-    v = (v * 0x00000101) & 0x0F00F00F
-    v = (v * 0x00000011) & 0xC30C30C3
-    v = (v * 0x00000005) & 0x49249249
-    return v.astype(np.uint32)
-
-
-def _morton_np(aabbs):
-    a = aabbs.astype(np.float32)
-    c = np.float32(0.5) * (a[:, :3] + a[:, 3:])
-    lo, hi = c.min(0), c.max(0)
-    ext = hi - lo
-    u = np.where(ext > 0, (c - lo) / np.where(ext > 0, ext, 1), np.float32(0)).astype(np.float32)
-    q = np.clip(u * np.float32(1024.0), 0, 1023).astype(np.uint32)
-    return (_expand(q[:, 0]) << 2) | (_expand(q[:, 1]) << 1) | _expand(q[:, 2])
 
 
 def _check_tree(sc, aabbs):
@@ -71,6 +54,11 @@ def _check_tree(sc, aabbs):
         np.testing.assert_array_equal(info["root_box"], aabbs[0])
     want_root = np.concatenate([aabbs[:, :3].min(0), aabbs[:, 3:].max(0)])
     np.testing.assert_array_equal(info["root_box"], want_root)
+    # and to the radix tree itself: leaf order, Karras's splits and indices, the depth (lbvh_ref.check_tree)
+    res = lbvh_ref.check_tree(nodes, gid, morton, aabbs, info["root_box"], info["max_depth"])
+    if n > 1:
+        for got, want in zip((res["lo"], res["hi"], res["gamma"]), lbvh_ref.karras(lbvh_ref.sort_keys(morton))):
+            np.testing.assert_array_equal(got, want)
     return info
 
 
@@ -120,9 +108,14 @@ def test_refit(ctx):
 
 
 def _check_tree_boxes_only(sc, aabbs):
-    nodes, _, _ = sc.bvh_download()
+    nodes, gid, morton = sc.bvh_download()
     fl = nodes.view(np.float32)
     n = aabbs.shape[0]
+    # a refit keeps the build's order, so the codes are the sorted ones put back: the order must still be stable
+    codes = np.empty(n, np.uint32)
+    codes[gid] = morton
+    info = sc.bvh_info()
+    lbvh_ref.check_tree(nodes, gid, morton, aabbs, info["root_box"], info["max_depth"], codes=codes)
     boxes = {}
     stack, post = [0], []
     while stack:
